@@ -11,7 +11,11 @@ collective; the only exchange is the gather of per-rank timings.  All convergenc
 in the timed region so that every step performs the full work (accepted or rejected steps launch the
 same kernels).
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline`.
+A plain run sets up, warms up, times exactly `--steps` steps, writes the timed path's results when `--dump-outputs DIR`
+is given, and prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the
+timed steps / --steps).  `--full` adds everything else: repeated timed regions (median / p10 / p90), `roofline`,
+`single_window`, `cpu_baseline`, the oracle check and the DOGLEG / configs[2] / fp32 / frontend / frame / strong-scaling
+records.
 """
 from __future__ import annotations
 
@@ -39,9 +43,19 @@ def parse():
     p.add_argument("--total-windows", type=int, default=0,
                    help="BASELINE configs[3]: this many windows IN TOTAL, window i on rank i mod N (strong scaling); "
                         "overrides --windows")
-    p.add_argument("--repeats", type=int, default=50, help="timed regions of --steps iterations each (median / p10 / p90); at least this many")
+    p.add_argument("--chunk-steps", type=int, default=200,
+                   help="the timed steps are issued as iterate() calls of at most this many steps (one captured graph per call length)")
+    p.add_argument("--full", action="store_true",
+                   help="besides the headline: repeated timed regions, roofline, single-window latency, CPU baselines, oracle check, "
+                        "DOGLEG / configs[2] / fp32 / frontend / frame / strong-scaling records")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the timed batch's results (states and summaries of its windows; rank 0's with several "
+                        "ranks) as DIR/<name>.npy")
+    p.add_argument("--repeats", type=int, default=50,
+                   help="--full: timed regions of min(--steps, --chunk-steps) iterations each after the headline (median / p10 / p90); "
+                        "at least this many")
     p.add_argument("--min-timed-s", type=float, default=3.0,
-                   help="the timed regions together cover at least this much wall time (more regions of EXACTLY --steps iterations each are "
+                   help="--full: those regions together cover at least this much wall time (more regions of the same length are "
                         "added: a 20-step region of the default batch is 3 ms, too short for a 1 Hz utilisation sampler to see)")
     p.add_argument("--streams", type=int, default=0, help="sub-batch streams (0 = auto)")
     p.add_argument("--tune", action="append", default=[], metavar="FIELD=VALUE",
@@ -51,12 +65,12 @@ def parse():
     p.add_argument("--landmarks", type=int, default=400)
     p.add_argument("--visibility", type=float, default=1.0)
     p.add_argument("--no-graph", action="store_true", help="eager launches (for rocprofv3 kernel traces)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines and the oracle check")
     p.add_argument("--cpu-iters", type=int, default=0, help="oracle iterations for the CPU baseline (0 = auto ~12 s)")
-    p.add_argument("--profile-steps", type=int, default=20, help="eager per-kernel HIP-event pass for the roofline")
+    p.add_argument("--profile-steps", type=int, default=20, help="--full: eager per-kernel HIP-event pass for the roofline")
     p.add_argument("--fp32", action="store_true", help="BASELINE configs[4]: fp32 Jacobian/Hessian build, fp64 solve (dtype f32+f64)")
-    p.add_argument("--no-extras", action="store_true", help="skip the dogleg / configs[2] / strong-scaling sub-records")
-    p.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 FETCH_SIZE/WRITE_SIZE passes (roofline.traffic = null)")
+    p.add_argument("--no-extras", action="store_true", help="--full: skip the dogleg / configs[2] / strong-scaling sub-records")
+    p.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 FETCH_SIZE/WRITE_SIZE passes (roofline.traffic = null)")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     p.add_argument("--pmc-separate", action="store_true", help=argparse.SUPPRESS)   # (child: the kernels of a sub-batch of a larger upload — not fused)
     return p.parse_args()
@@ -108,8 +122,43 @@ def pmc_traffic(a, kernel, windows=None, separate=False):
             "raw_kb": raw, "correction": "FETCH_SIZE x2 (gfx950), WRITE_SIZE x1 (uncalibrated); separate --pmc passes, eager launches"}
 
 
+def call_lengths(steps, chunk):
+    """the iterate() calls that issue `steps` steps in calls of at most `chunk` steps"""
+    return [chunk] * (steps // chunk) + ([steps % chunk] if steps % chunk else [])
+
+
+def run_steps(batch, steps, chunk):
+    for n in call_lengths(steps, chunk):
+        batch.iterate(n)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, batch, summaries, ids):
+    """What a caller of the timed path receives after its last step: every window's state (okvis_ba_get_state) and summary
+    (okvis_ba_finish), float64, windows concatenated in batch order.  Above DUMP_LIMIT_BYTES a fixed, seeded sample of
+    the windows is written; window_id.npy names the windows written."""
+    n = len(batch)
+    per = [56 * w.n_pose + 72 * w.n_sb + 32 * w.n_lm + 8 * 5 for w in batch.windows]
+    sel = np.arange(n)
+    if sum(per) > DUMP_LIMIT_BYTES:
+        sel = np.sort(np.random.default_rng(0).permutation(n)[:max(1, int(n * DUMP_LIMIT_BYTES / sum(per)) - 1)])
+    states = [batch.get_state(int(i)) for i in sel]
+    out = {"window_id": np.asarray(ids, np.float64)[sel],
+           "pose": np.concatenate([s[0] for s in states]), "speed_bias": np.concatenate([s[1] for s in states]),
+           "landmarks": np.concatenate([s[2] for s in states])}
+    for k in ("initial_cost", "final_cost", "iterations", "successful_steps"):
+        out[k] = np.array([summaries[int(i)][k] for i in sel], np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(v, np.float64))
+
+
 def main():
     a = parse()
+    if a.steps < 1 or a.warmup < 0 or a.chunk_steps < 1:
+        raise SystemExit("--steps >= 1, --warmup >= 0 and --chunk-steps >= 1")
     from okvis_amd import dist as D
     rk = D.Rank.from_env()
     rank, world, local_rank = rk.rank, rk.world, D.local_device(rk)
@@ -155,36 +204,54 @@ def main():
         batch.finish()
         batch.close()
         return
-    if a.warmup > 0:
-        batch.iterate(a.warmup)
-    # build the graph of the timed call outside the timed region
-    if not a.no_graph and a.steps != a.warmup:
-        batch.iterate(a.steps)
-    # R timed regions of EXACTLY --steps iterations each, every one bracketed by barrier + synchronize on both sides
-    # and MAX-reduced over the ranks; the reported value is the MEDIAN region (median + p10/p90)
-    walls, evs = [], []
-    n_regions = max(1, a.repeats)
-    k = 0
-    while k < n_regions:
-        barrier()
-        t0 = time.perf_counter()
-        batch.iterate(a.steps)
-        barrier()
-        t1 = time.perf_counter()
-        walls.append(D.max_over_ranks(dist, t1 - t0))
-        evs.append(batch.last_iterate_ms())
-        k += 1
-        if k == 5 and a.min_timed_s > 0:   # (every rank computes the same count from the max-reduced times)
-            n_regions = max(n_regions, min(20000, int(np.ceil(a.min_timed_s / max(float(np.median(walls)), 1e-6)))))
-    wall = float(np.median(walls))
-    ev_ms = float(np.median(evs))
-    # the one collective of the design: all-gather of the timing records (SURVEY.md section 8e), one record per window
-    # {window_id, iterations, final_cost (filled after finish), seconds}; ranks with fewer windows pad with id -1
-    summaries = None
+    chunk = a.chunk_steps
+    run_steps(batch, a.warmup, chunk)
+    # build the graphs of the timed calls outside the timed region (one per call length the warm-up did not capture)
+    if not a.no_graph:
+        for n in sorted(set(call_lengths(a.steps, chunk)) - set(call_lengths(a.warmup, chunk))):
+            batch.iterate(n)
+    # the timed region: EXACTLY --steps iterations, issued back to back in calls of at most --chunk-steps, bracketed by
+    # barrier + synchronize on both sides and MAX-reduced over the ranks
+    barrier()
+    t0 = time.perf_counter()
+    run_steps(batch, a.steps, chunk)
+    barrier()
+    t1 = time.perf_counter()
+    wall = D.max_over_ranks(dist, t1 - t0)
+    last_call = call_lengths(a.steps, chunk)[-1]
+    ev_ms = batch.last_iterate_ms() / last_call * a.steps   # (HIP events around the last call, scaled to the timed steps)
+    # what a caller of the timed path receives: the summaries of okvis_ba_finish and the states of the windows
+    summaries = batch.finish()
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, batch, summaries, ids)
+
+    # ---- --full: more timed regions of the same batch (median + p10/p90), every one bracketed by
+    #      barrier + synchronize on both sides and MAX-reduced over the ranks
+    rs = min(a.steps, chunk)   # steps of one region of --full (a call length of the timed region: its graph is captured)
+    regions = None
+    if a.full:
+        batch.begin()
+        batch.iterate(rs)
+        walls = []
+        n_regions = max(1, a.repeats)
+        k = 0
+        while k < n_regions:
+            barrier()
+            r0 = time.perf_counter()
+            batch.iterate(rs)
+            barrier()
+            walls.append(D.max_over_ranks(dist, time.perf_counter() - r0))
+            k += 1
+            if k == 5 and a.min_timed_s > 0:   # (every rank computes the same count from the max-reduced times)
+                n_regions = max(n_regions, min(20000, int(np.ceil(a.min_timed_s / max(float(np.median(walls)), 1e-6)))))
+        regions = {"n": len(walls), "steps_each": rs, "statistic": "median",
+                   "ms_per_step": {"median": float(np.median(walls)) * 1e3 / rs, "p10": float(np.percentile(walls, 10)) * 1e3 / rs,
+                                   "p90": float(np.percentile(walls, 90)) * 1e3 / rs, "first": walls[0] * 1e3 / rs,
+                                   "min": min(walls) * 1e3 / rs, "max": max(walls) * 1e3 / rs}}
 
     # ---- per-kernel attribution for the roofline (eager launches bracketed by HIP events on the solver's stream) ----
     roofline = None
-    if rank == 0 and a.profile_steps > 0:
+    if a.full and rank == 0 and a.profile_steps > 0:
         st = solver.check_window(wins[0])
         D_red = int(st["D"])
         n_cu, wg_per_cu = 256, 3
@@ -319,11 +386,11 @@ def main():
             wsat = wins + [synthetic.make_window(a.keyframes, a.landmarks, a.visibility, 20250000 + i) for i in range(nsat - len(wins))]
             bsat = solver.WindowBatch(wsat[:nsat], device=local_rank, options=opt)
             bsat.begin()
-            bsat.iterate(a.warmup)
-            bsat.iterate(a.steps)
+            run_steps(bsat, a.warmup, chunk)
+            bsat.iterate(rs)
             bsat.synchronize()
-            bsat.iterate(a.steps)
-            ms_sat = bsat.last_iterate_ms() / a.steps
+            bsat.iterate(rs)
+            ms_sat = bsat.last_iterate_ms() / rs
             nb_sat = bsat.algorithmic_bytes()
             bsat.finish()
             bsat.close()
@@ -331,14 +398,14 @@ def main():
             fl_sat = {"linearize": 1.5e3 * obs_s, "schur": 3.0 * (6.0 * a.keyframes) ** 2 * lm_s, "solve": nsat * (D_red ** 3 / 3.0 + 2.0 * D_red ** 2)}
             roofline["step_saturated"] = step_record(nsat, ms_sat, nb_sat, fl_sat, wsat[:nsat])
             roofline["step_saturated"]["iterations_per_s"] = nsat / (ms_sat * 1e-3)
-    summaries = batch.finish()
+    fixed = batch.finish() if a.full else None   # after every iteration of --full: thousands, at the fixed point (the oracle check)
     # ---- the timed batch against the oracle, AFTER the timed region (the checker, never the thing measured).  (i) the states the
     #      timed iterations ended in: thousands of Gauss-Newton iterations sit at the fixed point, which the oracle reaches from the
     #      same start (it iterates until its cost is stationary to 1e-14); (ii) the same solver, the same options, the same windows
     #      uploaded again (shapes unchanged: the captured graphs of the timed region are replayed) for optimize(10) from the start —
     #      an iteration-for-iteration comparison.  Four windows sampled over the three sub-batches.
     oracle_check = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.pmc_child and a.total_windows == 0:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not a.pmc_child and a.total_windows == 0:
         from tests import oracle_lib as _ol
         sample = sorted({0, a.windows // 3, (2 * a.windows) // 3, a.windows - 1})
         dev_fix = 0.0
@@ -350,7 +417,7 @@ def main():
                 if prev is not None and abs(r["final_cost"] - prev) <= 1e-14 * prev:
                     break
                 prev = r["final_cost"]
-            dev_fix = max(dev_fix, abs(summaries[i]["final_cost"] - r["final_cost"]) / r["final_cost"])
+            dev_fix = max(dev_fix, abs(fixed[i]["final_cost"] - r["final_cost"]) / r["final_cost"])
         batch.upload(wins)
         s10 = batch.optimize(10)
         dev_10, same_book = 0.0, True
@@ -363,6 +430,8 @@ def main():
                         "identical_iteration_bookkeeping": bool(same_book), "route": batch.launch_route(),
                         "note": "the timed solver object after the timed region, bench options, against oracle/ (CPU restatement pinned "
                                 "to the reference's sources, DESIGN.md section 3); tests/test_gpu_batch64.py checks all 64 windows"}
+    # the one collective of the design: all-gather of the timing records (SURVEY.md section 8e), one record per window
+    # {window_id, iterations, final_cost, seconds of the timed steps by HIP events}; ranks with fewer windows pad with id -1
     n_rec = (a.total_windows + world - 1) // world if a.total_windows > 0 else a.windows
     rec = []
     for k in range(n_rec):
@@ -375,21 +444,21 @@ def main():
     per_rank_ms = [r[3] * 1e3 for r in gathered]
 
     single = None
-    if rank == 0:
+    if a.full and rank == 0:
         # latency of ONE window (configs[1] exactly), graph replay
         b1 = solver.WindowBatch(wins[:1], device=local_rank, options=opt)
         b1.begin()
-        b1.iterate(a.steps)
+        b1.iterate(rs)
         b1.synchronize()
-        b1.iterate(a.steps)
+        b1.iterate(rs)
         ms1 = b1.last_iterate_ms()
         b1.finish()
         late = b1.helper_timeouts()   # solve launches whose helper workgroups were late (summed in the solving workgroup then)
         b1.close()
-        single = {"iterations_per_s": a.steps / (ms1 * 1e-3), "ms_per_iteration": ms1 / a.steps, "helper_timeouts": late}
+        single = {"iterations_per_s": rs / (ms1 * 1e-3), "ms_per_iteration": ms1 / rs, "helper_timeouts": late}
 
     cpu = cpu_mt = cpu_2t = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:   # reported at N=1 only
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:   # reported at N=1 only
         # CPU restatement (oracle/: same algorithm, same policy, g++ -O3), bounded sample of the same workload, on this
         # box's host cores: one thread, and OpenMP over the observation sweep + landmark Schur reduction at all cores.
         # Test infrastructure used here ONLY as the reported baseline, never in the measured path.  It is NOT Ceres
@@ -450,7 +519,7 @@ def main():
     config_c = None
     strong = None
     frontend = None
-    if rank == 0 and not a.no_extras and not a.pmc_child:
+    if a.full and rank == 0 and not a.no_extras and not a.pmc_child:
         dopt = default_options()
         dopt.use_graph = 0 if a.no_graph else 1
         dopt.n_streams = a.streams
@@ -550,7 +619,7 @@ def main():
                                  "per_launch_tflops": {k: fl_c[k] / (plc[k] * 1e-6) / 1e12 for k in fl_c if plc.get(k)},
                                  "algorithmic_bytes_per_iteration": B_c, "achieved_GBps": B_c / t_c / 1e9, "hbm_frac": B_c / t_c / 1e9 / HBM_PEAK_GBS}}
     fp32 = None
-    if rank == 0 and not a.no_extras and not a.pmc_child and not a.fp32:
+    if a.full and rank == 0 and not a.no_extras and not a.pmc_child and not a.fp32:
         # ---- BASELINE configs[4]: fp32 Jacobian / Hessian build, fp64 Schur complement and reduced solve (okvis_ba_options.
         #      fp32_linearize), on the windows and in the mode of the headline line; and what it does to the result in the
         #      reference's mode (DOGLEG, default tolerances, optimize(10) from the perturbed start) on window 0
@@ -559,13 +628,13 @@ def main():
         o32.fp32_linearize = 1
         b32 = solver.WindowBatch(wins, device=local_rank, options=o32)
         b32.begin()
-        b32.iterate(a.warmup)
+        run_steps(b32, a.warmup, chunk)
         b32.synchronize()
         ms32 = []
         for _ in range(9):
-            b32.iterate(a.steps)
+            b32.iterate(rs)
             b32.synchronize()
-            ms32.append(b32.last_iterate_ms() / a.steps)
+            ms32.append(b32.last_iterate_ms() / rs)
         pl32 = {k: float(np.median(v)) * 1e3 for k, v in b32.profile_launches(20).items()}
         b32.finish()
         b32.close()
@@ -589,7 +658,7 @@ def main():
                                     "max_landmark_dev_m": float(np.abs(dev["mixed"][1][2][:, :3] - dev["fp64"][1][2][:, :3]).max())},
                 "study": "profiles/r04_mixed_precision.json (8 seeds, 10 and 30 iterations)"}
     frame_host = None
-    if rank == 0 and not a.no_extras and not a.pmc_child:
+    if a.full and rank == 0 and not a.no_extras and not a.pmc_child:
         # ---- what surrounds the iterations of one frame of the estimator (one window, 8 frames, replay-sized): structure upload,
         #      the same change as an okvis_ba_patch (newest frame replaced), one marginalisation call
         try:
@@ -677,20 +746,20 @@ def main():
                 frame_host["estimator_replay"] = {"error": repr(e)}
         except Exception as e:   # a diagnostic record must never take the bench line with it
             frame_host = {"error": repr(e)}
-    if not a.no_extras and not a.pmc_child and world > 1 and a.total_windows == 0:
+    if a.full and not a.no_extras and not a.pmc_child and world > 1 and a.total_windows == 0:
         # ---- BASELINE configs[3] as written: 64 windows IN TOTAL over the ranks (strong scaling), next to the weak line
         tw = 64
         ids_s = D.shard_windows(tw, rank, world)
         wins_s = [synthetic.make_window(a.keyframes, a.landmarks, a.visibility, 20240923 + i) for i in ids_s]
         bsx = solver.WindowBatch(wins_s, device=local_rank, options=opt)
         bsx.begin()
-        bsx.iterate(a.warmup)
-        bsx.iterate(a.steps)
+        run_steps(bsx, a.warmup, chunk)
+        bsx.iterate(rs)
         ws = []
         for _ in range(max(5, a.repeats // 5)):
             barrier()
             t0 = time.perf_counter()
-            bsx.iterate(a.steps)
+            bsx.iterate(rs)
             bsx.synchronize()
             if dist is not None:
                 dist.barrier()
@@ -701,7 +770,7 @@ def main():
             wmed = float(np.median(ws))
             strong = {"total_windows": tw, "windows_on_rank0": len(wins_s), "ranks": world,
                       "backend": dist.get_backend() if dist is not None else None,
-                      "value": tw * a.steps / wmed, "unit": "iterations/s", "ms_per_step": wmed * 1e3 / a.steps,
+                      "value": tw * rs / wmed, "unit": "iterations/s", "ms_per_step": wmed * 1e3 / rs,
                       "scaling": "strong", "note": "BASELINE configs[3]: 64 independent windows sharded over the GPUs (8 per GPU at 8 GPUs)"}
     if rank == 0:
         n_windows_total = a.total_windows if a.total_windows > 0 else world * a.windows
@@ -721,11 +790,9 @@ def main():
                        "reduced_dim": wins[0].reduced_dim(), "graph": not a.no_graph, "parallelism": f"windows x{world}",
                        **({"tuning": a.tune} if a.tune else {})},
             "hip_event_ms_per_step": max(per_rank_ms) / a.steps,
-            "timed_regions": {"n": len(walls), "steps_each": a.steps, "statistic": "median",
-                              "ms_per_step": {"median": wall * 1e3 / a.steps, "p10": float(np.percentile(walls, 10)) * 1e3 / a.steps,
-                                              "p90": float(np.percentile(walls, 90)) * 1e3 / a.steps,
-                                              "first": walls[0] * 1e3 / a.steps, "min": min(walls) * 1e3 / a.steps,
-                                              "max": max(walls) * 1e3 / a.steps}},
+            "timed_steps": {"steps": a.steps, "calls": len(call_lengths(a.steps, chunk)), "max_steps_per_call": chunk,
+                            "statistic": "wall time of all timed steps / steps"},
+            "timed_regions": regions, "full": a.full,
             "window_records": {"fields": ["window_id", "iterations", "final_cost", "seconds"], "n": len(records),
                                "first": records[:2], "collective": (f"one all_gather, backend {dist.get_backend()}" + (" (= RCCL)" if dist.get_backend() == "nccl" else "")) if dist is not None else "none (1 rank)"},
             "single_window": single, "roofline": roofline, "dogleg": dogleg, "config_C": config_c, "fp32": fp32, "frontend": frontend, "frame_host": frame_host, "strong_scaling_64_windows": strong,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Split a rocprofv3 kernel trace (p_kernel_trace.csv) by launch shape.
 
-bench.py launches the same kernels in three shapes (1 window: `single_window`; windows/2 per stream: the timed
+bench.py --full launches the same kernels in three shapes (1 window: `single_window`; windows/2 per stream: the timed
 loop; all windows: `okvis_ba_profile_iterations`, the eager per-kernel pass behind `roofline`), so the averages of
 `--stats` mix them.  This prints one row per (kernel, windows in the launch) so that the `roofline.avg_launch_us`
 of the bench line can be compared with the profiler's average for the same launch shape.

@@ -5,13 +5,13 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/prof_r02
 mkdir -p $O
 cd $R
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --total-windows 64 --no-pmc --no-cpu-baseline > $O/bench_total64.json 2> $O/bench_total64.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --total-windows 64 --no-pmc --no-cpu-baseline > $O/bench_total64.json 2> $O/bench_total64.err
 cd /tmp && export TMPDIR=/tmp
 for mode in eager graph; do
   flag=""; [ $mode = eager ] && flag="--no-graph"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$mode -o p -- \
-    python $R/bench.py $flag --no-pmc --no-cpu-baseline --repeats 5 > $O/bench_$mode.json 2> $O/bench_$mode.err
+    python $R/bench.py --full $flag --no-pmc --no-cpu-baseline --repeats 5 > $O/bench_$mode.json 2> $O/bench_$mode.err
   f=$(find $O/$mode -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/kernel_stats_$mode.csv
   t=$(find $O/$mode -name "*kernel_trace.csv" | head -1)

@@ -8,7 +8,7 @@ cd /tmp && export TMPDIR=/tmp
 for mode in eager graph; do
   flag=""; [ $mode = eager ] && flag="--no-graph"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$mode -o p -- \
-    python $R/bench.py $flag --no-pmc --no-cpu-baseline --no-extras --repeats 5 $BENCH_ARGS > $O/bench_$mode.json 2> $O/bench_$mode.err
+    python $R/bench.py --full $flag --no-pmc --no-cpu-baseline --no-extras --repeats 5 $BENCH_ARGS > $O/bench_$mode.json 2> $O/bench_$mode.err
   f=$(find $O/$mode -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/kernel_stats_$mode.csv
   t=$(find $O/$mode -name "*kernel_trace.csv" | head -1)

@@ -10,9 +10,9 @@ cd $R
 export TMPDIR=/tmp
 OKVIS_AMD_CHECK_PATCH=1 timeout 1500 python -m pytest tests -m gpu -q > $O/pytest_gpu.log 2>&1
 tail -3 $O/pytest_gpu.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 head -c 300 $O/bench_default.json; echo
-python bench.py --total-windows 64 --no-pmc --no-cpu-baseline --no-extras > $O/bench_total64.json 2> $O/bench_total64.err
+python bench.py --full --total-windows 64 --no-pmc --no-cpu-baseline --no-extras > $O/bench_total64.json 2> $O/bench_total64.err
 for n in 1 2 4 8 16 32 64 128 256; do
   python bench.py --windows $n --no-pmc --no-cpu-baseline --no-extras --profile-steps 0 --repeats 15 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'windows': $n, 'iterations_per_s': d['value'], 'us_per_step': d['ms_per_step']*1e3}))"
 done > $O/batch_sweep.jsonl
@@ -25,7 +25,7 @@ cd /tmp
 for mode in eager graph; do
   flag=""; [ $mode = eager ] && flag="--no-graph"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/$mode -o p -- \
-    python $R/bench.py $flag --no-pmc --no-cpu-baseline --no-extras --repeats 5 > $O/bench_$mode.json 2> $O/bench_$mode.err
+    python $R/bench.py --full $flag --no-pmc --no-cpu-baseline --no-extras --repeats 5 > $O/bench_$mode.json 2> $O/bench_$mode.err
   f=$(find $O/$mode -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && cp $f $O/kernel_stats_$mode.csv
   t=$(find $O/$mode -name "*kernel_trace.csv" | head -1)

@@ -8,7 +8,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 OKVIS_AMD_CHECK_PATCH=1 timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.log 2>&1
 grep -E "passed|failed|FAILED|Error" $OUT/pytest_gpu.log | tail -8
-timeout 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 head -c 300 $OUT/bench_default.json; echo
 python - <<'PY'
 import json

@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 run() {   # name, env...
   local name=$1; shift
-  env "$@" python bench.py --no-extras --no-pmc --no-cpu-baseline --repeats 12 > $O/bench_$name.json 2> $O/bench_$name.err
+  env "$@" python bench.py --full --no-extras --no-pmc --no-cpu-baseline --repeats 12 > $O/bench_$name.json 2> $O/bench_$name.err
   env "$@" python scripts/r04_dogleg_trace.py run > $O/dogleg_$name.txt 2>&1
   python - "$name" <<'PY'
 import json, sys

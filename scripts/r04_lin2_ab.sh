@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 timeout 1200 python -m pytest tests -m gpu -q > $OUT/pytest.log 2>&1
 echo "pytest rc $?" >> $OUT/pytest.log
 grep -E "passed|failed|FAILED|rc " $OUT/pytest.log | tail -12
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 run() { name=$1; shift; ( "$@" ) > $OUT/$name.json 2> $OUT/$name.err; python - <<PY
 import json
 try:

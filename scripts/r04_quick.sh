@@ -6,7 +6,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_golden.py tests/test_gpu_dogleg.py tests/test_gpu_structure_paths.py tests/test_gpu_marginalization.py tests/test_gpu_random_sweep.py -m gpu -q -x > $OUT/pytest.log 2>&1
 grep -E "passed|failed|FAILED|Error" $OUT/pytest.log | tail -8
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 run() { name=$1; shift; ( "$@" ) > $OUT/$name.json 2> $OUT/$name.err; python - <<PY
 import json
 try:

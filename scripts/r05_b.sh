@@ -17,7 +17,7 @@ for v in r4 new; do
   done
 done
 echo "== new, 1 window"; cat $O/stamps_new_1.txt; echo "== new, 22 windows"; cat $O/stamps_new_22.txt
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 for v in r4 new; do
   d=$R/okvis_amd/lib_variants/$v; [ $v = new ] && d=$R/okvis_amd/lib
   OKVIS_AMD_LIB_DIR=$d timeout 300 $B > $O/bench_$v.json 2> $O/bench_$v.err
@@ -32,7 +32,7 @@ except Exception as e:
 PY
 done
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/graph -o p -- python $R/bench.py --no-pmc --no-cpu-baseline --no-extras --repeats 5 > $O/bench_graph.json 2> $O/bench_graph.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/graph -o p -- python $R/bench.py --full --no-pmc --no-cpu-baseline --no-extras --repeats 5 > $O/bench_graph.json 2> $O/bench_graph.err
 t=$(find $O/graph -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python $R/scripts/kernel_trace_by_shape.py $t > $O/kernel_by_shape_graph.csv
 f=$(find $O/graph -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_graph.csv
 rm -rf $O/graph

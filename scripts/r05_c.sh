@@ -12,7 +12,7 @@ timeout 900 python -m pytest tests -m gpu -q --timeout=240 > $O/pytest_gpu.log 2
 grep -E "passed|failed" $O/pytest_gpu.log | tail -3; grep -E "^FAILED|^ERROR" $O/pytest_gpu.log | head -20
 for n in 1 8 22; do timeout 120 python tools/gpu_solve_stamps.py $n > $O/stamps_new_$n.txt 2>&1; done
 echo "== new, 1 window"; cat $O/stamps_new_1.txt; echo "== new, 22 windows"; cat $O/stamps_new_22.txt
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 for v in new; do
   d=$R/okvis_amd/lib
   OKVIS_AMD_LIB_DIR=$d timeout 300 $B > $O/bench_$v.json 2> $O/bench_$v.err

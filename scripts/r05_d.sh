@@ -15,7 +15,7 @@ for v in r4 new; do
   echo "== $v, 1 window"; cat $O/stamps_${v}_1.txt
 done
 echo "== new, 22 windows"; cat $O/stamps_new_22.txt
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 for v in r4 new; do
   d=$R/okvis_amd/lib_variants/$v; [ $v = new ] && d=$R/okvis_amd/lib
   OKVIS_AMD_LIB_DIR=$d timeout 300 $B > $O/bench_$v.json 2> $O/bench_$v.err

@@ -10,7 +10,7 @@ grep -E "passed|failed" $O/pytest_gpu.log | tail -3; grep -E "^FAILED|^ERROR" $O
 for n in 1 22; do timeout 120 python tools/gpu_solve_stamps.py $n > $O/stamps_new_$n.txt 2>&1; done
 grep -E "total|LDL" $O/stamps_new_1.txt $O/stamps_new_22.txt
 timeout 120 python tools/gpu_prof_stamps.py > $O/prof_stamps.txt 2>&1; tail -12 $O/prof_stamps.txt
-B="python bench.py --no-pmc --no-extras --no-cpu-baseline --repeats 12"
+B="python bench.py --full --no-pmc --no-extras --no-cpu-baseline --repeats 12"
 timeout 300 $B > $O/bench_new.json 2> $O/bench_new.err
 python - <<PY
 import json

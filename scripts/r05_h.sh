@@ -21,5 +21,5 @@ PY
 timeout 400 python -m pytest tests -m gpu -q -x --timeout=240 2>&1 | grep -E "passed|failed|^FAILED" | head -3
 for v in nr1 default nr1 default; do
   if [ $v = default ]; then unset OKVIS_AMD_LIB_DIR; else export OKVIS_AMD_LIB_DIR=okvis_amd/lib_variants/nr1; fi
-  python bench.py --no-pmc --no-cpu-baseline --no-extras --repeats 12 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{}).get('launch_us',{}); print('$v: %.0f it/s single %s solve %s' % (d['value'], d.get('single_window',{}).get('iterations_per_s'), r.get('solve',{}).get('median')))"
+  python bench.py --full --no-pmc --no-cpu-baseline --no-extras --repeats 12 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline',{}).get('launch_us',{}); print('$v: %.0f it/s single %s solve %s' % (d['value'], d.get('single_window',{}).get('iterations_per_s'), r.get('solve',{}).get('median')))"
 done

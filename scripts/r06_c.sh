@@ -9,5 +9,5 @@ timeout 600 python -m pytest tests/test_gpu_chain_solve.py -m gpu -q -x -s > $O/
 tail -8 $O/pytest_chain.log
 for n in 1 64; do for m in dense chain; do timeout 120 python tools/gpu_solve_stamps.py $n $m > $O/solve_stamps_${n}_$m.txt 2>&1; done; done
 grep -h "chain solver\|LDL^T solver\|LDL^T + back\|total" $O/solve_stamps_*.txt | cut -c1-200
-timeout 300 python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 20 --min-timed-s 0.5 --profile-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench 64 windows', d['value'], d['ms_per_step'], d['single_window'])"
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 20 --min-timed-s 0.5 --profile-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('bench 64 windows', d['value'], d['ms_per_step'], d['single_window'])"
 echo done

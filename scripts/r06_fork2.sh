@@ -9,7 +9,7 @@ for f in 0 0x200; do
   timeout 300 python tools/gpu_dogleg_phases.py 64 $f > $O/dogleg_phases_$f.txt 2>&1; echo "dogleg, flags $f"; tail -4 $O/dogleg_phases_$f.txt
 done
 for f in 0 0x400; do
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 1.0 --tune flags=$f > $O/bench_$f.json 2> $O/bench_$f.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 1.0 --tune flags=$f > $O/bench_$f.json 2> $O/bench_$f.err
   python -c "
 import json; d = json.load(open('$O/bench_$f.json')); print('GN bench, flags $f: %.0f it/s %.4f ms/step' % (d['value'], d['ms_per_step']))"
 done

@@ -5,7 +5,7 @@ O=$R/gpurun_out/r06_region
 mkdir -p $O
 cd $R
 run() { name=$1; shift
-  timeout 300 python bench.py --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 "$@" > $O/$name.json 2> $O/$name.err
+  timeout 300 python bench.py --full --warmup 5 --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 "$@" > $O/$name.json 2> $O/$name.err
   python -c "
 import json; d = json.load(open('$O/$name.json')); print('%-24s %.0f it/s %.4f ms/step (hip events %.4f)' % ('$name', d['value'], d['ms_per_step'], d['hip_event_ms_per_step']))"
 }

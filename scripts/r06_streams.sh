@@ -7,7 +7,7 @@ cd $R
 for q in default 8 16; do
   for n in 2 3 4 5 6 8; do
     if [ $q = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
-    timeout 200 python bench.py --steps 20 --warmup 5 --streams $n --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 > $O/q${q}_s$n.json 2> $O/q${q}_s$n.err
+    timeout 200 python bench.py --full --steps 20 --warmup 5 --streams $n --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 > $O/q${q}_s$n.json 2> $O/q${q}_s$n.err
     python - <<PY
 import json
 try:

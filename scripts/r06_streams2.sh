@@ -8,7 +8,7 @@ for q in default 8; do
   for m in 1 2 3; do
     for n in 3 4 5 6 8; do
       if [ $q = default ]; then unset GPU_MAX_HW_QUEUES; else export GPU_MAX_HW_QUEUES=$q; fi
-      OKVIS_BA_EXP_PRIO=$m timeout 200 python bench.py --steps 20 --warmup 5 --streams $n --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 > $O/q${q}_m${m}_s$n.json 2> $O/q${q}_m${m}_s$n.err
+      OKVIS_BA_EXP_PRIO=$m timeout 200 python bench.py --full --steps 20 --warmup 5 --streams $n --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 > $O/q${q}_m${m}_s$n.json 2> $O/q${q}_m${m}_s$n.err
       python - <<PY
 import json
 try:

@@ -6,7 +6,7 @@ mkdir -p $O
 cd $R
 run() {  # name windows args...
   name=$1; w=$2; shift 2
-  timeout 300 python bench.py --steps 20 --warmup 5 --windows $w --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 "$@" > $O/$name.json 2> $O/$name.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --windows $w --no-pmc --no-cpu-baseline --no-extras --repeats 5 --min-timed-s 0.5 "$@" > $O/$name.json 2> $O/$name.err
   python - <<PY
 import json
 try:

@@ -99,10 +99,10 @@ def test_values_that_reach_the_backend(config):
         assert np.array_equal(cam["intr"][:8], synthetic.EUROC_INTR[k, :8]) and not cam["intr"][8:].any()
 
 
-REFERENCE_CONFIG = "/root/reference/config/config_fpga_p2_euroc.yaml"
+# the reference's config/config_fpga_p2_euroc.yaml, unchanged (a settings file, stored as a fixture)
+REFERENCE_CONFIG = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_fpga_p2_euroc.yaml")
 
 
-@pytest.mark.skipif(not os.path.exists(REFERENCE_CONFIG), reason="the reference tree is not here")
 def test_the_references_own_configuration_file():
     text = open(REFERENCE_CONFIG).read()
     ours, theirs = _plain(recording.yaml_to_json(text)), _pyyaml(text)
