@@ -176,7 +176,8 @@ typedef struct okvis_ba_window {
  * linked-in backend must not change its behaviour with its host process's environment, so they are fields now, set per solver
  * with okvis_ba_set_options BEFORE the upload they are meant for (okvis_ba_check_window[_lists] take them through their options
  * argument).  All zero = the defaults.  None of them changes what is computed; a different grouping of a sum moves its rounding.
- * Every field is driven against the oracle by tests/test_gpu_tuning.py.  The library reads ONE environment variable, OKVIS_BA_DEBUG
+ * The fields are driven against the oracle by tests/test_gpu_switches.py, test_gpu_separate_launch.py, test_gpu_chain_solve.py,
+ * test_gpu_structure_paths.py and test_index_build.py.  The library reads ONE environment variable, OKVIS_BA_DEBUG
  * (a comma-separated list of print-only diagnostics: "build", "upload", "marg", "arena=<file>"); it never changes a result.
  */
 #define OKVIS_BA_TUNE_SCHUR_DECIDES 0x1u      /* the separate Schur launch takes the trust-region decision itself (rounds 1-4) instead of

@@ -30,8 +30,8 @@ using namespace ba;
 
 // One translation unit, in parts:
 #include "capi_solver.inc"        // records: HostWin, Arena, okvis_ba_solver, DebugWord
-#include "capi_index_build.inc"   // build_window and its helpers (the index build)
-#include "capi_launch.inc"        // LDS sizes, launches of one iteration, sub-batch fork / join
+#include "capi_index_build.inc"   // batch_layout, build_batch, build_window and its helpers (the index build)
+#include "capi_launch.inc"        // LDS sizes, the launch plan (make_plan) and the launches, sub-batch fork / join
 // below: life cycle, options, upload / patch, state, begin / iterate / finish, queries and downloads, measurement hooks; then
 // capi_standalone.inc and capi_marginalize.inc
 
@@ -110,60 +110,13 @@ int okvis_ba_create(okvis_ba_solver** out, int device) {
     s->wins_capacity = 1;
   }
   // kernels may use more than the default 64 KB of dynamic LDS
-  auto lds = [&](const void* f, size_t bytes) {
-    if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  auto lds = [&](auto f, size_t bytes) {
+    if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(f), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
   };
-  lds(reinterpret_cast<const void*>(&linearize_kernel<true, double, false>), std::max(lin_smem(true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<true, double, true>), std::max(lin_smem(true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<true, float, false>), std::max(lin_smem(true, true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<true, float, true>), std::max(lin_smem(true, true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<false, float, false>), std::max(lin_smem(false, true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<false, float, true>), std::max(lin_smem(false, true), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<false, double, false>), std::max(lin_smem(false), small_smem()));
-  lds(reinterpret_cast<const void*>(&linearize_kernel<false, double, true>), std::max(lin_smem(false), small_smem()));
-  {
-    const size_t l2d = std::max(lin2_smem(MAX_D, true, false), small_smem()), l2f = std::max(lin2_smem(MAX_D, true, true), small_smem());
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<double, false, false, 3>), l2d);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<double, false, false, 4, 14>), l2d);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<double, false, true>), l2d);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<double, true, false>), l2d);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<double, true, true>), l2d);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<float, false, false, 3>), l2f);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<float, false, false, 4, 14>), l2f);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<float, false, true>), l2f);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<float, true, false>), l2f);
-    lds(reinterpret_cast<const void*>(&linearize2_kernel<float, true, true>), l2f);
-    lds(reinterpret_cast<const void*>(&small_kernel), small_smem());
-    lds(reinterpret_cast<const void*>(&small_prepare_kernel), small_smem());
-  }
-  lds(reinterpret_cast<const void*>(&schur_ride_kernel<3>), std::max((size_t)sch2_tile_doubles(TILE_DIM, sch2_nlb(TILE_DIM, 9216)) * sizeof(double), small_eval_smem()));
-  lds(reinterpret_cast<const void*>(&schur_mfma_kernel<3>), (size_t)sch2_tile_doubles(TILE_DIM, sch2_nlb(TILE_DIM, 9216)) * sizeof(double));
-  lds(reinterpret_cast<const void*>(&schur_mfma_kernel<9>), (size_t)sch2_tile_doubles(TILE_DIM, sch2_nlb(TILE_DIM, 9216)) * sizeof(double));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&schur_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(2 * SCHUR_LM_BATCH * TILE_DIM * 3 * sizeof(double)));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            std::max((int)solve_smem(((MAX_D_LDS + 5) / 6) * 6, false), SOLVE_LDS_LIMIT));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            std::max((int)solve_smem(((MAX_D_LDS + 5) / 6) * 6, false), SOLVE_LDS_LIMIT));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SOLVE_LDS_LIMIT_CHAIN);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<false, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SOLVE_LDS_LIMIT_CHAIN);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&solve_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)solve_smem(((MAX_D + 5) / 6) * 6, true));
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&chol_tiles_window_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            CT_SMEM_DOUBLES * 8);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, MARG_LDS_DOUBLES * 8);
-  if (e == hipSuccess)
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&marg_dense_kernel<MAX_D, MAX_MARG_DIM>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, MARG_LDS_DOUBLES_LARGE * 8);
+  for (const auto& k : plan_kernels()) lds(k.first, k.second);
+  lds(&chol_tiles_window_kernel, CT_SMEM_DOUBLES * 8);
+  lds(&marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
+  lds(&marg_dense_kernel<MAX_D, MAX_MARG_DIM>, MARG_LDS_DOUBLES_LARGE * 8);
 
   if (e != hipSuccess) {
     int code = OKVIS_BA_HIP_ERROR_BASE + (int)e;
@@ -212,11 +165,11 @@ int okvis_ba_set_options(okvis_ba_solver* s, const okvis_ba_options* opt) {
   }
   // unchanged options (the host class sets them before every upload): nothing to do - every upload writes the device copy
   if (std::memcmp(opt, &s->opt, sizeof(*opt)) == 0) return OKVIS_BA_OK;
-  // captured graphs name the kernels and the launch sequence of the options they were captured under: another linearise
-  // kernel (fp32) or another trust-region strategy (the DOGLEG graphs carry the iteration-budget kernel) invalidates them
-  if (opt->fp32_linearize != s->opt.fp32_linearize || opt->strategy != s->opt.strategy || opt->gauss_newton != s->opt.gauss_newton)
-    destroy_graphs(s);
   s->opt = *opt;
+  if (s->uploaded) {   // the launches of the new options (captured graphs hold those of the old ones)
+    s->plan = make_plan(s->layout, s->max, s->opt, (int)s->wins.size());
+    keep_graphs(s);
+  }
   s->stagger_ticks = (long long)(opt->tuning.stagger_us > 0 ? opt->tuning.stagger_us : opt->tuning.stagger_us < 0 ? 0 : 10) * 100;   // (round 6: 5 / 10 us 479 k, 20 us 476 k, 30 us 474 k, none 465 k at 64 windows)
   HIP_TRY(hipSetDevice(s->device));
   OptD d = make_optd(s->opt, (int)s->wins.size());
@@ -371,32 +324,10 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   const int n_pre = pre_launch(s, n_windows, windows, &pre_where, &pre_src);   // (runs on the device while the lists are built)
   const bool dbg_t = debug_word().upload;
   const auto t_u0 = std::chrono::steady_clock::now();
-  // the piece path of the linearise launch (ba_linearize2.hpp) unless a window of the batch does not fit it (free extrinsics,
-  // a landmark with more than LIN2_PIECES pieces) or options.reserved0 bit 3 asks for the staged kernel
-  bool lin2 = !(s->opt.reserved0 & 8);
-  // the reduced solve of the LDS-resident windows: the chain solver (ba_chain.hpp) when the options allow it and EVERY such
-  // window of the batch fits it, else the dense LDL^T for all of them (one kernel instantiation per launch)
-  int chain_min = 1;
-  bool chain = want_chain(s->opt, &chain_min);
-  for (int i = 0; i < n_windows; ++i) {
-    int rc = build_window(windows[i], s->opt, A, wins[i], n_windows, lin2, chain);
-    if (rc == BW_LIN2_UNFIT || rc == BW_CHAIN_UNFIT) {   // start over with the staged kernel's lists / the dense solver's layout for every window
-      if (rc == BW_LIN2_UNFIT) lin2 = false;
-      else chain = false;
-      A.size = 0;
-      A.zsize = 0;
-      i = -1;
-      continue;
-    }
-    if (rc != OKVIS_BA_OK) return rc;
-  }
-  s->lin2 = lin2;
-  {
-    // IMU / prior factors in a launch of their own when the batch fills the device (then four linearise workgroups share a
-    // CU); one launch for everything when a few windows wait for one another's latency
-    const int split_min = s->opt.tuning.split_small_min > 0 ? s->opt.tuning.split_small_min : SMALL_BATCH_WINDOWS;
-    s->split_small = lin2 && n_windows >= split_min;
-  }
+  // the layout the batch asks for, then the index build: the piece path unless a window does not fit it (free extrinsics, a landmark
+  // with more than LIN2_PIECES pieces), the chain solver where allowed if EVERY LDS-resident window fits it, else the dense LDL^T
+  BatchLayout L = batch_layout(s->opt, n_windows);
+  if (int rc = build_batch(windows, n_windows, s->opt, L, A, wins.data())) return rc;
   const auto t_u1 = std::chrono::steady_clock::now();
   // grow-only device allocations: the per-frame re-upload of okvis_amd::Estimator must not pay hipFree/hipMalloc
   if (A.host.size() < A.size) A.host.resize(A.size, 0);
@@ -425,44 +356,37 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   // (the control records follow the records of the windows that are there: n_windows of them, not the capacity)
   s->d_ctrl = reinterpret_cast<CtrlSlot*>(reinterpret_cast<unsigned char*>(s->d_opt) + ctrl_off((size_t)n_windows));
   std::vector<WinPtrs> ptrs(n_windows);
-  s->max_group = s->max_imu = s->max_schur_blocks = s->max_lm = s->max_Dpad = s->max_Dp = s->max_spart_stride = 0;
-  s->max_Dpad_small = s->max_Dpad_large = 0;
-  s->max_chain_doubles = 0;
-  s->chain = false;
-  s->any_ext = false;
-  s->group_chunks = true;
-  s->spec_schur = true;
-  s->fp32_at_upload = s->opt.fp32_linearize != 0;
+  BatchMax M;
+  M.group_chunks = M.spec_schur = true;
   for (int i = 0; i < n_windows; ++i) {
     relocate(wins[i].ptrs, s->d_arena, zbase, s->opt.debug_arrays);
     wins[i].ptrs.ctrl = (decltype(wins[i].ptrs.ctrl))(&s->d_ctrl[i].c);   // (not the arena's slot: see CtrlSlot)
     ptrs[i] = wins[i].ptrs;
     const WinPtrs& P = ptrs[i];
-    s->max_group = std::max(s->max_group, P.n_group);
-    s->max_imu = std::max(s->max_imu, P.n_imu);
-    s->max_schur_blocks = std::max(s->max_schur_blocks, P.n_chunk * (P.n_tile * (P.n_tile + 1) / 2));
-    s->max_spart_stride = std::max(s->max_spart_stride, P.spart_stride);
-    s->max_lm = std::max(s->max_lm, P.n_lm);
-    s->max_Dpad = std::max(s->max_Dpad, ((P.D + 5) / 6) * 6);
-    s->max_Dp = std::max(s->max_Dp, P.Dp);
+    M.group = std::max(M.group, P.n_group);
+    M.imu = std::max(M.imu, P.n_imu);
+    M.schur_blocks = std::max(M.schur_blocks, P.n_chunk * (P.n_tile * (P.n_tile + 1) / 2));
+    M.lm = std::max(M.lm, P.n_lm);
+    M.Dp = std::max(M.Dp, P.Dp);
+    M.chunks = std::max(M.chunks, P.n_chunk);
     if (P.D <= MAX_D_LDS) {
-      s->max_Dpad_small = std::max(s->max_Dpad_small, ((P.D + 5) / 6) * 6);
+      M.Dpad_small = std::max(M.Dpad_small, ((P.D + 5) / 6) * 6);
       if (P.chain) {
-        s->chain = true;
-        s->max_chain_doubles = std::max(s->max_chain_doubles, LChain::make(P.D, P.Dp).total);
+        M.chain = true;
+        M.chain_doubles = std::max(M.chain_doubles, LChain::make(P.D, P.Dp).total);
       }
     } else
-      s->max_Dpad_large = std::max(s->max_Dpad_large, ((P.D + 5) / 6) * 6);
-    s->any_ext = s->any_ext || P.has_ext;
-    s->group_chunks = s->group_chunks && wins[i].group_chunks;
-    s->spec_schur = s->spec_schur && wins[i].spec_ok;
+      M.Dpad_large = std::max(M.Dpad_large, ((P.D + 5) / 6) * 6);
+    M.any_ext = M.any_ext || P.has_ext;
+    M.group_chunks = M.group_chunks && wins[i].group_chunks;
+    M.spec_schur = M.spec_schur && wins[i].spec_ok;
   }
   // a batch is fused as a whole or not at all; a batch that is not takes the decision-free Schur launch as a whole or not at all;
   // otherwise one set of partials for everybody
-  if (s->group_chunks) s->spec_schur = false;
-  if (!s->group_chunks)
+  if (M.group_chunks) M.spec_schur = false;
+  if (!M.group_chunks)
     for (int i = 0; i < n_windows; ++i) ptrs[i].fuse_fast = 0;
-  if (!s->group_chunks && !s->spec_schur)
+  if (!M.group_chunks && !M.spec_schur)
     for (int i = 0; i < n_windows; ++i) ptrs[i].spart_buf_stride = 0;
   {
     // one copy: option record, window records and the (zeroed) control records behind them
@@ -485,20 +409,11 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
       HIP_TRY(hipGetLastError());
     }
   s->wins.swap(wins);
-  // ---- sub-batches: opt.n_streams (0 = auto).  Measured at 64 windows (scripts/sweep_streams.sh, r02): 1 stream 272 k,
-  //      2: 300 k, 3: 325 k, 4: 198 k window-iterations/s — the streams of the process that have work, or ever had, must not
-  //      exceed four (whatever GPU_MAX_HW_QUEUES and the stream priorities say: scripts/r06_streams.sh, r06_streams2.sh,
-  //      tools/micro/stream_concurrency.hip) ----
+  s->layout = L, s->max = M;
+  s->plan = make_plan(L, M, s->opt, n_windows);
   {
-    // measured on MI355X / ROCm 7.2 (profiles/r01_notes.md): branches inside ONE captured graph are not
-    // overlapped, but two independently replayed graphs on two streams are (+29 % at 64 windows); more
-    // than two streams lose again
-    // (round 6, profiles/r06_notes.md: from 128 windows on two streams are ahead again — 128: 613 k against 601 k, 256: 692 k
-    //  against 659 k, 512: 727 k against 700 k window-iterations/s; 96 windows: three, 568 k against 549 k)
-    int nsub = s->opt.n_streams > 0 ? s->opt.n_streams : (n_windows >= 128 ? 2 : (n_windows >= 56 ? 3 : (n_windows >= 8 ? 2 : 1)));   // (48 windows: 2 is better)
-    nsub = std::max(1, std::min(nsub, n_windows));
-    s->sub_begin.assign(nsub + 1, 0);
-    for (int k = 0; k <= nsub; ++k) s->sub_begin[k] = (int)((int64_t)n_windows * k / nsub);
+    // the sub-batches' streams (the first is the solver's own)
+    const int nsub = (int)s->plan.subs.size();
     const bool same = (nsub > 1 ? (int)s->sub_streams.size() == nsub : s->sub_streams.empty());
     if (!same) {
       for (auto st : s->sub_streams)
@@ -522,21 +437,7 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
       }
     }
   }
-  {
-    // Captured graphs hold grid sizes, LDS sizes, kernel choices and the device addresses of the window / option records —
-    // not the windows themselves.  A re-upload that leaves all of that unchanged (the same number of equally shaped windows:
-    // the per-frame pattern of a batch service, the dogleg record of bench.py) keeps them; anything else drops them.
-    std::vector<int64_t> sig = {n_windows, s->max_group, s->max_imu, s->max_schur_blocks, s->max_lm, s->max_Dpad, s->max_Dp,
-                                s->max_Dpad_small, s->max_Dpad_large, s->max_spart_stride, s->any_ext, s->group_chunks, s->spec_schur, s->lin2, s->split_small, s->chain, s->max_chain_doubles,
-                                s->fp32_at_upload, (int64_t)(intptr_t)s->d_wins, (int64_t)(intptr_t)s->d_opt,
-                                (int64_t)s->sub_streams.size()};
-    for (int b : s->sub_begin) sig.push_back(b);
-    for (auto st : s->sub_streams) sig.push_back((int64_t)(intptr_t)st);
-    if (sig != s->launch_sig) {
-      destroy_graphs(s);
-      s->launch_sig.swap(sig);
-    }
-  }
+  keep_graphs(s);
   s->uploaded = true;
   s->evaluated = false;
   s->res_staged = false;
@@ -579,19 +480,8 @@ int okvis_ba_check_window(const okvis_ba_window* w, const okvis_ba_options* opt,
       if (on) a.swap(b);
     }
   } give_back{A.host, kept, !dumping};
-  // the route okvis_ba_upload takes for a one-window batch: the piece path's lists unless the window does not fit them
-  int chain_min = 1;
-  bool chain = want_chain(o, &chain_min), lin2 = !(o.reserved0 & 8);
-  int rc;
-  for (;;) {   // (the route okvis_ba_upload takes for a one-window batch)
-    A.size = 0;
-    A.zsize = 0;
-    rc = build_window(*w, o, A, H, 1, lin2, chain);
-    if (rc == BW_LIN2_UNFIT) lin2 = false;
-    else if (rc == BW_CHAIN_UNFIT) chain = false;
-    else break;
-  }
-  if (rc != OKVIS_BA_OK) return rc;
+  BatchLayout L = batch_layout(o, 1);   // (the route okvis_ba_upload takes for a one-window batch)
+  if (int rc = build_batch(w, 1, o, L, A, &H)) return rc;
   if (dumping) {   // diagnostics (OKVIS_BA_DEBUG=arena=<file>): the index build's output, byte for byte
     if (FILE* f = std::fopen(debug_word().arena.c_str(), "wb")) {
       std::fwrite(A.host.data(), 1, A.size, f);
@@ -613,18 +503,8 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
   if (opt) o = *opt; else okvis_ba_default_options(&o);
   Arena A;
   HostWin H;
-  int chain_min = 1;
-  bool chain = want_chain(o, &chain_min), lin2 = !(o.reserved0 & 8);
-  int rc;
-  for (;;) {
-    A.size = 0;
-    A.zsize = 0;
-    rc = build_window(*w, o, A, H, n_windows, lin2, chain);
-    if (rc == BW_LIN2_UNFIT) lin2 = false;
-    else if (rc == BW_CHAIN_UNFIT) chain = false;
-    else break;
-  }
-  if (rc != OKVIS_BA_OK) return rc;
+  BatchLayout L = batch_layout(o, n_windows);   // (the window as one of a batch of n_windows)
+  if (int rc = build_batch(w, 1, o, L, A, &H)) return rc;
   const WinPtrs& P = H.ptrs;   // (the pointer members still hold offsets into the arena's data part)
   const unsigned char* base = A.host.data();
   auto at = [&](const void* field) { return base + reinterpret_cast<size_t>(field); };
@@ -943,7 +823,7 @@ int okvis_ba_iterate(okvis_ba_solver* s, int n) {
   s->slots += n;
   HIP_TRY(hipEventRecord(s->ev0, s->stream));
   const int nsub = (int)s->sub_streams.size();
-  if (s->opt.use_graph && nsub > 1) {
+  if (s->plan.graph && nsub > 1) {
     // one graph per sub-batch, each replayed on its own stream (independent launches overlap; branches
     // inside ONE captured graph were measured not to)
     HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
@@ -952,10 +832,9 @@ int okvis_ba_iterate(okvis_ba_solver* s, int n) {
       auto it = s->sub_graphs.find({n, k});
       if (it == s->sub_graphs.end()) {
         hipGraph_t graph = nullptr;
-        const Sub b{s->sub_streams[k], s->sub_begin[k], s->sub_begin[k + 1] - s->sub_begin[k]};
+        const Sub b = sub(s->sub_streams[k], s->plan.subs[k]);
         HIP_TRY(hipStreamBeginCapture(b.st, hipStreamCaptureModeRelaxed));
-        hipError_t e = launch_budget(s, b, n);
-        for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, b);
+        hipError_t e = launch_chain(s, b, n, n);
         hipError_t e2 = hipStreamEndCapture(b.st, &graph);
         if (e != hipSuccess) HIP_TRY(e);
         HIP_TRY(e2);
@@ -977,7 +856,7 @@ int okvis_ba_iterate(okvis_ba_solver* s, int n) {
       HIP_TRY(hipEventRecord(s->sub_events[k], s->sub_streams[k]));
       HIP_TRY(hipStreamWaitEvent(s->stream, s->sub_events[k], 0));
     }
-  } else if (s->opt.use_graph) {
+  } else if (s->plan.graph) {
     hipGraphExec_t exec = nullptr;
     auto it = s->graphs.find(n);
     if (it == s->graphs.end()) {
@@ -1025,8 +904,8 @@ int okvis_ba_finish(okvis_ba_solver* s, okvis_ba_summary* summaries) {
   size_t res_bytes = 0;
   auto finalize = [&]() -> int {
     HIP_TRY(launch_imu_take_back(s, 0, (int)s->wins.size()));
-    if (s->max_lm > 0) {
-      hipLaunchKernelGGL(quality_kernel, dim3((s->max_lm + 255) / 256, (unsigned)s->wins.size()), dim3(256), 0, s->stream, s->d_wins);
+    if (s->max.lm > 0) {
+      hipLaunchKernelGGL(quality_kernel, dim3((s->max.lm + 255) / 256, (unsigned)s->wins.size()), dim3(256), 0, s->stream, s->d_wins);
       HIP_TRY(hipGetLastError());
     }
     if (s->wins.size() == 1) {
@@ -1160,42 +1039,24 @@ int okvis_ba_helper_timeouts(okvis_ba_solver* s, int64_t* count) {
 int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route) {
   if (!s || !route) return OKVIS_BA_ERR_ARG;
   if (!s->uploaded) return OKVIS_BA_ERR_STATE;
-  for (int i = 0; i < OKVIS_BA_ROUTE_COUNT; ++i) route[i] = 0;
-  const int n = (int)s->wins.size(), nsub = std::max<int>(1, (int)s->sub_streams.size());
-  int sub_max = n;
-  if (s->sub_streams.size() > 1) {
-    sub_max = 0;
-    for (size_t k = 0; k + 1 < s->sub_begin.size(); ++k) sub_max = std::max(sub_max, s->sub_begin[k + 1] - s->sub_begin[k]);
-  }
-  route[OKVIS_BA_ROUTE_WINDOWS] = n;
-  route[OKVIS_BA_ROUTE_FUSED] = fused(s) ? 1 : 0;
-  route[OKVIS_BA_ROUTE_DECISION_FREE_SCHUR] = spec_schur_now(s) ? 1 : 0;
-  route[OKVIS_BA_ROUTE_PIECE_PATH] = s->lin2 ? 1 : 0;
-  route[OKVIS_BA_ROUTE_SPLIT_SMALL] = s->split_small ? 1 : 0;
-  route[OKVIS_BA_ROUTE_SUB_BATCHES] = nsub;
-  route[OKVIS_BA_ROUTE_SUB_BATCH_MAX_WINDOWS] = sub_max;
-  {   // the kernel launch_schur picks (same conditions, nothing launched)
-    const int trows = std::min(TILE_DIM, s->max_Dp);
-    int k = 0;
-    if (s->max_schur_blocks > 0 && !fused(s)) {
-      if (!s->any_ext && !(s->opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_VALU) &&
-          (trows + 1 <= SCH2_MAXT_SMALL_ROWS || (s->opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_MFMA_LARGE)))
-        k = trows + 1 <= SCH2_MAXT_SMALL_ROWS ? 2 : 3;
-      else
-        k = 1;
-    }
-    route[OKVIS_BA_ROUTE_SCHUR_KERNEL] = k;
-  }
-  route[OKVIS_BA_ROUTE_SOLVE_DBUF] = (s->max_Dpad_small > 0 && (s->group_chunks || s->spec_schur)) ? 1 : 0;
-  route[OKVIS_BA_ROUTE_SOLVE_TILED] = s->max_Dpad_large > 0 ? 1 : 0;
-  route[OKVIS_BA_ROUTE_SOLVE_HELPERS] = sub_max <= SOLVE_HELPED_MAX_WINDOWS ? SOLVE_HELPERS : 0;
-  route[OKVIS_BA_ROUTE_GRAPH] = s->opt.use_graph ? 1 : 0;
-  int ch = 0;
-  for (const HostWin& H : s->wins) ch = std::max(ch, H.n_chunk);
-  route[OKVIS_BA_ROUTE_MAX_CHUNKS] = ch;
+  const LaunchPlan& p = s->plan;
+  const Extent& big = *std::max_element(p.subs.begin(), p.subs.end(), [](const Extent& a, const Extent& b) { return a.nw < b.nw; });
+  route[OKVIS_BA_ROUTE_WINDOWS] = p.whole.nw;
+  route[OKVIS_BA_ROUTE_FUSED] = p.fused;
+  route[OKVIS_BA_ROUTE_DECISION_FREE_SCHUR] = p.nodec;
+  route[OKVIS_BA_ROUTE_PIECE_PATH] = p.lin2;
+  route[OKVIS_BA_ROUTE_SPLIT_SMALL] = p.split_small;
+  route[OKVIS_BA_ROUTE_SUB_BATCHES] = (int)p.subs.size();
+  route[OKVIS_BA_ROUTE_SUB_BATCH_MAX_WINDOWS] = big.nw;
+  route[OKVIS_BA_ROUTE_SCHUR_KERNEL] = p.schur.k == SCHUR_RIDE3 ? SCHUR_MFMA3 : p.schur.k;   // (the riding kernel is schur_mfma_kernel<3>'s)
+  route[OKVIS_BA_ROUTE_SOLVE_DBUF] = p.solve.k == SOLVE_DENSE_DBUF || p.solve.k == SOLVE_CHAIN_DBUF;
+  route[OKVIS_BA_ROUTE_SOLVE_TILED] = p.tiled.k != SOLVE_NONE;
+  route[OKVIS_BA_ROUTE_SOLVE_HELPERS] = big.helpers;
+  route[OKVIS_BA_ROUTE_GRAPH] = p.graph;
+  route[OKVIS_BA_ROUTE_MAX_CHUNKS] = s->max.chunks;
   route[OKVIS_BA_ROUTE_SLOTS] = (int32_t)std::min<long long>(s->slots, 0x7fffffff);
-  route[OKVIS_BA_ROUTE_SMALL_RIDES] = small_rides(s) ? 1 : 0;
-  route[OKVIS_BA_ROUTE_SOLVE_MODE] = s->max_Dpad_small > 0 ? (s->chain ? OKVIS_BA_SOLVE_CHAIN : OKVIS_BA_SOLVE_DENSE) : 0;
+  route[OKVIS_BA_ROUTE_SMALL_RIDES] = p.rides;
+  route[OKVIS_BA_ROUTE_SOLVE_MODE] = p.solve.k == SOLVE_NONE ? 0 : p.solve.k >= SOLVE_CHAIN ? OKVIS_BA_SOLVE_CHAIN : OKVIS_BA_SOLVE_DENSE;
   return OKVIS_BA_OK;
 }
 int okvis_ba_pair_count(okvis_ba_solver* s, int w, int32_t* n_pair) {

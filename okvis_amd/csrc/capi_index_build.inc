@@ -124,14 +124,42 @@ constexpr int BW_CHAIN_UNFIT = -1001;
 // 8 + 3 (the sliding window of the replay): 1.32 — two sweeps, the pose system's update and the back-substitution are fixed costs
 // that a short chain does not earn back.
 constexpr int CHAIN_AUTO_MIN_BLOCKS = 8;
-// the reduced solve the options ask for: 0 = dense, 1 = chain where every window has at least `*min_blocks` blocks in a chain
-inline bool want_chain(const okvis_ba_options& o, int* min_blocks) {
-  *min_blocks = o.tuning.solve_mode == OKVIS_BA_SOLVE_CHAIN ? 1 : CHAIN_AUTO_MIN_BLOCKS;
-  return o.tuning.solve_mode != OKVIS_BA_SOLVE_DENSE;
+
+// The layout a batch of n_windows asks for under the options o (BatchLayout), before any window is looked at
+BatchLayout batch_layout(const okvis_ba_options& o, int n_windows) {
+  BatchLayout L;
+  // the piece path unless options.reserved0 bit 3 asks for the staged kernel; the chain solve where the options allow it (every
+  // LDS-resident window then needs at least chain_min speed/bias blocks in a chain)
+  L.lin2 = !(o.reserved0 & 8);
+  L.chain = o.tuning.solve_mode != OKVIS_BA_SOLVE_DENSE;
+  L.chain_min = o.tuning.solve_mode == OKVIS_BA_SOLVE_CHAIN ? 1 : CHAIN_AUTO_MIN_BLOCKS;
+  // fused mode (the linearise workgroup reduces its own group, no Schur launch: DOGLEG and fixed-radius runs) up to
+  // fused_max_windows; options.reserved0 bit 2 keeps the separate launch (A/B switch)
+  L.fuse = !(o.reserved0 & 4) && o.schur_lm_per_block == 0 && n_windows <= fused_max_windows(o) && decision_free(o);
+  L.spec = !(o.tuning.flags & OKVIS_BA_TUNE_SCHUR_DECIDES) && schur_mfma_allowed(o) && o.schur_lm_per_block == 0 && decision_free(o);
+  // landmarks per Schur workgroup: 48 (three staged batches of 16) keeps the workgroup count low when many windows share
+  // the device; a few windows have the device to themselves and finish sooner with 32 (measured, tools/gpu_chunk_diag.py:
+  // one window 114.7 vs 119.7 us per iteration, 64 windows 239 vs 217)
+  L.schur_lm = std::min(o.schur_lm_per_block > 0 ? o.schur_lm_per_block : (n_windows <= 8 ? 16 : n_windows < SMALL_BATCH_WINDOWS ? 32 : n_windows < 128 ? 48 : 64), SCHUR_CHUNK_LM_MAX);   // (round 4 sweep with the matrix-core kernel, 64 windows: 12: 382 k, 24: 436 k, 48: 448 k, 64: 448 k it/s; 256 windows: 48: 585 k, 64: 597 k)
+  // Landmarks per group: GROUP_LM (64) is what the kernels hold; the index build fills 32, and 16 when at most GROUP_LM_FEW_WINDOWS
+  // windows share the device.  A group of 64 short tracks (landmarks that entered the window with the last frame or two: 2 - 4
+  // observations each) is the slowest workgroup of its launch — the landmark elimination loops over the landmarks of the group —
+  // and OKVIS hands its landmark ids out in increasing order, so a real window has its short tracks side by side at the end.
+  // Measured (profiles/r04_notes.md; windows whose groups close at 256 observations first — configs[1]: 12 landmarks per group —
+  // are not touched): one 8-frame window in age order 77.3 us per iteration with 64, 69.0 with 32 (= random order); batches of
+  // short-track windows (8 frames, 430 landmarks, 8 observations each), us per step with 64 / 32 / 24 / 16 landmarks per group:
+  // 1 window 68.7 / 68.9 / 65.5 / 64.3, 8: 72.1 / 72.3 / 69.0 / 68.6, 64: 124.8 / 125.5 / 115.1 / 121.1, 256: 302 / 304 / 304 / 331;
+  // the replay's ten iterations per frame 0.830 (ids by first sighting) / 0.817 / 0.785 / 0.783 ms.  okvis_ba_tuning::group_lm overrides.
+  L.group_lm = std::max(1, std::min(o.tuning.group_lm > 0 ? o.tuning.group_lm : (n_windows <= GROUP_LM_FEW_WINDOWS ? GROUP_LM_FEW : GROUP_LM_DEFAULT), GROUP_LM));
+  // IMU / prior factors in a launch of their own when the batch fills the device (then four linearise workgroups share a
+  // CU); one launch for everything when a few windows wait for one another's latency
+  L.split_small = n_windows >= (o.tuning.split_small_min > 0 ? o.tuning.split_small_min : SMALL_BATCH_WINDOWS);
+  L.fp32 = o.fp32_linearize != 0;
+  return L;
 }
 
-int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A, HostWin& H, int n_windows_total = 1, bool lin2 = false,
-                 bool chain = false) {
+int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const BatchLayout& lay, Arena& A, HostWin& H) {
+  const bool lin2 = lay.lin2;
   auto bw_t0 = std::chrono::steady_clock::now();
   if (g_build_times.on) g_build_times.calls++;
 #define BW_T(name)                                                                                       \
@@ -289,16 +317,6 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
   // step, 64: 451 k -> 358 k it/s).  Not the default: the other grouping moves the rounding of every single-window run, and one
   // of the ill-conditioned DOGLEG cases that sit at the 1e-6 bound (test_dogleg_rejected_steps) lands at 1.25e-6.
   const long group_work_cap = opt.tuning.group_work > 0 ? opt.tuning.group_work : 0L;
-  // Landmarks per group: GROUP_LM (64) is what the kernels hold; the index build fills 32, and 16 when at most GROUP_LM_FEW_WINDOWS
-  // windows share the device.  A group of 64 short tracks (landmarks that entered the window with the last frame or two: 2 - 4
-  // observations each) is the slowest workgroup of its launch — the landmark elimination loops over the landmarks of the group —
-  // and OKVIS hands its landmark ids out in increasing order, so a real window has its short tracks side by side at the end.
-  // Measured (profiles/r04_notes.md; windows whose groups close at 256 observations first — configs[1]: 12 landmarks per group —
-  // are not touched): one 8-frame window in age order 77.3 us per iteration with 64, 69.0 with 32 (= random order); batches of
-  // short-track windows (8 frames, 430 landmarks, 8 observations each), us per step with 64 / 32 / 24 / 16 landmarks per group:
-  // 1 window 68.7 / 68.9 / 65.5 / 64.3, 8: 72.1 / 72.3 / 69.0 / 68.6, 64: 124.8 / 125.5 / 115.1 / 121.1, 256: 302 / 304 / 304 / 331;
-  // the replay's ten iterations per frame 0.830 (ids by first sighting) / 0.817 / 0.785 / 0.783 ms.  okvis_ba_tuning::group_lm overrides.
-  const int group_lm_cap = std::max(1, std::min(opt.tuning.group_lm > 0 ? opt.tuning.group_lm : (n_windows_total <= GROUP_LM_FEW_WINDOWS ? GROUP_LM_FEW : GROUP_LM_DEFAULT), GROUP_LM));
   // piece path (ba_linearize2.hpp): pieces instead of per-observation lists.  A piece = one or two adjacent observations of the same
   // pose inside one row of 16 lanes, greedy from the start of the run (the rule of linearize2_kernel's phase B).  The pieces of a
   // landmark depend on the lane its first observation takes, i.e. on the group it joins, so they are laid out while the groups
@@ -325,7 +343,7 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
         const int o0 = lm_obs_begin[l], o1 = lm_obs_begin[l + 1], p0 = lm_pair_begin[l], p1 = lm_pair_begin[l + 1];
         const int lo = o1 - o0, lp = p1 - p0;
         if (group_work_cap > 0 && nl > 0 && work + (long)lp * (lp + 1) / 2 > group_work_cap) break;
-        if (nl > 0 && (no + lo > GROUP_OBS || np + lp > GROUP_PAIRS || nl + 1 > group_lm_cap)) break;
+        if (nl > 0 && (no + lo > GROUP_OBS || np + lp > GROUP_PAIRS || nl + 1 > lay.group_lm)) break;
         int lpc = 0;
         int wc[4] = {0, 0, 0, 0};
         if (lin2) {   // piece path: at most LIN2_PIECES pieces per group (a pair has at least one piece)
@@ -521,23 +539,13 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
   std::vector<Chunk>& chunks = S.chunks;
   chunks.clear();
   {
-    // landmarks per Schur workgroup: 48 (three staged batches of 16) keeps the workgroup count low when many windows share
-    // the device; a few windows have the device to themselves and finish sooner with 32 (measured, tools/gpu_chunk_diag.py:
-    // one window 114.7 vs 119.7 us per iteration, 64 windows 239 vs 217)
-    int per = std::min(opt.schur_lm_per_block > 0 ? opt.schur_lm_per_block : (n_windows_total <= 8 ? 16 : n_windows_total < SMALL_BATCH_WINDOWS ? 32 : n_windows_total < 128 ? 48 : 64), SCHUR_CHUNK_LM_MAX);   // (round 4 sweep with the matrix-core kernel, 64 windows: 12: 382 k, 24: 436 k, 48: 448 k, 64: 448 k it/s; 256 windows: 48: 585 k, 64: 597 k)
-    // fused mode (the linearise workgroup reduces its own group, no Schur launch: DOGLEG and fixed-radius runs): possible when
-    // the reduced system is solved in LDS, the pose part is one Schur tile and the reduction's landmark tables fit the observation stage of the linearise kernel;
-    // then chunk = group.  options.reserved0 bit 2 keeps the separate launch (A/B switch).
+    // fused mode, where the batch allows it: the reduced system is solved in LDS, the pose part is one Schur tile and the
+    // reduction's landmark tables fit the observation stage of the linearise kernel; then chunk = group
     const int stage = opt.fp32_linearize ? (has_ext ? LinCfg<true, float>::STAGE_DOUBLES : LinCfg<false, float>::STAGE_DOUBLES)
                                          : (has_ext ? LinCfg<true, double>::STAGE_DOUBLES : LinCfg<false, double>::STAGE_DOUBLES);
-    H.group_chunks = !(opt.reserved0 & 4) && opt.schur_lm_per_block == 0 && D <= MAX_D_LDS && Dp <= TILE_DIM && n_windows_total <= fused_max_windows(opt) && 2 * SCHUR_LM_BATCH * 3 * Dp <= stage &&
-                     (opt.strategy == OKVIS_BA_STRATEGY_DOGLEG || opt.gauss_newton);
-    if (H.group_chunks) per = 1;
-    {
-      const bool no_spec = (opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_DECIDES) != 0, no_mfma = (opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_VALU) != 0;
-      H.spec_ok = !no_spec && !no_mfma && opt.schur_lm_per_block == 0 && D <= MAX_D_LDS && !has_ext && std::min(TILE_DIM, Dp) + 1 <= SCH2_MAXT_SMALL_ROWS &&
-                  (opt.strategy == OKVIS_BA_STRATEGY_DOGLEG || opt.gauss_newton);
-    }
+    H.group_chunks = lay.fuse && D <= MAX_D_LDS && Dp <= TILE_DIM && 2 * SCHUR_LM_BATCH * 3 * Dp <= stage;
+    const int per = H.group_chunks ? 1 : lay.schur_lm;
+    H.spec_ok = lay.spec && D <= MAX_D_LDS && !has_ext && schur_small_tiles(Dp);
     int g = 0;
     while (g < ngroup) {
       Chunk C;
@@ -691,10 +699,8 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
   //      window's blocks do, in time order.  Windows solved in HBM (D > MAX_D_LDS) are not concerned.
   bool use_chain = false;
   if (D <= MAX_D_LDS) {
-    int min_blocks = 1;
-    (void)want_chain(opt, &min_blocks);
     const int Ks = (D - Dp) / 9;
-    bool fits = Dp >= 6 && Ks >= min_blocks && Ks <= CH_MAX_KS && LChain::tiles_fit(Dp) &&
+    bool fits = Dp >= 6 && Ks >= lay.chain_min && Ks <= CH_MAX_KS && LChain::tiles_fit(Dp) &&
                 (int)solve_smem_chain(LChain::make(D, Dp).total, ((D + 5) / 6) * 6) <= SOLVE_LDS_LIMIT_CHAIN;
     auto rank = [&](int b) { return sb_off[b] < 0 ? -1 : (sb_off[b] - Dp) / 9; };
     for (int f = 0; f < w.n_imu && fits; ++f) {
@@ -708,8 +714,8 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
         if (r >= 0) lo = std::min(lo, r), hi = std::max(hi, r);
       }
     if (hi - lo > 1) fits = false;
-    if (chain && !fits) return BW_CHAIN_UNFIT;
-    use_chain = chain;
+    if (lay.chain && !fits) return BW_CHAIN_UNFIT;
+    use_chain = lay.chain;
   }
   H.chain = use_chain;
   P.chain = use_chain ? (D - Dp) / 9 : 0;
@@ -1050,6 +1056,22 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, Arena& A
                   8 * (int64_t)Dm * Dm + 8 * (int64_t)D + 2 * (56 * (int64_t)npose + 72 * (int64_t)nsb);
   H.bytes_small = (int64_t)w.n_imu * (8 * IMU_LIN_STRIDE + (int64_t)sizeof(ImuCacheD) + 2 * 56 + 2 * 72) +
                   8 * (int64_t)Dm * Dm * 2;
+  return OKVIS_BA_OK;
+}
+
+// The index build of a batch laid out by L: windows w[0 .. n) into A and H[0 .. n).  A window that does not fit the piece path or the
+// chain solve sends the whole batch back to the staged kernel's lists / the dense solve's layout (L says which it got).
+int build_batch(const okvis_ba_window* w, int n, const okvis_ba_options& o, BatchLayout& L, Arena& A, HostWin* H) {
+  for (int i = 0; i < n; ++i) {
+    const int rc = build_window(w[i], o, L, A, H[i]);
+    if (rc == BW_LIN2_UNFIT || rc == BW_CHAIN_UNFIT) {   // start over with every window
+      (rc == BW_LIN2_UNFIT ? L.lin2 : L.chain) = false;
+      A.size = A.zsize = 0;
+      i = -1;
+    } else if (rc != OKVIS_BA_OK)
+      return rc;
+  }
+  L.split_small = L.split_small && L.lin2;
   return OKVIS_BA_OK;
 }
 

@@ -1,5 +1,5 @@
-// Part of ba_capi.hip (see capi_solver.inc).  Dynamic LDS sizes and the launches of one iteration: Schur, solve, factors + linearise,
-// the sub-batch fork / join, the control-record fetch.
+// Part of ba_capi.hip (see capi_solver.inc).  Dynamic LDS sizes, the launch plan (make_plan: where every launch route is decided) and
+// the launches that read it: Schur, solve, factors + linearise, the sub-batch fork / join; the control-record fetch.
 namespace {
 
 size_t lin_smem(bool ext, bool f32 = false) {
@@ -13,19 +13,6 @@ size_t solve_smem(int Dpad, bool large) {
 }
 // chain solver (ba_chain.hpp): its matrix area (LChain::total of the batch's largest window) + the four vectors
 size_t solve_smem_chain(int chain_doubles, int Dpad) { return ((size_t)chain_doubles + 4 * (size_t)Dpad) * sizeof(double) + 16; }
-// the solve launch of the LDS-resident windows: the instantiation the batch was laid out for
-void launch_solve_small(okvis_ba_solver* s, dim3 grid, hipStream_t st, const WinPtrs* wins, int final_only, CtrlSlot* ctrls) {
-  const bool dbuf = s->group_chunks || s->spec_schur;   // (one set of partials per linearisation buffer)
-  if (s->chain) {
-    const size_t sm = solve_smem_chain(s->max_chain_doubles, s->max_Dpad_small);
-    if (dbuf) hipLaunchKernelGGL((solve_kernel<false, true, true>), grid, dim3(SOLVE_THREADS), sm, st, wins, s->d_opt, final_only, ctrls);
-    else hipLaunchKernelGGL((solve_kernel<false, false, true>), grid, dim3(SOLVE_THREADS), sm, st, wins, s->d_opt, final_only, ctrls);
-  } else {
-    const size_t sm = solve_smem(s->max_Dpad_small, false);
-    if (dbuf) hipLaunchKernelGGL((solve_kernel<false, true>), grid, dim3(SOLVE_THREADS), sm, st, wins, s->d_opt, final_only, ctrls);
-    else hipLaunchKernelGGL((solve_kernel<false, false>), grid, dim3(SOLVE_THREADS), sm, st, wins, s->d_opt, final_only, ctrls);
-  }
-}
 // dynamic LDS of linearize2_kernel: fixed part + the pose part of the step (fused: the aux area of the group reduction)
 int lin2_step_doubles(int max_Dp, bool fuse, bool f32) {
   const int aux = fuse ? (f32 ? Lin2Cfg<float, true>::MIN_STEP_DOUBLES : Lin2Cfg<double, true>::MIN_STEP_DOUBLES) : Lin2Cfg<double, false>::MIN_STEP_DOUBLES;
@@ -38,6 +25,145 @@ size_t lin2_smem(int max_Dp, bool fuse, bool f32, bool two_rounds = false) {
   return (size_t)(fixed + lin2_step_doubles(max_Dp, fuse, f32)) * sizeof(double);
 }
 size_t small_smem() { return (size_t)std::max<int>(std::max<int>(ImuLds::TOTAL, EvalLds::TOTAL), 2 * MAX_MARG_DIM) * sizeof(double); }
+
+size_t small_eval_smem() { return (size_t)std::max<int>(EvalLds::TOTAL, 2 * MAX_MARG_DIM) * sizeof(double); }
+
+// Every instantiation a launch plan can name, with the most dynamic LDS a plan gives it (okvis_ba_create allows it that much).
+// It comes first on purpose: the first reference to a kernel template in this file fixes where its code lands in the code object,
+// and this is the order the launches have always named them in (the same code layout, the same timing).
+std::vector<std::pair<const void*, size_t>> plan_kernels() {
+  auto f = [](auto k) { return reinterpret_cast<const void*>(k); };
+  const size_t dense = std::max(solve_smem(((MAX_D_LDS + 5) / 6) * 6, false), (size_t)SOLVE_LDS_LIMIT), chain = SOLVE_LDS_LIMIT_CHAIN;
+  const size_t wide = (size_t)sch2_tile_doubles(TILE_DIM, sch2_nlb(TILE_DIM, 9216)) * sizeof(double);
+  const size_t d = std::max(lin2_smem(MAX_D, true, false), small_smem()), s = std::max(lin2_smem(MAX_D, true, true), small_smem());
+  const size_t ef = std::max(lin_smem(true, true), small_smem()), ed = std::max(lin_smem(true), small_smem());
+  const size_t pf = std::max(lin_smem(false, true), small_smem()), pd = std::max(lin_smem(false), small_smem());
+  return {{f(&solve_kernel<false, true, true>), chain}, {f(&solve_kernel<false, false, true>), chain},
+          {f(&solve_kernel<false, true>), dense}, {f(&solve_kernel<false, false>), dense},
+          {f(&schur_ride_kernel<3>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3>), wide}, {f(&schur_mfma_kernel<9>), wide},
+          {f(&schur_kernel), 2 * SCHUR_LM_BATCH * TILE_DIM * 3 * sizeof(double)},
+          {f(&solve_kernel<true, false>), solve_smem(((MAX_D + 5) / 6) * 6, true)},
+          {f(&small_kernel), small_smem()}, {f(&small_prepare_kernel), small_smem()},
+          {f(&linearize2_kernel<float, true, false>), s}, {f(&linearize2_kernel<float, false, false, 4, 14>), s},
+          {f(&linearize2_kernel<float, false, false, 3>), s}, {f(&linearize2_kernel<double, true, false>), d},
+          {f(&linearize2_kernel<double, false, false, 4, 14>), d}, {f(&linearize2_kernel<double, false, false, 3>), d},
+          {f(&linearize2_kernel<float, true, true>), s}, {f(&linearize2_kernel<float, false, true>), s},
+          {f(&linearize2_kernel<double, true, true>), d}, {f(&linearize2_kernel<double, false, true>), d},
+          {f(&linearize_kernel<true, float, true>), ef}, {f(&linearize_kernel<true, float, false>), ef},
+          {f(&linearize_kernel<true, double, true>), ed}, {f(&linearize_kernel<true, double, false>), ed},
+          {f(&linearize_kernel<false, float, true>), pf}, {f(&linearize_kernel<false, float, false>), pf},
+          {f(&linearize_kernel<false, double, true>), pd}, {f(&linearize_kernel<false, double, false>), pd}};
+}
+
+// ---- The instantiations a launch plan names (Launch::k is the index in the table of its kind) ----
+using LinFn = decltype(&linearize_kernel<false, double, false>);
+using Lin2Fn = decltype(&linearize2_kernel<double, false, true>);
+using SolveFn = decltype(&solve_kernel<false, false>);
+// the staged kernel (ba_linearize.hpp): [4 * free extrinsics + 2 * fp32 + fused]
+const LinFn LIN[8] = {&linearize_kernel<false, double, false>, &linearize_kernel<false, double, true>, &linearize_kernel<false, float, false>,
+                      &linearize_kernel<false, float, true>,   &linearize_kernel<true, double, false>,  &linearize_kernel<true, double, true>,
+                      &linearize_kernel<true, float, false>,   &linearize_kernel<true, float, true>};
+// the piece path (ba_linearize2.hpp): [5 * fp32 + LIN2_*]
+enum { LIN2_FUSED, LIN2_FUSED_SMALL, LIN2_SMALL, LIN2_OCC3, LIN2_OCC4 };
+const Lin2Fn LIN2[10] = {&linearize2_kernel<double, true, false>, &linearize2_kernel<double, true, true>, &linearize2_kernel<double, false, true>,
+                         &linearize2_kernel<double, false, false, 3>, &linearize2_kernel<double, false, false, 4, 14>,
+                         &linearize2_kernel<float, true, false>, &linearize2_kernel<float, true, true>, &linearize2_kernel<float, false, true>,
+                         &linearize2_kernel<float, false, false, 3>, &linearize2_kernel<float, false, false, 4, 14>};
+// the reduced solve: the LDS-resident windows (dense or chain; DBUF: one set of Schur partials per linearisation buffer), the tiled ones
+enum { SOLVE_NONE, SOLVE_DENSE, SOLVE_DENSE_DBUF, SOLVE_CHAIN, SOLVE_CHAIN_DBUF, SOLVE_TILED };
+const SolveFn SOLVE[6] = {nullptr, &solve_kernel<false, false>, &solve_kernel<false, true>, &solve_kernel<false, false, true>,
+                          &solve_kernel<false, true, true>, &solve_kernel<true, false>};
+// the Schur launch (the first four: OKVIS_BA_ROUTE_SCHUR_KERNEL) and the factors' own launch (their kernels' arguments differ)
+enum { SCHUR_NONE, SCHUR_VALU, SCHUR_MFMA3, SCHUR_MFMA9, SCHUR_RIDE3 };
+enum { SMALL_NONE, SMALL_ALL, SMALL_PREPARE };
+// The launch plan (LaunchPlan) of a batch of n_windows laid out by L whose windows have the maxima M, under the options o.  Host only:
+// okvis_ba_upload computes it, okvis_ba_set_options again for the options of an uploaded batch, and every launch of the solver reads
+// it.  The layout fixed at upload bounds what later options can select: a batch uploaded under LM keeps its deciding Schur launch
+// after a switch to DOGLEG.
+LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_options& o, int n_windows) {
+  LaunchPlan p;
+  const bool f32 = o.fp32_linearize != 0;
+  // fused mode: linearise reduces its groups, no Schur launch (the reduction was sized at upload for one precision's stage)
+  p.fused = M.group_chunks && f32 == L.fp32 && decision_free(o);
+  // the decision-free Schur launch (BatchMax::spec_schur) while the options still ask for a mode that allows it
+  p.nodec = M.spec_schur && !p.fused && decision_free(o);
+  p.lin2 = L.lin2, p.split_small = L.split_small, p.graph = o.use_graph != 0;
+  p.n_small = M.imu + 1;
+  // ---- Schur.  No pose x extrinsics cross blocks: the reduction as a GEMM on the fp64 matrix core (ba_schur2.hpp).  Pose parts
+  //      beyond 63 rows (several 96-row tile pairs per chunk) keep schur_kernel unless OKVIS_BA_TUNE_SCHUR_MFMA_LARGE is set: every
+  //      tile pair of a chunk scans all its (landmark, block) rows to fill its tiles, and at configs[2] that makes the matrix-core
+  //      kernel the slower one (111 against 100 us per launch) ----
+  p.trows = std::min(TILE_DIM, M.Dp);
+  if (M.schur_blocks > 0 && !p.fused) {
+    const bool small_tiles = schur_small_tiles(M.Dp);
+    if (!M.any_ext && schur_mfma_allowed(o) && (small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_MFMA_LARGE))) {
+      p.nlb = sch2_nlb(p.trows, 5120);                  // 40 KB of tiles: three workgroups per CU
+      if (p.nlb < 12) p.nlb = sch2_nlb(p.trows, 9216);  // wide tiles: 72 KB, two per CU
+      const int sm = sch2_tile_doubles(p.trows, p.nlb) * (int)sizeof(double);
+      // The EVALUATION of the IMU / prior factors rides in the decision-free launch with the small tiles (schur_ride_kernel) where
+      // they have a launch of their own (piece path, batches of 40 windows and more): small_prepare_kernel right behind the solve
+      // launch keeps what may change a preintegration record, the rest leaves the chain of the sub-batch.
+      // okvis_ba_tuning::flags & OKVIS_BA_TUNE_NO_SMALL_RIDE: the whole factors in small_kernel as until round 6.
+      p.rides = small_tiles && p.nodec && L.split_small && !(o.tuning.flags & OKVIS_BA_TUNE_NO_SMALL_RIDE);
+      if (p.rides) p.schur = Launch{SCHUR_RIDE3, p.n_small + M.schur_blocks, std::max(sm, (int)small_eval_smem())};
+      else p.schur = Launch{small_tiles ? SCHUR_MFMA3 : SCHUR_MFMA9, M.schur_blocks, sm};
+    } else {
+      p.schur = Launch{SCHUR_VALU, M.schur_blocks, (int)(2 * SCHUR_LM_BATCH * p.trows * 3 * sizeof(double))};
+    }
+  }
+  if (M.Dpad_small > 0)   // (DBUF: one set of partials per linearisation buffer)
+    p.solve = Launch{(M.chain ? SOLVE_CHAIN : SOLVE_DENSE) + (M.group_chunks || M.spec_schur), 0,
+                     (int)(M.chain ? solve_smem_chain(M.chain_doubles, M.Dpad_small) : solve_smem(M.Dpad_small, false))};
+  if (M.Dpad_large > 0) {   // large windows: assemble + export, tiled multi-workgroup Cholesky (fp64 MFMA), back-substitution + finish
+    p.tiled = Launch{SOLVE_TILED, 0, (int)solve_smem(M.Dpad_large, true)};
+    p.nT = (M.Dpad_large + CT_TB - 1) / CT_TB;
+  }
+  // ---- IMU / prior factors and linearise: one launch for everything that depends only on the trial state (factors first) ----
+  const Launch small{SMALL_ALL, p.n_small, (int)small_smem()};
+  if (L.lin2) {
+    const int t = f32 ? 5 : 0, smem2 = (int)lin2_smem(M.Dp, p.fused, f32);
+    p.sd = lin2_step_doubles(M.Dp, p.fused, f32);
+    if (L.split_small) {
+      // (the initial evaluation keeps the whole factors: okvis_ba_begin is followed by a Schur launch too, whose riding workgroups then
+      //  evaluate the same states again — the same bits)
+      p.small_init = small;
+      p.small_iter = !p.rides ? small : M.imu > 0 ? Launch{SMALL_PREPARE, M.imu, (int)small_smem()} : Launch{};
+      const int occ = o.tuning.lin2_occupancy > 0 ? o.tuning.lin2_occupancy : 4;
+      const bool two_rounds = !p.fused && occ >= 4;   // block records in two rounds: 37 KB of LDS, four workgroups per CU
+      p.lin = Launch{t + (p.fused ? LIN2_FUSED : occ >= 4 ? LIN2_OCC4 : LIN2_OCC3), M.group,
+                     two_rounds ? (int)lin2_smem(M.Dp, false, f32, true) : smem2};
+    } else {
+      p.lin = Launch{t + (p.fused ? LIN2_FUSED_SMALL : LIN2_SMALL), p.n_small + M.group, std::max(smem2, (int)small_smem())};
+      p.lin_n_small = p.n_small;
+    }
+  } else {
+    p.lin = Launch{4 * M.any_ext + 2 * f32 + p.fused, p.n_small + M.group, (int)std::max(lin_smem(M.any_ext, f32), small_smem())};
+    p.lin_n_small = p.n_small;
+  }
+  // the preintegrations a discarded speculative evaluation left behind (DOGLEG), taken back before results leave the device
+  if (M.imu > 0 && o.strategy == OKVIS_BA_STRATEGY_DOGLEG && !o.gauss_newton) p.take_back = Launch{1, M.imu, 0};
+  p.budget = o.strategy == OKVIS_BA_STRATEGY_DOGLEG;
+  // ---- sub-batches: opt.n_streams (0 = auto).  Measured at 64 windows (scripts/sweep_streams.sh, r02): 1 stream 272 k,
+  //      2: 300 k, 3: 325 k, 4: 198 k window-iterations/s — the streams of the process that have work, or ever had, must not
+  //      exceed four (whatever GPU_MAX_HW_QUEUES and the stream priorities say: scripts/r06_streams.sh, r06_streams2.sh,
+  //      tools/micro/stream_concurrency.hip).
+  //      Measured on MI355X / ROCm 7.2 (profiles/r01_notes.md): branches inside ONE captured graph are not overlapped, but two
+  //      independently replayed graphs on two streams are (+29 % at 64 windows); more than two streams lose again.
+  //      (round 6, profiles/r06_notes.md: from 128 windows on two streams are ahead again — 128: 613 k against 601 k, 256: 692 k
+  //      against 659 k, 512: 727 k against 700 k window-iterations/s; 96 windows: three, 568 k against 549 k) ----
+  int nsub = o.n_streams > 0 ? o.n_streams : (n_windows >= 128 ? 2 : (n_windows >= 56 ? 3 : (n_windows >= 8 ? 2 : 1)));   // (48 windows: 2 is better)
+  nsub = std::max(1, std::min(nsub, n_windows));
+  // helper workgroups per window sum the Schur chunk partials for the solving one; launches of more windows sum inside the
+  // solving workgroup (a helper takes a whole CU)
+  auto extent = [](int w0, int nw) { return Extent{w0, nw, nw <= SOLVE_HELPED_MAX_WINDOWS ? SOLVE_HELPERS : 0}; };
+  for (int k = 0; k < nsub; ++k) {
+    const int w0 = (int)((int64_t)n_windows * k / nsub), w1 = (int)((int64_t)n_windows * (k + 1) / nsub);
+    p.subs.push_back(extent(w0, w1 - w0));
+  }
+  p.whole = extent(0, n_windows);
+  p.one_helpers = extent(0, 1).helpers;
+  return p;
+}
 
 // okvis_ba_begin for every window in ONE launch (it used to be three device copies and one upload per window: 1 ms of API calls
 // for 64 windows): the trial buffers start as copies of the accepted ones, the control record starts a new optimisation.
@@ -74,69 +200,37 @@ __global__ void delay_kernel(long long ticks) {
   while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(32);
 }
 
-struct Sub {
-  hipStream_t st;
-  int w0, nw;
-};
-Sub whole(okvis_ba_solver* s) { return Sub{s->stream, 0, (int)s->wins.size()}; }
+struct Sub { hipStream_t st; int w0, nw, helpers; };   // the windows of one launch (Extent) and its stream
+Sub sub(hipStream_t st, const Extent& e) { return Sub{st, e.w0, e.nw, e.helpers}; }
+Sub whole(okvis_ba_solver* s) { return sub(s->stream, s->plan.whole); }
 
-// fused mode: the linearise launch reduces every group it has linearised (ba_linearize.hpp); no Schur launch
-bool fused(const okvis_ba_solver* s) {
-  // (the fused reduction was sized at upload for the observation stage of one precision)
-  return s->group_chunks && (s->opt.fp32_linearize != 0) == s->fp32_at_upload &&
-         (s->opt.strategy == OKVIS_BA_STRATEGY_DOGLEG || s->opt.gauss_newton);
-}
-// decision-free Schur launch (okvis_ba_solver::spec_schur): the batch was laid out for it and the options still ask for a mode
-// whose damping does not depend on the decision
-bool spec_schur_now(const okvis_ba_solver* s) {
-  return s->spec_schur && !fused(s) && (s->opt.strategy == OKVIS_BA_STRATEGY_DOGLEG || s->opt.gauss_newton);
-}
-// ... and the EVALUATION of the IMU / prior factors rides in that launch (schur_ride_kernel) where they have a launch of their own today
-// (piece path, batches of 40 windows and more) and the matrix-core Schur kernel with the small tiles runs: small_prepare_kernel right
-// behind the solve launch keeps what may change a preintegration record, the rest leaves the chain of the sub-batch.
-// okvis_ba_tuning::flags & OKVIS_BA_TUNE_NO_SMALL_RIDE: the whole factors in small_kernel as until round 6.
-size_t small_eval_smem() { return (size_t)std::max<int>(EvalLds::TOTAL, 2 * MAX_MARG_DIM) * sizeof(double); }
-bool small_rides(const okvis_ba_solver* s) {
-  return !(s->opt.tuning.flags & (OKVIS_BA_TUNE_NO_SMALL_RIDE | OKVIS_BA_TUNE_SCHUR_VALU)) && spec_schur_now(s) && s->lin2 && s->split_small &&
-         s->max_schur_blocks > 0 && !s->any_ext && std::min(TILE_DIM, s->max_Dp) + 1 <= SCH2_MAXT_SMALL_ROWS;
-}
+// ---- The launches, each as the plan has it ----
 hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
-  if (s->max_schur_blocks == 0 || fused(s)) return hipSuccess;
-  const int trows = std::min(TILE_DIM, s->max_Dp);
-  const bool no_mfma = (s->opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_VALU) != 0;
-  // no pose x extrinsics cross blocks: the reduction as a GEMM on the fp64 matrix core (ba_schur2.hpp).  Pose parts beyond 63 rows
-  // (several 96-row tile pairs per chunk) keep schur_kernel unless OKVIS_BA_TUNE_SCHUR_MFMA_LARGE is set: every tile pair of a chunk
-  // scans all its (landmark, block) rows to fill its tiles, and at configs[2] that makes the matrix-core kernel the slower one
-  // (111 against 100 us per launch)
-  const bool mfma_large = (s->opt.tuning.flags & OKVIS_BA_TUNE_SCHUR_MFMA_LARGE) != 0;
-  if (!s->any_ext && !no_mfma && (trows + 1 <= SCH2_MAXT_SMALL_ROWS || mfma_large)) {
-    int nlb = sch2_nlb(trows, 5120);              // 40 KB of tiles: three workgroups per CU
-    if (nlb < 12) nlb = sch2_nlb(trows, 9216);    // wide tiles: 72 KB, two per CU
-    const size_t sm = (size_t)sch2_tile_doubles(trows, nlb) * sizeof(double);
-    if (small_rides(s)) {
-      const int n_small = s->max_imu + 1;
-      hipLaunchKernelGGL(schur_ride_kernel<3>, dim3(n_small + s->max_schur_blocks, (unsigned)b.nw), dim3(SCHUR_THREADS), std::max(sm, small_eval_smem()), b.st,
-                         s->d_wins + b.w0, s->d_opt, trows, final_call, nlb, s->d_ctrl + b.w0, 1, n_small);
-    } else if (trows + 1 <= SCH2_MAXT_SMALL_ROWS)
-      hipLaunchKernelGGL(schur_mfma_kernel<3>, dim3(s->max_schur_blocks, (unsigned)b.nw), dim3(SCHUR_THREADS), sm, b.st, s->d_wins + b.w0, s->d_opt, trows, final_call, nlb, s->d_ctrl + b.w0, spec_schur_now(s) ? 1 : 0);
-    else
-      hipLaunchKernelGGL(schur_mfma_kernel<9>, dim3(s->max_schur_blocks, (unsigned)b.nw), dim3(SCHUR_THREADS), sm, b.st, s->d_wins + b.w0, s->d_opt, trows, final_call, nlb, s->d_ctrl + b.w0, 0);
-    return hipGetLastError();
+  const LaunchPlan& p = s->plan;
+  const dim3 grid((unsigned)p.schur.gx, (unsigned)b.nw), blk(SCHUR_THREADS);
+  const WinPtrs* wins = s->d_wins + b.w0;
+  const CtrlSlot* ctrls = s->d_ctrl + b.w0;
+  switch (p.schur.k) {
+    case SCHUR_NONE: return hipSuccess;
+    case SCHUR_VALU: hipLaunchKernelGGL(schur_kernel, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call); break;
+    case SCHUR_MFMA3: hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
+    case SCHUR_MFMA9: hipLaunchKernelGGL(schur_mfma_kernel<9>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
+    case SCHUR_RIDE3: hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small); break;
   }
-  hipLaunchKernelGGL(schur_kernel, dim3(s->max_schur_blocks, (unsigned)b.nw), dim3(SCHUR_THREADS),
-                     (size_t)2 * SCHUR_LM_BATCH * trows * 3 * sizeof(double), b.st, s->d_wins + b.w0, s->d_opt, trows,
-                     final_call);
   return hipGetLastError();
 }
+// one solve_kernel launch (l: the plan's solve or tiled) on the window records `wins`
+void launch_solve_kernel(okvis_ba_solver* s, const Launch& l, dim3 grid, hipStream_t st, const WinPtrs* wins, int final_only, CtrlSlot* ctrls) {
+  const SolveFn fn = SOLVE[l.k];
+  hipLaunchKernelGGL(fn, grid, dim3(SOLVE_THREADS), l.lds, st, wins, s->d_opt, final_only, ctrls);
+}
 hipError_t launch_solve(okvis_ba_solver* s, Sub b, int final_only) {
-  if (s->max_Dpad_small > 0)
-    launch_solve_small(s, dim3((unsigned)b.nw, 1 + (b.nw <= SOLVE_HELPED_MAX_WINDOWS ? SOLVE_HELPERS : 0)), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0);
-  if (s->max_Dpad_large > 0) {
-    // large windows: assemble + export, tiled multi-workgroup Cholesky (fp64 MFMA), back-substitution + finish
-    hipLaunchKernelGGL((solve_kernel<true, false>), dim3((unsigned)b.nw), dim3(SOLVE_THREADS), solve_smem(s->max_Dpad_large, true), b.st,
-                       s->d_wins + b.w0, s->d_opt, final_only, s->d_ctrl + b.w0);
+  const LaunchPlan& p = s->plan;
+  if (p.solve.k) launch_solve_kernel(s, p.solve, dim3((unsigned)b.nw, 1 + b.helpers), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0);
+  if (p.tiled.k) {
+    launch_solve_kernel(s, p.tiled, dim3((unsigned)b.nw), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0);
     if (!final_only) {
-      const int nT = (s->max_Dpad_large + CT_TB - 1) / CT_TB;
+      const int nT = p.nT;   // (Cholesky tiles per dimension)
       hipLaunchKernelGGL(large_export_kernel, dim3(nT * (nT + 1) / 2, (unsigned)b.nw, CT_TILE / CT_THREADS), dim3(CT_THREADS), 0, b.st,
                          s->d_wins + b.w0);
       hipLaunchKernelGGL(chol_tiles_window_kernel, dim3(nT * (nT + 1) / 2 + nT, (unsigned)b.nw), dim3(CT_THREADS), CT_SMEM_DOUBLES * 8,
@@ -146,55 +240,26 @@ hipError_t launch_solve(okvis_ba_solver* s, Sub b, int final_only) {
   }
   return hipGetLastError();
 }
-// one launch for everything that depends only on the trial state: IMU / prior factors (first max_imu + 1
-// workgroups) and the reprojection groups
+// the IMU / prior factors' launch of their own (init: okvis_ba_begin's), then the linearise launch
 hipError_t launch_lin(okvis_ba_solver* s, Sub b, int init) {
-  const int n_small = s->max_imu + 1;
-  const bool f32 = s->opt.fp32_linearize != 0;
-  const bool fuse = fused(s);
-  if (s->lin2) {   // piece path (ba_linearize2.hpp)
-    const int sd = lin2_step_doubles(s->max_Dp, fuse, f32);
-    const size_t smem2 = lin2_smem(s->max_Dp, fuse, f32);
-    if (s->split_small) {
-      // (the initial evaluation keeps the whole factors: okvis_ba_begin is followed by a Schur launch too, whose riding workgroups then
-      //  evaluate the same states again — the same bits)
-      if (init || !small_rides(s))
-        hipLaunchKernelGGL(small_kernel, dim3(n_small, (unsigned)b.nw), dim3(LIN_THREADS), small_smem(), b.st, s->d_wins + b.w0, init);
-      else if (s->max_imu > 0)
-        hipLaunchKernelGGL(small_prepare_kernel, dim3(s->max_imu, (unsigned)b.nw), dim3(LIN_THREADS), small_smem(), b.st, s->d_wins + b.w0);
-      const dim3 grid2(s->max_group, (unsigned)b.nw);
-      const int occ_env = s->opt.tuning.lin2_occupancy > 0 ? s->opt.tuning.lin2_occupancy : 4;
-      const bool two_rounds = !fuse && occ_env >= 4;   // block records in two rounds: 37 KB of LDS, four workgroups per CU
-      const size_t smem2v = two_rounds ? lin2_smem(s->max_Dp, false, f32, true) : smem2;
-      auto go2 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid2, dim3(LIN_THREADS), smem2v, b.st, s->d_wins + b.w0, s->d_opt, init, 0, sd); };
-      const int occ = occ_env;
-      if (f32) fuse ? go2(linearize2_kernel<float, true, false>) : (occ >= 4 ? go2(linearize2_kernel<float, false, false, 4, 14>) : go2(linearize2_kernel<float, false, false, 3>));
-      else fuse ? go2(linearize2_kernel<double, true, false>) : (occ >= 4 ? go2(linearize2_kernel<double, false, false, 4, 14>) : go2(linearize2_kernel<double, false, false, 3>));
-    } else {
-      const dim3 grid2(n_small + s->max_group, (unsigned)b.nw);
-      const size_t sm = std::max(smem2, small_smem());
-      auto go2 = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid2, dim3(LIN_THREADS), sm, b.st, s->d_wins + b.w0, s->d_opt, init, n_small, sd); };
-      if (f32) fuse ? go2(linearize2_kernel<float, true, true>) : go2(linearize2_kernel<float, false, true>);
-      else fuse ? go2(linearize2_kernel<double, true, true>) : go2(linearize2_kernel<double, false, true>);
-    }
-    return hipGetLastError();
-  }
-  const dim3 grid(n_small + s->max_group, (unsigned)b.nw), blk(LIN_THREADS);
-  const size_t smem = std::max(lin_smem(s->any_ext, f32), small_smem());
-  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, blk, smem, b.st, s->d_wins + b.w0, s->d_opt, init, n_small); };
-  if (s->any_ext) {
-    if (f32) fuse ? go(linearize_kernel<true, float, true>) : go(linearize_kernel<true, float, false>);
-    else fuse ? go(linearize_kernel<true, double, true>) : go(linearize_kernel<true, double, false>);
+  const LaunchPlan& p = s->plan;
+  const WinPtrs* wins = s->d_wins + b.w0;
+  const Launch& f = init ? p.small_init : p.small_iter;
+  if (f.k == SMALL_ALL) hipLaunchKernelGGL(small_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins, init);
+  if (f.k == SMALL_PREPARE) hipLaunchKernelGGL(small_prepare_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins);
+  const dim3 grid((unsigned)p.lin.gx, (unsigned)b.nw);
+  if (p.lin2) {
+    const Lin2Fn fn = LIN2[p.lin.k];
+    hipLaunchKernelGGL(fn, grid, dim3(LIN_THREADS), p.lin.lds, b.st, wins, s->d_opt, init, p.lin_n_small, p.sd);
   } else {
-    if (f32) fuse ? go(linearize_kernel<false, float, true>) : go(linearize_kernel<false, float, false>);
-    else fuse ? go(linearize_kernel<false, double, true>) : go(linearize_kernel<false, double, false>);
+    const LinFn fn = LIN[p.lin.k];
+    hipLaunchKernelGGL(fn, grid, dim3(LIN_THREADS), p.lin.lds, b.st, wins, s->d_opt, init, p.lin_n_small);
   }
   return hipGetLastError();
 }
-// the preintegrations a discarded speculative evaluation left behind, taken back before results leave the device (ba_solve.hpp)
 hipError_t launch_imu_take_back(okvis_ba_solver* s, int w0, int nw) {
-  if (s->max_imu == 0 || s->opt.strategy != OKVIS_BA_STRATEGY_DOGLEG || s->opt.gauss_newton) return hipSuccess;
-  hipLaunchKernelGGL(imu_take_back_kernel, dim3((unsigned)s->max_imu, (unsigned)nw), dim3(64), 0, s->stream, s->d_wins + w0);
+  if (!s->plan.take_back.k) return hipSuccess;
+  hipLaunchKernelGGL(imu_take_back_kernel, dim3((unsigned)s->plan.take_back.gx, (unsigned)nw), dim3(64), 0, s->stream, s->d_wins + w0);
   return hipGetLastError();
 }
 hipError_t launch_iteration(okvis_ba_solver* s, Sub b) {
@@ -203,26 +268,26 @@ hipError_t launch_iteration(okvis_ba_solver* s, Sub b) {
   if ((e = launch_solve(s, b, 0)) != hipSuccess) return e;
   return launch_lin(s, b, 0);
 }
-// n iterations of every sub-batch: fork from the main stream, one chain per sub-stream, join
 hipError_t launch_budget(okvis_ba_solver* s, Sub b, int n) {
-  if (s->opt.strategy != OKVIS_BA_STRATEGY_DOGLEG || n <= 0) return hipSuccess;
+  if (!s->plan.budget || n <= 0) return hipSuccess;
   hipLaunchKernelGGL(add_budget_kernel, dim3((unsigned)b.nw), dim3(64), 0, b.st, s->d_wins + b.w0, n);
   return hipGetLastError();
 }
+// the chain of one sub-batch: the iteration budget, then n iterations (eager, or captured into the sub-batch's graph)
+hipError_t launch_chain(okvis_ba_solver* s, Sub b, int n, int budget) {
+  hipError_t e = launch_budget(s, b, budget);
+  for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, b);
+  return e;
+}
+// n iterations of every sub-batch: fork from the main stream, one chain per sub-stream, join
 hipError_t launch_iterations_forked(okvis_ba_solver* s, int n, int budget = -1) {
   const int nsub = (int)s->sub_streams.size();
   if (budget < 0) budget = n;
-  if (nsub <= 1) {
-    hipError_t e = launch_budget(s, whole(s), budget);
-    for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, whole(s));
-    return e;
-  }
+  if (nsub <= 1) return launch_chain(s, whole(s), n, budget);
   hipError_t e = hipEventRecord(s->ev_fork, s->stream);
   for (int k = 0; k < nsub && e == hipSuccess; ++k) {
     e = hipStreamWaitEvent(s->sub_streams[k], s->ev_fork, 0);
-    const Sub b{s->sub_streams[k], s->sub_begin[k], s->sub_begin[k + 1] - s->sub_begin[k]};
-    if (e == hipSuccess) e = launch_budget(s, b, budget);
-    for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, b);
+    if (e == hipSuccess) e = launch_chain(s, sub(s->sub_streams[k], s->plan.subs[k]), n, budget);
     if (e == hipSuccess) e = hipEventRecord(s->sub_events[k], s->sub_streams[k]);
     if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->sub_events[k], 0);
   }

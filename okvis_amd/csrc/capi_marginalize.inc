@@ -125,16 +125,15 @@ int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_sp
   int rc = okvis_ba_begin(s);
   if (rc != OKVIS_BA_OK) return rc;
   s->begun = false;
-  const Sub one{s->stream, w, 1};
-  HIP_TRY(launch_schur(s, one));
+  HIP_TRY(launch_schur(s, sub(s->stream, Extent{w, 1, s->plan.one_helpers})));
   if (large_window) {
     // assembly of the undamped system, then the kernel that completes it (Schur partials, IMU terms) and, because this copy of
     // the window carries an S pointer, writes it out as one full symmetric D x D matrix
-    hipLaunchKernelGGL((solve_kernel<true, false>), dim3(1), dim3(SOLVE_THREADS), solve_smem(s->max_Dpad_large, true), s->stream, d_win, s->d_opt, 2, s->d_ctrl + w);
+    launch_solve_kernel(s, s->plan.tiled, dim3(1), s->stream, d_win, 2, s->d_ctrl + w);
     const int nT = (((D + 5) / 6) * 6 + CT_TB - 1) / CT_TB;
     hipLaunchKernelGGL(large_export_kernel, dim3(nT * (nT + 1) / 2, 1, CT_TILE / CT_THREADS), dim3(CT_THREADS), 0, s->stream, d_win);
   } else
-    launch_solve_small(s, dim3(1, 1 + SOLVE_HELPERS), s->stream, d_win, 2, s->d_ctrl + w);
+    launch_solve_kernel(s, s->plan.solve, dim3(1, 1 + s->plan.one_helpers), s->stream, d_win, 2, s->d_ctrl + w);
   HIP_TRY(hipGetLastError());
   MargArgs ma;
   ma.pose_marg = d + o_pm;

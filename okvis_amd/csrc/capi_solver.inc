@@ -81,6 +81,51 @@ struct Arena {
   size_t total() const { return data_bytes() + zsize; }
 };
 
+// What a batch asks of its windows' layout, from the options and the window count alone (batch_layout); build_window adds the
+// conditions on a window's shape, build_batch clears lin2 / chain for the whole batch when a window does not fit them
+struct BatchLayout {
+  bool lin2 = false, chain = false;   // the piece path's lists (ba_linearize2.hpp), the chain solve's layout (ba_chain.hpp) ...
+  int chain_min = 1;                  // ... for LDS-resident windows with at least this many speed/bias blocks
+  bool fuse = false, spec = false;    // the fused linearise + reduce launch / the decision-free Schur launch allowed
+  int schur_lm = 0, group_lm = 0;     // landmarks per Schur chunk / per linearise group (at most)
+  bool split_small = false;           // piece path: IMU / prior factors in a launch of their own (small_kernel)
+  bool fp32 = false;                  // the observation stage the fused reduction was sized for
+};
+// The per-window maxima of an uploaded batch that its launches are sized by, and what its windows' layouts have in common
+struct BatchMax {
+  int group = 0, imu = 0, schur_blocks = 0, lm = 0, Dp = 0, chunks = 0;
+  int Dpad_small = 0, Dpad_large = 0, chain_doubles = 0;   // LDS-resident windows / solved in HBM; the chain solver's LChain::total
+  bool any_ext = false, chain = false;   // free extrinsics somewhere; LDS-resident windows laid out for the chain solver
+  bool group_chunks = false;             // every window has one Schur chunk per linearise group (fused mode possible)
+  // Batches that are not fused but run DOGLEG or fixed-radius iterations on windows the matrix-core Schur kernel serves: the Schur
+  // launch takes no decision (schur_mfma_kernel, nodec) and reduces the trial buffer into that buffer's own set of partials, the
+  // solve kernel decides (its DBUF instantiation, as in fused mode).  OKVIS_BA_TUNE_SCHUR_DECIDES keeps the decision in the Schur launch.
+  bool spec_schur = false;
+};
+struct Launch {   // one launch: the instantiation (capi_launch.inc, 0 = none), grid.x (grid.y = windows), dynamic LDS in bytes
+  int k = 0, gx = 0, lds = 0;
+};
+struct Extent {   // windows [w0, w0 + nw) of one launch, and the helper workgroups per window of their solve launch
+  int w0 = 0, nw = 0, helpers = 0;
+  bool operator==(const Extent& o) const { return w0 == o.w0 && nw == o.nw && helpers == o.helpers; }
+};
+// The launch plan of an uploaded batch (make_plan, capi_launch.inc): its route, every launch the solver issues and their scalar
+// arguments.  (ints only, no padding: plans are compared byte for byte)
+struct PlanFixed {
+  int lin2 = 0, split_small = 0, fused = 0, nodec = 0, rides = 0, graph = 0;   // the route
+  Launch schur; int trows = 0, nlb = 0, n_small = 0;   // (nodec above)
+  Launch solve, tiled; int nT = 0;                     // the LDS-resident windows / the windows solved in HBM (+ their tiles per dimension)
+  Launch small_init, small_iter, lin; int lin_n_small = 0, sd = 0;   // the factors' launch of okvis_ba_begin / of an iteration; linearise
+  Launch take_back; int budget = 0;                    // imu_take_back_kernel; add_budget_kernel in front of the iterations
+  Extent whole; int one_helpers = 0;                   // okvis_ba_begin / okvis_ba_finish; okvis_ba_marginalize (one window)
+};
+struct LaunchPlan : PlanFixed {
+  std::vector<Extent> subs;   // okvis_ba_iterate's sub-batches, one stream each
+  bool operator==(const LaunchPlan& o) const {
+    return std::memcmp(static_cast<const PlanFixed*>(this), static_cast<const PlanFixed*>(&o), sizeof(PlanFixed)) == 0 && subs == o.subs;
+  }
+};
+
 }  // namespace
 
 struct okvis_ba_solver {
@@ -90,7 +135,6 @@ struct okvis_ba_solver {
   // windows overlap on the 256 CUs
   std::vector<hipStream_t> sub_streams;
   std::vector<hipEvent_t> sub_events;
-  std::vector<int> sub_begin;  // [n_sub+1] window ranges
   hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr;
   okvis_ba_options opt;
   OptD* d_opt = nullptr;
@@ -101,18 +145,12 @@ struct okvis_ba_solver {
   StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize)
   StageVec stage, stage_small;   // pinned staging of the arena's data part / of the WinPtrs + OptD records (kept across uploads)
   std::vector<HostWin> wins;
-  bool uploaded = false, begun = false, any_ext = false;
-  bool lin2 = false;          // the batch's index lists are those of the piece path (ba_linearize2.hpp)
-  bool split_small = false;   // piece path: IMU / prior factors in a launch of their own (small_kernel), three linearise workgroups per CU
-  bool group_chunks = false;   // every window of the batch has one Schur chunk per linearise group (see fused())
-  // Batches that are not fused but run DOGLEG or fixed-radius iterations on windows the matrix-core Schur kernel serves: the Schur
-  // launch takes no decision (schur_mfma_kernel, nodec) and reduces the trial buffer into that buffer's own set of partials, the
-  // solve kernel decides (its DBUF instantiation, as in fused mode).  OKVIS_BA_TUNE_SCHUR_DECIDES keeps the decision in the Schur launch.
-  bool spec_schur = false;
-  bool chain = false;          // the LDS-resident windows of the batch are laid out for the chain solver (ba_chain.hpp): solve_kernel<.., CHAIN>
-  int max_chain_doubles = 0;   // its matrix area (LChain::total), largest window
-  bool fp32_at_upload = false;
-  std::vector<int64_t> launch_sig;   // what the captured graphs depend on (see okvis_ba_upload)
+  bool uploaded = false, begun = false;
+  BatchLayout layout;   // of the uploaded batch
+  BatchMax max;
+  LaunchPlan plan;      // (upload, set_options)
+  LaunchPlan graph_plan;                // what the captured graphs were captured under: the plan ...
+  std::vector<const void*> graph_addr;  // ... and the device records and streams they name (see keep_graphs)
   unsigned char* h_ctrl_stage = nullptr;   // pinned / device staging of per-window control data (begin, fetch_ctrl)
   unsigned char* d_ctrl_stage = nullptr;
   size_t ctrl_stage_bytes = 0;
@@ -138,8 +176,6 @@ struct okvis_ba_solver {
   StageVec stage_pre;            // first preintegrations started at upload (imu_pre_kernel): the staged block and its device copy
   unsigned char* d_pre = nullptr;   // (PRE_MAX_TERMS records)
   bool acc_fresh = false;   // HostWin::acc mirrors the device's accepted-buffer index (no kernel launched since it was read)
-  int max_group = 0, max_imu = 0, max_schur_blocks = 0, max_lm = 0, max_Dpad = 0, max_Dp = 0, max_spart_stride = 0;
-  int max_Dpad_small = 0, max_Dpad_large = 0;
   long long stagger_ticks = 0;   // start offset between consecutive sub-batch streams (wall_clock64 ticks, 100 MHz); okvis_ba_tuning::stagger_us
   bool skip_topup = false;   // okvis_ba_optimize_timed ran out of time: finish() must not grant the slots mis-speculated steps still owe
   long long slots = 0;   // launch slots (schur + solve + linearise triples) since okvis_ba_begin: diagnostics (array 96)
@@ -153,7 +189,6 @@ struct okvis_ba_solver {
 
 namespace {
 
-size_t solve_smem(int Dpad, bool large);
 size_t solve_smem_chain(int chain_doubles, int Dpad);
 
 constexpr int FUSED_MAX_WINDOWS = 48;   // up to here the fused linearise + reduce launch beats the separate Schur launch (tools/gpu_fused_sweep.py:
@@ -162,6 +197,12 @@ constexpr int FUSED_MAX_WINDOWS = 48;   // up to here the fused linearise + redu
 int fused_max_windows(const okvis_ba_options& o) {
   return o.tuning.fused_max_windows > 0 ? o.tuning.fused_max_windows : o.tuning.fused_max_windows < 0 ? 0 : FUSED_MAX_WINDOWS;
 }
+// the options ask for a mode whose damping does not depend on the accept / reject decision (DOGLEG, or Gauss-Newton's fixed radius)
+inline bool decision_free(const okvis_ba_options& o) { return o.strategy == OKVIS_BA_STRATEGY_DOGLEG || o.gauss_newton; }
+// the Schur reduction may run on the fp64 matrix core (OKVIS_BA_TUNE_SCHUR_VALU keeps schur_kernel)
+inline bool schur_mfma_allowed(const okvis_ba_options& o) { return !(o.tuning.flags & OKVIS_BA_TUNE_SCHUR_VALU); }
+// a pose part of Dp rows fits the small tiles of the matrix-core Schur kernel (schur_mfma_kernel<3>)
+inline bool schur_small_tiles(int Dp) { return std::min(TILE_DIM, Dp) + 1 <= SCH2_MAXT_SMALL_ROWS; }
 // Print-only diagnostics: the ONE environment variable the library reads, once per process.  OKVIS_BA_DEBUG is a comma-separated
 // list of "build" (host time of build_window's sections, printed at exit), "upload" (sections of every upload), "marg" (ranks and
 // bounds of every marginalisation), "arena=<file>" (okvis_ba_check_window dumps the index build's output).  Nothing here changes a
@@ -221,6 +262,16 @@ void destroy_graphs(okvis_ba_solver* s) {
   s->graphs.clear();
   for (auto& kv : s->sub_graphs) (void)hipGraphExecDestroy(kv.second);
   s->sub_graphs.clear();
+}
+// Captured graphs hold the plan's launches, the addresses of the window / option / control records and the sub-batch streams: a
+// re-upload or an option change that leaves all of that as it was (equally shaped windows: the per-frame pattern) keeps them.
+void keep_graphs(okvis_ba_solver* s) {
+  std::vector<const void*> addr = {s->d_wins, s->d_opt, s->d_ctrl};
+  for (auto st : s->sub_streams) addr.push_back(st);
+  if (s->plan == s->graph_plan && addr == s->graph_addr) return;
+  destroy_graphs(s);
+  s->graph_plan = s->plan;
+  s->graph_addr.swap(addr);
 }
 
 }  // namespace
