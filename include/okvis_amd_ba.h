@@ -191,6 +191,9 @@ typedef struct okvis_ba_window {
 #define OKVIS_BA_TUNE_NO_MARG_TILES 0x80u     /* okvis_ba_marginalize: kept blocks > 96 rows on the single workgroup, not on the tiled tail */
 #define OKVIS_BA_TUNE_NO_SMALL_RIDE 0x100u    /* IMU / prior factors evaluated in small_kernel behind the solve launch (rounds 4-5), not inside
                                                  the decision-free Schur launch (schur_ride_kernel)                                          */
+#define OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES 0x200u /* small tiles of the matrix-core Schur kernel: the serial loop over batches of 12 landmarks
+                                                 (rounds 4-6) instead of the pipelined ring of 4-landmark stages — the referee of the new
+                                                 loop for one release, the same sums bit for bit (OKVIS_BA_ROUTE_SCHUR_KERNEL reports 4)      */
 #define OKVIS_BA_SOLVE_AUTO 0                  /* the library picks (OKVIS_BA_ROUTE_SOLVE_MODE reports what it picked)                     */
 #define OKVIS_BA_SOLVE_DENSE 1                /* blocked LDL^T of the whole D x D reduced system in LDS (rounds 3-5)                      */
 #define OKVIS_BA_SOLVE_CHAIN 2                /* speed/bias blocks eliminated along the IMU chain first, dense pose system behind it      */
@@ -494,7 +497,8 @@ int okvis_ba_helper_timeouts(okvis_ba_solver* s, int64_t* count);
 #define OKVIS_BA_ROUTE_SPLIT_SMALL 4            /* 1 = IMU / prior factors in small_kernel, a launch of their own                   */
 #define OKVIS_BA_ROUTE_SUB_BATCHES 5            /* streams the batch is spread over                                                 */
 #define OKVIS_BA_ROUTE_SUB_BATCH_MAX_WINDOWS 6
-#define OKVIS_BA_ROUTE_SCHUR_KERNEL 7           /* 0 none, 1 schur_kernel, 2 schur_mfma_kernel<3>, 3 schur_mfma_kernel<9>           */
+#define OKVIS_BA_ROUTE_SCHUR_KERNEL 7           /* 0 none, 1 schur_kernel, 2 schur_mfma_kernel<3>, 3 schur_mfma_kernel<9>,
+                                                   4 schur_mfma_kernel<3> with serial landmark batches (the referee)                */
 #define OKVIS_BA_ROUTE_SOLVE_DBUF 8             /* 1 = solve_kernel<false, true> (one set of Schur partials per linearisation buffer) */
 #define OKVIS_BA_ROUTE_SOLVE_TILED 9            /* 1 = at least one window above the LDS solver's size (chol_tiles_window_kernel)    */
 #define OKVIS_BA_ROUTE_SOLVE_HELPERS 10         /* helper workgroups per solving workgroup (0 above 8 windows per launch)           */

@@ -1048,7 +1048,8 @@ int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route) {
   route[OKVIS_BA_ROUTE_SPLIT_SMALL] = p.split_small;
   route[OKVIS_BA_ROUTE_SUB_BATCHES] = (int)p.subs.size();
   route[OKVIS_BA_ROUTE_SUB_BATCH_MAX_WINDOWS] = big.nw;
-  route[OKVIS_BA_ROUTE_SCHUR_KERNEL] = p.schur.k == SCHUR_RIDE3 ? SCHUR_MFMA3 : p.schur.k;   // (the riding kernel is schur_mfma_kernel<3>'s)
+  // (the riding kernel is schur_mfma_kernel<3>'s; 4 = either of them with the serial batch loop, OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
+  route[OKVIS_BA_ROUTE_SCHUR_KERNEL] = p.schur.k == SCHUR_RIDE3 ? SCHUR_MFMA3 : p.schur.k >= SCHUR_MFMA3_SERIAL ? 4 : p.schur.k;
   route[OKVIS_BA_ROUTE_SOLVE_DBUF] = p.solve.k == SOLVE_DENSE_DBUF || p.solve.k == SOLVE_CHAIN_DBUF;
   route[OKVIS_BA_ROUTE_SOLVE_TILED] = p.tiled.k != SOLVE_NONE;
   route[OKVIS_BA_ROUTE_SOLVE_HELPERS] = big.helpers;

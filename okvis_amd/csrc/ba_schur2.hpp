@@ -5,16 +5,32 @@
 //
 // Same decomposition, same output as schur_kernel: a workgroup owns (chunk of landmarks) x (tile pair of <= 16 x 16 pose
 // blocks = 96 x 96 rows), lower triangle only, partials in the solve kernel's block-packed layout.  The landmarks of the
-// chunk are staged `nlb` at a time as two dense row-major LDS tiles [rows][3 nlb + 1] (contraction index = 3 x landmark +
-// coordinate; missing (landmark, block) pairs are zeros; odd row stride: the 16 rows a wave reads per operand fall into 16
-// banks), one for the row blocks holding Y — plus, on diagonal tile pairs, one extra row holding V^-1 b, so that Y b falls
-// out of the same product — one for the column blocks holding W.  The 16 x 16 output tiles are spread over the four waves and
-// stay in accumulator registers across the batches (A lane l = Y[row l & 15][k + (l >> 4)], B lane l = W[col l & 15][k + (l >> 4)]).
+// chunk are staged as two dense row-major LDS tiles [rows][3 n + 1] (contraction index = 3 x landmark + coordinate; missing
+// (landmark, block) pairs are zeros; odd row stride: the 16 rows a wave reads per operand fall into 16 bank pairs), one for the
+// row blocks holding Y — plus, on diagonal tile pairs, one extra row holding V^-1 b, so that Y b falls out of the same
+// product — one for the column blocks holding W.  The 16 x 16 output tiles are spread over the four waves and stay in
+// accumulator registers across the chunk (A lane l = Y[row l & 15][k + (l >> 4)], B lane l = W[col l & 15][k + (l >> 4)]).
 // Off-diagonal 6x6 blocks go from the accumulators to global memory; diagonal blocks and Y b meet the chunk's J^T J / J^T r
 // partial lists in LDS first (one work-item per entry, list order) and leave as coalesced stores.
 //
-// 48 KB of LDS and 150 registers: three workgroups per CU (schur_kernel: two, at 222 registers), and the block products of
-// a 48-landmark chunk take 1.5 k matrix-core cycles per wave instead of 3 x 3 us of LDS-bound 6x6 block products.
+// How the landmarks reach the tiles:
+//   * pose parts within 63 rows (one tile pair; schur_mfma_kernel<3>, schur_ride_kernel<3>): a software pipeline over a RING of
+//     three tile sets of n = 4 landmarks (12 contraction indices = three whole groups of the instruction; 13.3 KB a set at 60
+//     rows).  One barrier per stage: between two barriers a wave writes stage s + 1 from registers, requests stage s + 4 into the
+//     registers that frees (straight-line requests: counted waits, three stages in flight) and runs the products of stage s.  One
+//     work-item per (pair, row of its 6 x 3 block): 240 of 256 work-items fill, neighbouring lanes read neighbouring 24 bytes of W,
+//     and 16 consecutive rows at stride 13 doubles write 32 distinct LDS banks.  The ring is zeroed once; a set is zeroed again, two
+//     barriers ahead of its fill, only in front of a stage that does not overwrite it (a pair missing, or the ragged last stage).
+//     The chunk's J^T J / J^T r lists are requested in front of V^-1 and summed behind the first fill.
+//   * the serial loop (SCH2_SERIAL; rounds 4-6): n = nlb = 12 landmarks per batch, one work-item per pair, zero / fill / products
+//     with a barrier behind each.  It stays for pose parts of several 96-row tiles (schur_mfma_kernel<9>) and, for one release, as
+//     the referee of the ring loop (okvis_ba_tuning::flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES; OKVIS_BA_ROUTE_SCHUR_KERNEL = 4).
+//     Both loops feed the matrix core the same groups of four indices in the same order into the same accumulators: the same sums
+//     bit for bit (tests/test_gpu_schur_pipeline.py); only the exact zeros of a ragged last batch are no longer added.
+//
+// 49 KB of LDS and 166 registers, no scratch in the Schur workgroups: three workgroups per CU (schur_kernel: two, at 222
+// registers), and the block products of a 48-landmark chunk take 1.5 k matrix-core cycles per wave instead of 3 x 3 us of
+// LDS-bound 6x6 block products.  Phase stamps and launch times: profiles/schur_pipeline_notes.md.
 #pragma once
 #include "ba_imu.hpp"
 #include "ba_schur.hpp"
@@ -33,8 +49,14 @@ __host__ __device__ constexpr int sch2_nlb(int trows, int budget) {
   return 4 * ((budget / (sch2_pad16(trows + 1) + sch2_pad16(trows)) - 1) / 12);
 }
 __host__ __device__ constexpr int sch2_tile_doubles(int trows, int nlb) { return (sch2_pad16(trows + 1) + sch2_pad16(trows)) * (3 * nlb + 1); }
+// the pipelined loop of the small tiles: a ring of SCH2_RING tile sets of SCH2_STAGE_LM landmarks each (12 contraction indices = three
+// whole groups of v_mfma_f64_16x16x4_f64; the chunk descriptor carries one pair range per four landmarks)
+constexpr int SCH2_RING = 3, SCH2_STAGE_LM = 4, SCH2_STAGE_KP = 3 * SCH2_STAGE_LM + 1;
+__host__ __device__ constexpr int sch2_ring_doubles(int trows) { return SCH2_RING * sch2_tile_doubles(trows, SCH2_STAGE_LM); }
 
-template <int SCH2_MAXT>
+// SCH2_SERIAL: the batch loop of rounds 4-6 (nlb landmarks per batch, three barriers per batch) — the large tiles, and the referee of
+// the pipelined loop (OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows, int final_call, int nlb,
                                                 const CtrlSlot* __restrict__ ctrls, int nodec, const int bx) {
   const WinPtrs& W = wins[blockIdx.y];
@@ -50,7 +72,9 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   const int n_tp = W.n_tile * (W.n_tile + 1) / 2;
   if (bx >= W.n_chunk * n_tp) return;
 
-  extern __shared__ __attribute__((aligned(16))) double sch_smem[];   // tY [pad16(tile_rows + 1)][3 nlb + 1] | tW [pad16(tile_rows)][3 nlb + 1]
+  static_assert(SCH2_SERIAL || SCH2_MAXT <= 3, "the pipelined loop serves the small tiles (one tile pair per chunk)");
+  // serial: tY [pad16(tile_rows + 1)][3 nlb + 1] | tW [pad16(tile_rows)][3 nlb + 1]; pipelined: SCH2_RING such sets of four landmarks
+  extern __shared__ __attribute__((aligned(16))) double sch_smem[];
   __shared__ double s_vinv[SCHUR_CHUNK_LM_MAX][6];   // (V_l + lambda D_l^2)^-1 of every landmark of the chunk
   __shared__ double s_vb[SCHUR_CHUNK_LM_MAX][3];     // V^-1 b
   __shared__ double s_diag[SCHUR_TILE_BLOCKS][36];   // diagonal 6x6 blocks of Y W^T (lower triangle)
@@ -97,6 +121,15 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   const int K = 3 * nlb, KP = K + 1;
   double* tY = sch_smem;
   double* tW = sch_smem + (size_t)sch2_pad16(tile_rows + 1) * KP;
+  // pipelined: set r of the ring = tY | tW of one stage at sch_smem + r * set_doubles, rows of SCH2_STAGE_KP doubles
+  const int rowsY = sch2_pad16(tile_rows + 1), set_doubles = (rowsY + sch2_pad16(tile_rows)) * SCH2_STAGE_KP;
+  if constexpr (!SCH2_SERIAL) {
+    // The whole ring is zeroed ONCE, behind the first loads: the padding rows stay zero for the life of the workgroup, and a set
+    // is zeroed again only in front of a stage that does not overwrite all of it (ring loop below).  Visible behind the barrier
+    // of the decision.
+    double2* z = reinterpret_cast<double2*>(sch_smem);
+    for (int i = tid; i < SCH2_RING * set_doubles / 2; i += SCHUR_THREADS) z[i] = make_double2(0.0, 0.0);
+  }
   // the per-group J^T J / J^T r partials (task outputs) that sum into the diagonal blocks of this tile pair: work-item e <
   // 36 nrow owns entry e of the blocks (up to SCH2_DI items), work-item r < 6 nrow row r of Y b | g | diag U.  Their list
   // heads (up to SCH2_LL entries; longer lists are walked in global memory) are static structure
@@ -143,16 +176,23 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   }
   // pair ranges of the landmark batches (uniform)
   constexpr int SCH2_NB = SCHUR_CHUNK_LM_MAX / 4;   // batches of >= 4 landmarks
-  int pbv[SCH2_NB + 1];
+  int pbv[SCH2_SERIAL ? SCH2_NB + 1 : 1];
+  if constexpr (SCH2_SERIAL) {
 #pragma unroll
-  for (int ib = 0; ib <= SCH2_NB; ++ib) pbv[ib] = cd[2 + min(ib * (nlb / 4), SCH2_NB)];
+    for (int ib = 0; ib <= SCH2_NB; ++ib) pbv[ib] = cd[2 + min(ib * (nlb / 4), SCH2_NB)];
+  }
   auto pb_at = [&](int ib) {
     int r = 0;
 #pragma unroll
-    for (int q = 0; q <= SCH2_NB; ++q)   // static indexing keeps the values in (scalar) registers
+    for (int q = 0; q <= (SCH2_SERIAL ? SCH2_NB : 0); ++q)   // static indexing keeps the values in (scalar) registers
       if (q == ib) r = pbv[q];
     return r;
   };
+  // pipelined: one range per stage of four landmarks = the descriptor's own entries, lane q of every wave holds entry q
+  static_assert(SCH2_NB + 1 <= 64, "one descriptor entry per lane");
+  const int pb_lane = SCH2_SERIAL ? 0 : cd[2 + min(lane, SCH2_NB)];
+  auto pb_stage = [&](int st) { return __builtin_amdgcn_readlane(pb_lane, min(st, SCH2_NB)); };   // (st uniform)
+  const int nst = (nl + SCH2_STAGE_LM - 1) / SCH2_STAGE_LM;
 
   // ---- what the reduction reads first, from the speculated buffer: the (landmark, block) rows of the first batch and the
   //      landmark blocks (one landmark per work-item: a chunk has at most SCHUR_CHUNK_LM_MAX <= SCHUR_THREADS of them) ----
@@ -160,6 +200,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   double wp[18];
   int f_slot = -1, f_lb = 0;
   auto load_batch = [&](int ib) {   // one work-item per (landmark, block) pair of batch ib
+    if constexpr (!SCH2_SERIAL) return;
     const int pp = pb_at(ib) + tid;
     f_slot = -1;
     if (!tiled && pp < pb_at(ib + 1)) {
@@ -168,6 +209,38 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
       for (int i = 0; i < 18; ++i) wp[i] = Wp[i];
       f_slot = W.pair_off[pp] / 6;
       f_lb = W.pair_lm[pp] - (lm_begin + ib * nlb);
+    }
+  };
+  // pipelined: one work-item per (pair, row of its 6 x 3 block) of a stage — a stage has at most four landmarks x 10 blocks, and
+  // neighbouring lanes read neighbouring rows (24 bytes each) of W.  Register set u holds the stage s with s % SCH2_RING == u from
+  // its request until it is written to set u of the ring.
+  static_assert(SCH2_SERIAL || SCH2_STAGE_LM * (SCH2_MAXT_SMALL_ROWS / 6) * 6 <= SCHUR_THREADS, "one pass of the workgroup fills a stage");
+  const int f_q = tid / 6, f_a = tid - 6 * f_q;
+  double sw[SCH2_RING][3];
+  int s_off[SCH2_RING], s_lm[SCH2_RING];   // pair_off / pair_lm as loaded: nothing is computed from a request before its fill
+  bool s_on[SCH2_RING];
+#pragma unroll
+  for (int u = 0; u < SCH2_RING; ++u) s_on[u] = false, s_off[u] = s_lm[u] = 0, sw[u][0] = sw[u][1] = sw[u][2] = 0.0;
+  // Every work-item requests in every stage — items without a pair re-read the chunk's last pair and drop it — so that the requests
+  // of a stage are straight-line code and the wait in front of a fill is a counted one that leaves the younger stages in flight.
+  const int p_last = SCH2_SERIAL ? 0 : pb_stage(SCH2_NB) - 1;   // (the entries behind the chunk's last stage repeat its end)
+  const bool any_pair = !SCH2_SERIAL && p_last >= pb_stage(0);   // (uniform; a chunk without a single pair requests nothing)
+  auto load_stage = [&](int u, int st) {   // (u static)
+    const int pp = pb_stage(st) + f_q;
+    s_on[u] = pp < pb_stage(st + 1);
+    const int pc = min(pp, p_last);
+    const double* Wp = Wb + (size_t)pc * 18 + 3 * f_a;
+    sw[u][0] = Wp[0], sw[u][1] = Wp[1], sw[u][2] = Wp[2];
+    s_off[u] = W.pair_off[pc], s_lm[u] = W.pair_lm[pc];
+  };
+  auto load_first = [&]() {
+    if constexpr (SCH2_SERIAL) {
+      load_batch(0);
+    } else {
+      if (any_pair) {
+#pragma unroll
+        for (int u = 0; u < SCH2_RING; ++u) load_stage(u, u);
+      }
     }
   };
   static_assert(SCHUR_CHUNK_LM_MAX <= SCHUR_THREADS, "one landmark per work-item");
@@ -181,7 +254,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
       lb3[0] = bl[0], lb3[1] = bl[1], lb3[2] = bl[2];
     }
   };
-  load_batch(0);
+  load_first();
   load_landmark(spec);
   if (!nodec) schur_decision_finish(W, opt, dl, final_call, bx, tid, s_ctrl, s_dec, s_lambda);
   __syncthreads();
@@ -193,46 +266,99 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   const double lambda = nodec ? (chead.y ? lam_next : (opt.dogleg ? c_mu : 1.0 / c_radius)) : s_lambda;
   if (acc != spec) {   // (a rejected trial: the other buffer is the one to reduce — requested again)
     Wb = W.W[acc];
-    load_batch(0);
+    load_first();
     load_landmark(acc);
   }
   const double* gp = W.gpart[acc];
+  // The chunk's J^T J / J^T r lists, summed in list order.  Serial loop: requested and summed here.  Pipelined loop: requested here,
+  // summed behind the first fill, where the workgroup would otherwise wait for nothing (they do not depend on the product); a
+  // pose part within 64 rows has at most SCH2_DIP x SCHUR_THREADS diagonal entries.
   double d_u[SCH2_DI], r_g = 0.0, r_du = 0.0;
-  if (diag) {
+  constexpr int SCH2_DIP = SCH2_SERIAL ? 1 : (SCH2_MAXT_SMALL_ROWS / 6 * 36 + SCHUR_THREADS - 1) / SCHUR_THREADS;
+  double d_v[SCH2_DIP][SCH2_LL], r_vg[SCH2_LL], r_vd[SCH2_LL];
 #pragma unroll
-    for (int it = 0; it < SCH2_DI; ++it) {
-      d_u[it] = 0.0;
+  for (int it = 0; it < SCH2_DI; ++it) d_u[it] = 0.0;
+  if constexpr (SCH2_SERIAL) {
+    if (diag) {
+  #pragma unroll
+      for (int it = 0; it < SCH2_DI; ++it) {
+        d_u[it] = 0.0;
+        const int e = tid + it * SCHUR_THREADS;
+        if (e < nrow * 36) {
+          const int k = e % 36, ii = k / 6, jj = k - 6 * ii;
+          if (jj <= ii) {   // U_pp: lower triangle, in list order
+            const int uk = jj * 6 - (jj * (jj - 1)) / 2 + (ii - jj);
+            double v[SCH2_LL];
+  #pragma unroll
+            for (int q = 0; q < SCH2_LL; ++q) v[q] = q < d_n[it] ? gp[d_out[it][q] + uk] : 0.0;
+  #pragma unroll
+            for (int q = 0; q < SCH2_LL; ++q) d_u[it] += v[q];
+            for (int q = SCH2_LL; q < d_n[it]; ++q) d_u[it] += gp[W.chunk_diag_out[d_q0[it] + q] + uk];
+          }
+        }
+      }
+      if (tid < 6 * nrow) {
+        const int a = tid % 6, dk = a * 6 - (a * (a - 1)) / 2;
+        double vg[SCH2_LL], vd[SCH2_LL];
+  #pragma unroll
+        for (int q = 0; q < SCH2_LL; ++q) {
+          vg[q] = q < r_n ? gp[r_out[q] + 21 + a] : 0.0;
+          vd[q] = q < r_n ? gp[r_out[q] + dk] : 0.0;
+        }
+  #pragma unroll
+        for (int q = 0; q < SCH2_LL; ++q) r_g += vg[q], r_du += vd[q];
+        for (int q = SCH2_LL; q < r_n; ++q) {
+          const double* o = gp + W.chunk_diag_out[r_q0 + q];
+          r_g += o[21 + a];
+          r_du += o[dk];
+        }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int it = 0; it < SCH2_DIP; ++it) {
+      const int e = tid + it * SCHUR_THREADS;
+      const int k = e % 36, ii = k / 6, jj = k - 6 * ii;
+      const int uk = jj * 6 - (jj * (jj - 1)) / 2 + (ii - jj);
+      const bool on = diag && e < nrow * 36 && jj <= ii;   // U_pp: lower triangle
+#pragma unroll
+      for (int q = 0; q < SCH2_LL; ++q) d_v[it][q] = on && q < d_n[it] ? gp[d_out[it][q] + uk] : 0.0;
+    }
+  }
+  auto lists_request_rows = [&]() {   // (pipelined loop: g | diag U of the rows, requested behind V^-1 — registers)
+    const int a = tid % 6, dk = a * 6 - (a * (a - 1)) / 2;
+#pragma unroll
+    for (int q = 0; q < SCH2_LL; ++q) {
+      r_vg[q] = diag && tid < 6 * nrow && q < r_n ? gp[r_out[q] + 21 + a] : 0.0;
+      r_vd[q] = diag && tid < 6 * nrow && q < r_n ? gp[r_out[q] + dk] : 0.0;
+    }
+  };
+  auto lists_sum = [&]() {   // (pipelined loop)
+    if (!diag) return;
+#pragma unroll
+    for (int it = 0; it < SCH2_DIP; ++it) {
       const int e = tid + it * SCHUR_THREADS;
       if (e < nrow * 36) {
         const int k = e % 36, ii = k / 6, jj = k - 6 * ii;
-        if (jj <= ii) {   // U_pp: lower triangle, in list order
+        if (jj <= ii) {
           const int uk = jj * 6 - (jj * (jj - 1)) / 2 + (ii - jj);
-          double v[SCH2_LL];
 #pragma unroll
-          for (int q = 0; q < SCH2_LL; ++q) v[q] = q < d_n[it] ? gp[d_out[it][q] + uk] : 0.0;
-#pragma unroll
-          for (int q = 0; q < SCH2_LL; ++q) d_u[it] += v[q];
+          for (int q = 0; q < SCH2_LL; ++q) d_u[it] += d_v[it][q];
           for (int q = SCH2_LL; q < d_n[it]; ++q) d_u[it] += gp[W.chunk_diag_out[d_q0[it] + q] + uk];
         }
       }
     }
     if (tid < 6 * nrow) {
       const int a = tid % 6, dk = a * 6 - (a * (a - 1)) / 2;
-      double vg[SCH2_LL], vd[SCH2_LL];
 #pragma unroll
-      for (int q = 0; q < SCH2_LL; ++q) {
-        vg[q] = q < r_n ? gp[r_out[q] + 21 + a] : 0.0;
-        vd[q] = q < r_n ? gp[r_out[q] + dk] : 0.0;
-      }
-#pragma unroll
-      for (int q = 0; q < SCH2_LL; ++q) r_g += vg[q], r_du += vd[q];
+      for (int q = 0; q < SCH2_LL; ++q) r_g += r_vg[q], r_du += r_vd[q];
       for (int q = SCH2_LL; q < r_n; ++q) {
         const double* o = gp + W.chunk_diag_out[r_q0 + q];
         r_g += o[21 + a];
         r_du += o[dk];
       }
     }
-  }
+  };
   // (V_l + lambda D_l^2)^-1 and V^-1 b of every landmark of the chunk (work-item i: landmark i, its blocks are in registers)
   if (tid < nl) {
     const int i = tid;
@@ -255,9 +381,17 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     }
 #pragma unroll
     for (int e = 0; e < 6; ++e) s_vinv[i][e] = vi[e];
-    s_vb[i][0] = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
-    s_vb[i][1] = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
-    s_vb[i][2] = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
+    if constexpr (SCH2_SERIAL) {
+      s_vb[i][0] = vi[0] * b0 + vi[1] * b1 + vi[2] * b2;
+      s_vb[i][1] = vi[1] * b0 + vi[3] * b1 + vi[4] * b2;
+      s_vb[i][2] = vi[2] * b0 + vi[4] * b1 + vi[5] * b2;
+    } else {
+      // (the contraction the compiler gives the expressions above in the serial loop, spelled out: which product stays a product
+      //  depends on the code around it, and the two loops have to agree to the bit)
+      s_vb[i][0] = __builtin_fma(vi[2], b2, __builtin_fma(vi[1], b1, vi[0] * b0));
+      s_vb[i][1] = __builtin_fma(vi[4], b2, __builtin_fma(vi[3], b1, vi[1] * b0));
+      s_vb[i][2] = __builtin_fma(vi[5], b2, __builtin_fma(vi[4], b1, vi[2] * b0));
+    }
   }
 
   // ---- my output tiles: tt = wave + 4 t; diagonal tile pair: tile (I, J) with J <= min(I, CT - 1), else all RT x CT ----
@@ -286,95 +420,197 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
 #pragma unroll
   for (int t = 0; t < SCH2_MAXT; ++t) accv[t] = sch2_v4{0.0, 0.0, 0.0, 0.0};
 
-  int ib = 0;
-  for (int l0 = lm_begin; l0 < lm_end; l0 += nlb, ++ib) {
-    const int nb = min(nlb, lm_end - l0);
-    const int p0 = pb_at(ib), p1 = pb_at(ib + 1);
-    {
-      double2* z = reinterpret_cast<double2*>(sch_smem);
-      const int n2 = (sch2_pad16(tile_rows + 1) + sch2_pad16(tile_rows)) * KP / 2;
-      for (int i = tid; i < n2; i += SCHUR_THREADS) z[i] = make_double2(0.0, 0.0);
-    }
-    __syncthreads();
-    if (l0 == lm_begin) SSTAMP(18);
-    auto fill = [&](const double (&w18)[18], int slot, int lb) {
-      if (slot >= row0 && slot < row0 + nrow) {
-        const double* vi = s_vinv[l0 - lm_begin + lb];
-        const double v0 = vi[0], v1 = vi[1], v2 = vi[2], v3 = vi[3], v4 = vi[4], v5 = vi[5];
-        double* y = tY + (size_t)(slot - row0) * 6 * KP + 3 * lb;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          const double w0 = w18[3 * a], w1 = w18[3 * a + 1], w2 = w18[3 * a + 2];
-          y[a * KP] = w0 * v0 + w1 * v1 + w2 * v2;
-          y[a * KP + 1] = w0 * v1 + w1 * v3 + w2 * v4;
-          y[a * KP + 2] = w0 * v2 + w1 * v4 + w2 * v5;
-        }
+  if constexpr (SCH2_SERIAL) {
+    int ib = 0;
+    for (int l0 = lm_begin; l0 < lm_end; l0 += nlb, ++ib) {
+      const int nb = min(nlb, lm_end - l0);
+      const int p0 = pb_at(ib), p1 = pb_at(ib + 1);
+      {
+        double2* z = reinterpret_cast<double2*>(sch_smem);
+        const int n2 = (sch2_pad16(tile_rows + 1) + sch2_pad16(tile_rows)) * KP / 2;
+        for (int i = tid; i < n2; i += SCHUR_THREADS) z[i] = make_double2(0.0, 0.0);
       }
-      if (slot >= col0 && slot < col0 + ncol) {
-        double* w = tW + (size_t)(slot - col0) * 6 * KP + 3 * lb;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-          w[a * KP] = w18[3 * a];
-          w[a * KP + 1] = w18[3 * a + 1];
-          w[a * KP + 2] = w18[3 * a + 2];
+      __syncthreads();
+      if (l0 == lm_begin) SSTAMP(18);
+      auto fill = [&](const double (&w18)[18], int slot, int lb) {
+        if (slot >= row0 && slot < row0 + nrow) {
+          const double* vi = s_vinv[l0 - lm_begin + lb];
+          const double v0 = vi[0], v1 = vi[1], v2 = vi[2], v3 = vi[3], v4 = vi[4], v5 = vi[5];
+          double* y = tY + (size_t)(slot - row0) * 6 * KP + 3 * lb;
+  #pragma unroll
+          for (int a = 0; a < 6; ++a) {
+            const double w0 = w18[3 * a], w1 = w18[3 * a + 1], w2 = w18[3 * a + 2];
+            y[a * KP] = w0 * v0 + w1 * v1 + w2 * v2;
+            y[a * KP + 1] = w0 * v1 + w1 * v3 + w2 * v4;
+            y[a * KP + 2] = w0 * v2 + w1 * v4 + w2 * v5;
+          }
         }
-      }
-    };
-    if (f_slot >= 0) fill(wp, f_slot, f_lb);
-    if constexpr (SCH2_MAXT > 3) {
-      if (tiled) {
-        // only the pairs of this tile pair: item = (landmark of the batch, row | column tile, block of the tile)
-        for (int it = tid; it < nb * 32; it += SCHUR_THREADS) {
-          const int lb = it >> 5, side = (it >> 4) & 1;
-          if (diag && side) continue;   // (row tile = column tile: the row side fills both operands)
-          const int2 r = s_tb[2 * (l0 - lm_begin + lb) + side];
-          const int q = r.x + (it & 15);
-          if (q < r.y) {
-            const double* Wp = Wb + (size_t)q * 18;
-            double w2[18];
-#pragma unroll
-            for (int i = 0; i < 18; ++i) w2[i] = Wp[i];
-            fill(w2, W.pair_off[q] / 6, lb);
+        if (slot >= col0 && slot < col0 + ncol) {
+          double* w = tW + (size_t)(slot - col0) * 6 * KP + 3 * lb;
+  #pragma unroll
+          for (int a = 0; a < 6; ++a) {
+            w[a * KP] = w18[3 * a];
+            w[a * KP + 1] = w18[3 * a + 1];
+            w[a * KP + 2] = w18[3 * a + 2];
+          }
+        }
+      };
+      if (f_slot >= 0) fill(wp, f_slot, f_lb);
+      if constexpr (SCH2_MAXT > 3) {
+        if (tiled) {
+          // only the pairs of this tile pair: item = (landmark of the batch, row | column tile, block of the tile)
+          for (int it = tid; it < nb * 32; it += SCHUR_THREADS) {
+            const int lb = it >> 5, side = (it >> 4) & 1;
+            if (diag && side) continue;   // (row tile = column tile: the row side fills both operands)
+            const int2 r = s_tb[2 * (l0 - lm_begin + lb) + side];
+            const int q = r.x + (it & 15);
+            if (q < r.y) {
+              const double* Wp = Wb + (size_t)q * 18;
+              double w2[18];
+  #pragma unroll
+              for (int i = 0; i < 18; ++i) w2[i] = Wp[i];
+              fill(w2, W.pair_off[q] / 6, lb);
+            }
           }
         }
       }
+      for (int q = p0 + tid + SCHUR_THREADS; !tiled && q < p1; q += SCHUR_THREADS) {   // more than 256 pairs in the batch
+        const double* Wp = Wb + (size_t)q * 18;
+        double w2[18];
+  #pragma unroll
+        for (int i = 0; i < 18; ++i) w2[i] = Wp[i];
+        fill(w2, W.pair_off[q] / 6, W.pair_lm[q] - l0);
+      }
+      if (diag && tid < nb) {   // row 6 nrow of the row tile: V^-1 b (gives Y b = W V^-1 b in that row of the product)
+        double* y = tY + (size_t)(6 * nrow) * KP + 3 * tid;
+        const double* vb = s_vb[l0 - lm_begin + tid];
+        y[0] = vb[0], y[1] = vb[1], y[2] = vb[2];
+      }
+      // the next batch's rows are requested now: in flight during the products
+      if (l0 + nlb < lm_end) load_batch(ib + 1);
+      __syncthreads();
+      if (l0 == lm_begin) SSTAMP(19);
+  #pragma unroll
+      for (int t = 0; t < SCH2_MAXT; ++t) {
+        const int tt = wave + 4 * t;
+        if (tt < ntiles) {
+          int I, J;
+          tile_of(tt, I, J);
+          const double* pa = tY + (size_t)(16 * I + (lane & 15)) * KP + (lane >> 4);
+          const double* pb = tW + (size_t)(16 * J + (lane & 15)) * KP + (lane >> 4);
+          sch2_v4 a = accv[t];
+          for (int k = 0; k < K; k += 12) {   // (K = 3 nlb is a multiple of 12) six operands in flight, then three products
+            const double a0 = pa[k], b0 = pb[k], a1 = pa[k + 4], b1 = pb[k + 4], a2 = pa[k + 8], b2 = pb[k + 8];
+            a = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, a, 0, 0, 0);
+            a = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, a, 0, 0, 0);
+          }
+          accv[t] = a;
+        }
+      }
+      if (l0 + nlb < lm_end) __syncthreads();
+      if (l0 == lm_begin) SSTAMP(20);
     }
-    for (int q = p0 + tid + SCHUR_THREADS; !tiled && q < p1; q += SCHUR_THREADS) {   // more than 256 pairs in the batch
-      const double* Wp = Wb + (size_t)q * 18;
-      double w2[18];
-#pragma unroll
-      for (int i = 0; i < 18; ++i) w2[i] = Wp[i];
-      fill(w2, W.pair_off[q] / 6, W.pair_lm[q] - l0);
-    }
-    if (diag && tid < nb) {   // row 6 nrow of the row tile: V^-1 b (gives Y b = W V^-1 b in that row of the product)
-      double* y = tY + (size_t)(6 * nrow) * KP + 3 * tid;
-      const double* vb = s_vb[l0 - lm_begin + tid];
-      y[0] = vb[0], y[1] = vb[1], y[2] = vb[2];
-    }
-    // the next batch's rows are requested now: in flight during the products
-    if (l0 + nlb < lm_end) load_batch(ib + 1);
-    __syncthreads();
-    if (l0 == lm_begin) SSTAMP(19);
+  } else {
+    // ---- The ring loop.  Stage st = landmarks [4 st, 4 st + 4) of the chunk = 12 contraction indices = the three groups of four
+    //      that the serial loop feeds the matrix core at the same place of the same order, so every accumulator sees the same
+    //      sums.  One barrier per stage; between two barriers a wave
+    //        zeroes set (st + 2) % 3   if stage st + 2 will not overwrite all that stage st - 1 left there,
+    //        writes stage st + 1        from its registers (requested three stages ago) into set (st + 1) % 3,
+    //        requests stage st + 4      into the registers that this frees,
+    //        runs the products of stage st on set st % 3.
+    //      Set (st + 2) % 3 was last read by the products of stage st - 1, in front of the previous barrier; the fill of stage
+    //      st + 2 comes behind the next one.  Nothing here waits for anything but the workgroup's own barrier. ----
+    lists_request_rows();
+    __syncthreads();   // s_vinv / s_vb
+    SSTAMP(18);
+    const bool vb_item = diag && tid >= SCHUR_THREADS - SCH2_STAGE_LM;   // the V^-1 b row: the last work-items, idle in the fill
+    auto write_stage = [&](int u, int st) {   // (u static: register set and ring set)
+      double* sy = sch_smem + (size_t)u * set_doubles;
+      double* sW = sy + (size_t)rowsY * SCH2_STAGE_KP;
+      const int slot = s_off[u] / 6, lb = s_lm[u] - (lm_begin + st * SCH2_STAGE_LM);
+      if (s_on[u] && (unsigned)lb < (unsigned)SCH2_STAGE_LM) {
+        const double w0 = sw[u][0], w1 = sw[u][1], w2 = sw[u][2];
+        if (slot >= row0 && slot < row0 + nrow) {
+          const double* vi = s_vinv[st * SCH2_STAGE_LM + lb];
+          const double v0 = vi[0], v1 = vi[1], v2 = vi[2], v3 = vi[3], v4 = vi[4], v5 = vi[5];
+          double* y = sy + (size_t)((slot - row0) * 6 + f_a) * SCH2_STAGE_KP + 3 * lb;
+          // Y = W V^-1: w0 v0 + w1 v1 + w2 v2 with the contraction of the serial loop's fill spelled out (see s_vb)
+          y[0] = __builtin_fma(w2, v2, __builtin_fma(w0, v0, w1 * v1));
+          y[1] = __builtin_fma(w2, v4, __builtin_fma(w0, v1, w1 * v3));
+          y[2] = __builtin_fma(w2, v5, __builtin_fma(w0, v2, w1 * v4));
+        }
+        if (slot >= col0 && slot < col0 + ncol) {
+          double* w = sW + (size_t)((slot - col0) * 6 + f_a) * SCH2_STAGE_KP + 3 * lb;
+          w[0] = w0, w[1] = w1, w[2] = w2;
+        }
+      }
+      const int vl = tid - (SCHUR_THREADS - SCH2_STAGE_LM);
+      if (vb_item && st * SCH2_STAGE_LM + vl < nl) {   // row 6 nrow of the row tile: V^-1 b (gives Y b = W V^-1 b in that row of the product)
+        double* y = sy + (size_t)(6 * nrow) * SCH2_STAGE_KP + 3 * vl;
+        const double* vb = s_vb[st * SCH2_STAGE_LM + vl];
+        y[0] = vb[0], y[1] = vb[1], y[2] = vb[2];
+      }
+    };
+    // a stage overwrites everything an earlier stage wrote to its set iff it has four landmarks with a pair on every block
+    auto dense = [&](int st) { return (st + 1) * SCH2_STAGE_LM <= nl && pb_stage(st + 1) - pb_stage(st) == SCH2_STAGE_LM * nrow; };
+    // my tiles' operand rows (loop invariants)
+    int offa[SCH2_MAXT], offb[SCH2_MAXT];
 #pragma unroll
     for (int t = 0; t < SCH2_MAXT; ++t) {
-      const int tt = wave + 4 * t;
-      if (tt < ntiles) {
-        int I, J;
-        tile_of(tt, I, J);
-        const double* pa = tY + (size_t)(16 * I + (lane & 15)) * KP + (lane >> 4);
-        const double* pb = tW + (size_t)(16 * J + (lane & 15)) * KP + (lane >> 4);
-        sch2_v4 a = accv[t];
-        for (int k = 0; k < K; k += 12) {   // (K = 3 nlb is a multiple of 12) six operands in flight, then three products
-          const double a0 = pa[k], b0 = pb[k], a1 = pa[k + 4], b1 = pb[k + 4], a2 = pa[k + 8], b2 = pb[k + 8];
-          a = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, a, 0, 0, 0);
-          a = __builtin_amdgcn_mfma_f64_16x16x4f64(a2, b2, a, 0, 0, 0);
+      int I = 0, J = 0;
+      if (wave + 4 * t < ntiles) tile_of(wave + 4 * t, I, J);
+      offa[t] = (16 * I + (lane & 15)) * SCH2_STAGE_KP + (lane >> 4);
+      offb[t] = (rowsY + 16 * J + (lane & 15)) * SCH2_STAGE_KP + (lane >> 4);
+    }
+    auto products = [&](int u, int st) {   // (u static)
+      const double* sy = sch_smem + (size_t)u * set_doubles;
+      // groups of four indices with a landmark in them: 3; 1 - 3 in a ragged last stage, none behind it
+      const int ng = (3 * max(0, min(SCH2_STAGE_LM, nl - st * SCH2_STAGE_LM)) + 3) / 4;
+      double oa[SCH2_MAXT][3], ob[SCH2_MAXT][3];
+#pragma unroll
+      for (int t = 0; t < SCH2_MAXT; ++t)   // the operand reads of every tile go out before the first product
+        if (wave + 4 * t < ntiles) {
+#pragma unroll
+          for (int g = 0; g < 3; ++g) oa[t][g] = sy[offa[t] + 4 * g], ob[t][g] = sy[offb[t] + 4 * g];
         }
-        accv[t] = a;
+#pragma unroll
+      for (int t = 0; t < SCH2_MAXT; ++t)
+        if (wave + 4 * t < ntiles) {
+          sch2_v4 a = accv[t];
+          if (ng > 0) a = __builtin_amdgcn_mfma_f64_16x16x4f64(oa[t][0], ob[t][0], a, 0, 0, 0);
+          if (ng > 1) a = __builtin_amdgcn_mfma_f64_16x16x4f64(oa[t][1], ob[t][1], a, 0, 0, 0);
+          if (ng > 2) a = __builtin_amdgcn_mfma_f64_16x16x4f64(oa[t][2], ob[t][2], a, 0, 0, 0);
+          accv[t] = a;
+        }
+    };
+    // prologue = the step in front of stage 0 (nothing to multiply yet), then the steps st = 0 .. nst - 1, three to a round so that
+    // register sets and ring sets are named statically
+    if (any_pair) {
+      write_stage(0, 0);
+      load_stage(0, SCH2_RING);
+    }
+    lists_sum();
+    __syncthreads();
+    SSTAMP(19);
+    for (int s0 = 0; any_pair && s0 < nst; s0 += SCH2_RING) {
+#pragma unroll
+      for (int u = 0; u < SCH2_RING; ++u) {
+        // (the steps of the last round behind the chunk's last stage find no pair, no landmark and no group: the fill, the request
+        //  and the barrier stay unconditional so that the requests of three stages are straight-line code with counted waits)
+        const int st = s0 + u;
+        constexpr int SCH2_R = SCH2_RING;
+        if (st >= 1 && st + 2 < nst && !dense(st + 2)) {
+          double2* z = reinterpret_cast<double2*>(sch_smem + (size_t)((u + 2) % SCH2_R) * set_doubles);
+          for (int i = tid; i < set_doubles / 2; i += SCHUR_THREADS) z[i] = make_double2(0.0, 0.0);
+        }
+        write_stage((u + 1) % SCH2_R, st + 1);
+        load_stage((u + 1) % SCH2_R, st + 1 + SCH2_R);
+        products(u, st);
+        __syncthreads();
+        if (st == 0) SSTAMP(20);
       }
     }
-    if (l0 + nlb < lm_end) __syncthreads();
-    if (l0 == lm_begin) SSTAMP(20);
   }
   SSTAMP(21);
 
@@ -487,10 +723,10 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
 }
 
 
-template <int SCH2_MAXT>
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_mfma_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp,
                                                                       int tile_rows, int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec) {
-  schur_mfma_body<SCH2_MAXT>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x);
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x);
 }
 
 // The decision-free Schur launch with the EVALUATION of the IMU / prior factors of the same trial riding along (round 6): workgroups
@@ -499,7 +735,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_m
 // Schur workgroups.  Neither kind waits for the other — the reduction does not need the factors' costs when it takes no decision —
 // and both only have to be through before the next solve launch.  (Round 5 let the WHOLE factor workgroups ride: 255 registers and
 // 62 KB of LDS of the re-preintegration path put the launch at two workgroups per CU and cost the line 6 %; this half keeps three.)
-template <int SCH2_MAXT>
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __global__ __launch_bounds__(SCHUR_THREADS, 3) void schur_ride_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows,
                                                                       int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec, int n_small) {
   static_assert(SCHUR_THREADS == IMU_THREADS && SCHUR_THREADS == LIN_THREADS, "one block size for both kinds of workgroup");
@@ -508,7 +744,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, 3) void schur_ride_kernel(const WinP
     small_body<2>(wins[blockIdx.y], 0, (int)blockIdx.x, sch_smem);
     return;
   }
-  schur_mfma_body<SCH2_MAXT>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small);
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small);
 }
 
 }  // namespace ba

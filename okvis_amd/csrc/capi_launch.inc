@@ -52,7 +52,9 @@ std::vector<std::pair<const void*, size_t>> plan_kernels() {
           {f(&linearize_kernel<true, float, true>), ef}, {f(&linearize_kernel<true, float, false>), ef},
           {f(&linearize_kernel<true, double, true>), ed}, {f(&linearize_kernel<true, double, false>), ed},
           {f(&linearize_kernel<false, float, true>), pf}, {f(&linearize_kernel<false, float, false>), pf},
-          {f(&linearize_kernel<false, double, true>), pd}, {f(&linearize_kernel<false, double, false>), pd}};
+          {f(&linearize_kernel<false, double, true>), pd}, {f(&linearize_kernel<false, double, false>), pd},
+          // (the serial batch loop of the small tiles: the referee of the pipelined one, OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
+          {f(&schur_ride_kernel<3, true>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3, true>), wide}};
 }
 
 // ---- The instantiations a launch plan names (Launch::k is the index in the table of its kind) ----
@@ -74,7 +76,7 @@ enum { SOLVE_NONE, SOLVE_DENSE, SOLVE_DENSE_DBUF, SOLVE_CHAIN, SOLVE_CHAIN_DBUF,
 const SolveFn SOLVE[6] = {nullptr, &solve_kernel<false, false>, &solve_kernel<false, true>, &solve_kernel<false, false, true>,
                           &solve_kernel<false, true, true>, &solve_kernel<true, false>};
 // the Schur launch (the first four: OKVIS_BA_ROUTE_SCHUR_KERNEL) and the factors' own launch (their kernels' arguments differ)
-enum { SCHUR_NONE, SCHUR_VALU, SCHUR_MFMA3, SCHUR_MFMA9, SCHUR_RIDE3 };
+enum { SCHUR_NONE, SCHUR_VALU, SCHUR_MFMA3, SCHUR_MFMA9, SCHUR_RIDE3, SCHUR_MFMA3_SERIAL, SCHUR_RIDE3_SERIAL };
 enum { SMALL_NONE, SMALL_ALL, SMALL_PREPARE };
 // The launch plan (LaunchPlan) of a batch of n_windows laid out by L whose windows have the maxima M, under the options o.  Host only:
 // okvis_ba_upload computes it, okvis_ba_set_options again for the options of an uploaded batch, and every launch of the solver reads
@@ -99,14 +101,18 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
     if (!M.any_ext && schur_mfma_allowed(o) && (small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_MFMA_LARGE))) {
       p.nlb = sch2_nlb(p.trows, 5120);                  // 40 KB of tiles: three workgroups per CU
       if (p.nlb < 12) p.nlb = sch2_nlb(p.trows, 9216);  // wide tiles: 72 KB, two per CU
-      const int sm = sch2_tile_doubles(p.trows, p.nlb) * (int)sizeof(double);
+      // the small tiles: stages of four landmarks pipelined over a ring of three tile sets (39 KB at 60 rows: three per CU as well);
+      // OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES keeps the batch loop above as the referee
+      const bool serial = !small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES);
+      if (!serial) p.nlb = SCH2_STAGE_LM;
+      const int sm = (serial ? sch2_tile_doubles(p.trows, p.nlb) : sch2_ring_doubles(p.trows)) * (int)sizeof(double);
       // The EVALUATION of the IMU / prior factors rides in the decision-free launch with the small tiles (schur_ride_kernel) where
       // they have a launch of their own (piece path, batches of 40 windows and more): small_prepare_kernel right behind the solve
       // launch keeps what may change a preintegration record, the rest leaves the chain of the sub-batch.
       // okvis_ba_tuning::flags & OKVIS_BA_TUNE_NO_SMALL_RIDE: the whole factors in small_kernel as until round 6.
       p.rides = small_tiles && p.nodec && L.split_small && !(o.tuning.flags & OKVIS_BA_TUNE_NO_SMALL_RIDE);
-      if (p.rides) p.schur = Launch{SCHUR_RIDE3, p.n_small + M.schur_blocks, std::max(sm, (int)small_eval_smem())};
-      else p.schur = Launch{small_tiles ? SCHUR_MFMA3 : SCHUR_MFMA9, M.schur_blocks, sm};
+      if (p.rides) p.schur = Launch{serial ? SCHUR_RIDE3_SERIAL : SCHUR_RIDE3, p.n_small + M.schur_blocks, std::max(sm, (int)small_eval_smem())};
+      else p.schur = Launch{!small_tiles ? SCHUR_MFMA9 : serial ? SCHUR_MFMA3_SERIAL : SCHUR_MFMA3, M.schur_blocks, sm};
     } else {
       p.schur = Launch{SCHUR_VALU, M.schur_blocks, (int)(2 * SCHUR_LM_BATCH * p.trows * 3 * sizeof(double))};
     }
@@ -216,6 +222,8 @@ hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
     case SCHUR_MFMA3: hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
     case SCHUR_MFMA9: hipLaunchKernelGGL(schur_mfma_kernel<9>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
     case SCHUR_RIDE3: hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small); break;
+    case SCHUR_MFMA3_SERIAL: hipLaunchKernelGGL((schur_mfma_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
+    case SCHUR_RIDE3_SERIAL: hipLaunchKernelGGL((schur_ride_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small); break;
   }
   return hipGetLastError();
 }

@@ -16,11 +16,13 @@ prev = 0
 for k in (1, 2, 5, 6, 7, 8, 9):
     d = p[k]-p[prev]; prev = k; print(f"  {names[k]:16s} {d:10.0f} cyc  {d/2100:8.2f} us")
 print("  total", p[9]-p[0], (p[9]-p[0])/2100)
-sn = {17: "decision", 18: "batch 0: zero tables + V^-1", 19: "batch 0: fill Y / W tables", 20: "batch 0: block products",
-      21: "remaining batches", 22: "U_pp / cross lists", 23: "slice reduction + write"}
+# (ring loop of the small tiles, ba_schur2.hpp: batch = stage of 4 landmarks, the list sums sit behind the first fill;
+#  serial loop, okvis_ba_tuning::flags 0x200: batch = 12 landmarks, the list sums and the zeroing in front of it)
+sn = {17: "head / decision", 18: "V^-1 (serial: + list sums, zeroing)", 19: "batch 0: fill Y / W tiles", 20: "batch 0: block products",
+      21: "remaining batches", 22: "accumulators -> LDS image", 23: "partial stores"}
 print("schur phases (workgroup 0, thread 0):")
 for k in range(17, 24):
-    d = p[k]-p[k-1]; print(f"  {sn[k]:30s} {d:10.0f} cyc {d/2100:8.2f} us")
+    d = p[k]-p[k-1]; print(f"  {sn[k]:36s} {d:10.0f} cyc {d/2100:8.2f} us")
 print("  total", (p[23]-p[16])/2100, "us")
 print("sb levels (us): level 0 factor", (p[53]-p[52])/2100, " Y", (p[54]-p[53])/2100, " update", (p[55]-p[54])/2100, " all levels", (p[56]-p[52])/2100, " dense chol", (p[7]-p[56])/2100, " dense backsub", (p[57]-p[7])/2100, " sb recovery", (p[8]-p[57])/2100)
 print("kb=0: panel", p[11]-p[10], "trailing(thread0 work)", p[26]-p[11], "trailing+barrier", p[12]-p[11])
