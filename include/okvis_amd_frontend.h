@@ -1,5 +1,5 @@
 /*
- * okvis_amd_frontend.h — C-ABI of the batched reprojection pieces of the OKVIS frontend.
+ * okvis_amd_frontend.h — C-ABI of the batched reprojection and matching pieces of the OKVIS frontend.
  *
  * The frontend calls the backend's reprojection algebra once per candidate match, one at a time, from the matcher's inner
  * loop.  These entries do the same arithmetic for ALL candidates of one (frame A, frame B, camera pair) in one launch:
@@ -11,9 +11,16 @@
  *                                (okvis_frontend/src/VioKeyframeWindowMatchingAlgorithm.cpp:165-213)
  *   okvis_fe_gate_3d2d           ... ::verifyMatch (:320-337) and the gate of ::setBestMatch (:494-512)
  *
+ * and the matching itself, for binary descriptors of 16, 32, 48 (BRISK) or 64 bytes under the Hamming distance:
+ *
+ *   okvis_fe_hamming_candidates  every pair of keypoints whose descriptors are closer than a threshold, in ascending (a, b) order
+ *                                (the double loop a matching algorithm's doSetup would run on the host)
+ *   okvis_fe_match_descriptors   okvis::DenseMatcher::match with ONE matcher thread, for many image pairs per call
+ *                                (okvis_matcher/include/okvis/implementation/DenseMatcher.hpp:47-225, okvis_matcher/src/DenseMatcher.cpp:69-111)
+ *
  * What stays with the caller is what needs the estimator's book-keeping or image data: which keypoints carry a landmark,
- * descriptor distances, the best-match search, addLandmark / addObservation.  G = PinholeCamera<D> with the distortion
- * models of okvis_amd_ba.h.  All arithmetic is IEEE double like the reference; keypoints are float like cv::KeyPoint.
+ * addLandmark / addObservation.  G = PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
+ * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
  * Plain pointers and sizes, int status codes (okvis_amd_ba.h), host buffers in and out; no CPU path.
  */
 #ifndef OKVIS_AMD_FRONTEND_H_
@@ -90,6 +97,40 @@ int okvis_fe_project_landmarks(okvis_fe_context* ctx, const okvis_fe_camera* cam
  * chi2 [n_pairs] = err^T (sigma_B^2 I + U_a)^-1 err, flags [n_pairs]. */
 int okvis_fe_gate_3d2d(okvis_fe_context* ctx, int32_t n_proj, const double* uv, const double* U, int32_t n_b,
                        const float* kp_b, int32_t n_pairs, const int32_t* pairs, double* chi2, uint8_t* flags);
+
+/* Descriptors: desc_bytes = 16, 32, 48 or 64 (brisk::Hamming::PopcntofXORed with numberOf128BitWords 1..4), desc_a [n_a][desc_bytes],
+ * desc_b [n_b][desc_bytes], row after row.  skip_a [n_a] / skip_b [n_b]: non-zero = the keypoint is out of play (skipA / skipB of
+ * okvis::MatchingAlgorithm); NULL = none is.  At most 65536 keypoints per image.  An image without keypoints is valid.
+ *
+ * Every pair (a, b) of keypoints in play with (float)popcount(desc_a[a] ^ desc_b[b]) < threshold (strictly), in ascending (a, b)
+ * order.  *n_pairs always receives the number of such pairs (INT32_MAX where it does not fit); pairs [capacity][2] and dist [capacity]
+ * (may be NULL) receive the first min(capacity, total) of them.  A total above capacity is not an error: size the buffers by
+ * *n_pairs and call again (capacity 0 only counts). */
+int okvis_fe_hamming_candidates(okvis_fe_context* ctx, int32_t desc_bytes, int32_t n_a, const uint8_t* desc_a, const uint8_t* skip_a,
+                                int32_t n_b, const uint8_t* desc_b, const uint8_t* skip_b, float threshold, int32_t capacity,
+                                int32_t* pairs, float* dist, int32_t* n_pairs);
+
+typedef struct okvis_fe_match_job { /* one (image A, image B) */
+  int32_t n_a, n_b;
+  const uint8_t *desc_a, *desc_b, *skip_a, *skip_b;
+  int32_t* pair_a;   /* [n_b] out: vpairs[b].indexA after matchBody, -1 = unpaired      */
+  float* pair_dist;  /* [n_b] out: vpairs[b].distance (FLT_MAX where unpaired)          */
+  uint8_t* accepted; /* [n_b] out: 1 where matchBody would call setBestMatch(pair_a, b) */
+} okvis_fe_match_job;
+
+/* okvis::DenseMatcher(1, num_best, use_ratio).match(algorithm) for every job, where algorithm.distance(a, b) is the Hamming distance
+ * of the two descriptors if that is < threshold and FLT_MAX otherwise, distanceThreshold() = threshold and distanceRatioThreshold()
+ * = ratio_threshold.  The semantics are those of ONE matcher thread: the rows of A in ascending order, each row's list of its
+ * num_best closest b built by scanning b in ascending order (a candidate enters only if strictly closer than the list's last entry,
+ * in front of entries of its own distance), assignbest directly after the row's scan (a taker must be strictly closer to displace a
+ * holder, who goes on from position 1 of its own list), then matchBody's final loop with, under use_ratio, the ratio rule on the
+ * first two entries of the A row's list.  With several matcher threads the reference's result depends on their interleaving where
+ * distances tie; integer distances tie often.
+ * The distances and the per-row lists are computed on the device, one grid for all jobs of the call; the assignment chains are
+ * sequential by nature and O(n_a num_best), and run on the host inside this entry, after the device's lists have come back.
+ * num_best is 1..8; use_ratio needs num_best >= 2 (the rule reads list entry 1). */
+int okvis_fe_match_descriptors(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_match_job* jobs, int32_t desc_bytes,
+                               float threshold, int32_t num_best, int32_t use_ratio, float ratio_threshold);
 
 #ifdef __cplusplus
 }

@@ -3,12 +3,15 @@
 // copy.  No CPU path: every entry fails with OKVIS_BA_ERR_NO_DEVICE / a HIP status when there is no GPU.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <vector>
 
 #include "fe_kernels.hpp"
+#include "fe_match.hpp"
 
 struct okvis_fe_context {
   int device = 0;
@@ -89,6 +92,55 @@ bool spd_inverse6(const double* A, double* inv) {
       inv[6 * i + j] = s;
     }
   return true;
+}
+
+bool desc_bytes_ok(int32_t n) { return n == 16 || n == 32 || n == 48 || n == 64; }
+constexpr int32_t MATCH_MAX_KEYPOINTS = 65536;
+
+template <bool WRITE>
+void launch_hamming_rows(int words, const fe::CandParams& P, hipStream_t stream) {
+  const dim3 grid((P.n_a + fe::MATCH_WAVES - 1) / fe::MATCH_WAVES), block(fe::MATCH_THREADS);
+  switch (words) {
+    case 1: hipLaunchKernelGGL((fe::hamming_rows_kernel<1, WRITE>), grid, block, 0, stream, P); break;
+    case 2: hipLaunchKernelGGL((fe::hamming_rows_kernel<2, WRITE>), grid, block, 0, stream, P); break;
+    case 3: hipLaunchKernelGGL((fe::hamming_rows_kernel<3, WRITE>), grid, block, 0, stream, P); break;
+    default: hipLaunchKernelGGL((fe::hamming_rows_kernel<4, WRITE>), grid, block, 0, stream, P); break;
+  }
+}
+
+void launch_best_lists(int words, int blocks, const fe::BestParams& P, hipStream_t stream) {
+  const dim3 grid(blocks), block(fe::MATCH_THREADS);
+  switch (words) {
+    case 1: hipLaunchKernelGGL(fe::best_lists_kernel<1>, grid, block, 0, stream, P); break;
+    case 2: hipLaunchKernelGGL(fe::best_lists_kernel<2>, grid, block, 0, stream, P); break;
+    case 3: hipLaunchKernelGGL(fe::best_lists_kernel<3>, grid, block, 0, stream, P); break;
+    default: hipLaunchKernelGGL(fe::best_lists_kernel<4>, grid, block, 0, stream, P); break;
+  }
+}
+
+// DenseMatcher::assignbest (okvis_matcher/src/DenseMatcher.cpp:69-111) for row a, its recursion written as a loop: a taker has to
+// be strictly better than the holder, and the holder it displaces goes on from position 1 of its own list
+void assign_best(int a, int num_best, const int32_t* list_idx, const float* list_dist, int32_t* pair_a, float* pair_dist) {
+  int cur = a, start = 0;
+  for (;;) {
+    const int32_t* li = list_idx + (size_t)cur * num_best;
+    const float* ld = list_dist + (size_t)cur * num_best;
+    int displaced = -1;
+    for (int k = start; k < num_best && li[k] != -1; ++k) {
+      const int b = li[k];
+      if (pair_a[b] == -1) {
+        pair_a[b] = cur, pair_dist[b] = ld[k];
+        return;
+      }
+      if (ld[k] < pair_dist[b]) {
+        displaced = pair_a[b];
+        pair_a[b] = cur, pair_dist[b] = ld[k];
+        break;
+      }
+    }
+    if (displaced < 0) return;
+    cur = displaced, start = 1;
+  }
 }
 
 }  // namespace
@@ -239,6 +291,145 @@ int okvis_fe_gate_3d2d(okvis_fe_context* c, int32_t n_proj, const double* uv, co
   FE_TRY(hipStreamSynchronize(c->stream));
   if (chi2) std::memcpy(chi2, c->h_stage + o_chi, sizeof(double) * n_pairs);
   if (flags) std::memcpy(flags, c->h_stage + o_fl, n_pairs);
+  return OKVIS_BA_OK;
+}
+
+int okvis_fe_hamming_candidates(okvis_fe_context* c, int32_t desc_bytes, int32_t n_a, const uint8_t* desc_a, const uint8_t* skip_a,
+                                int32_t n_b, const uint8_t* desc_b, const uint8_t* skip_b, float threshold, int32_t capacity,
+                                int32_t* pairs, float* dist, int32_t* n_pairs) {
+  if (!c || !desc_bytes_ok(desc_bytes) || n_a < 0 || n_b < 0 || n_a > MATCH_MAX_KEYPOINTS || n_b > MATCH_MAX_KEYPOINTS || capacity < 0 ||
+      !n_pairs || (capacity > 0 && !pairs))
+    return OKVIS_BA_ERR_ARG;
+  *n_pairs = 0;
+  if (n_a == 0 || n_b == 0) return OKVIS_BA_OK;
+  if (!desc_a || !desc_b) return OKVIS_BA_ERR_ARG;
+  FE_TRY(hipSetDevice(c->device));
+  const size_t na = (size_t)n_a, nb = (size_t)n_b, cap = (size_t)capacity, db = (size_t)desc_bytes;
+  Layout in, all;
+  const size_t o_da = in.add(db * na), o_db = in.add(db * nb);
+  const size_t o_sa = skip_a ? in.add(na) : 0, o_sb = skip_b ? in.add(nb) : 0;
+  all = in;
+  const size_t o_cnt = all.add(sizeof(int32_t) * na), o_off = all.add(sizeof(unsigned long long) * na);
+  const size_t o_tot = all.add(sizeof(unsigned long long)), o_pairs = all.add(sizeof(int32_t) * 2 * cap), o_dist = all.add(sizeof(float) * cap);
+  if (int rc = reserve(c, all.size)) return rc;
+  std::memcpy(c->h_stage + o_da, desc_a, db * na);
+  std::memcpy(c->h_stage + o_db, desc_b, db * nb);
+  if (skip_a) std::memcpy(c->h_stage + o_sa, skip_a, na);
+  if (skip_b) std::memcpy(c->h_stage + o_sb, skip_b, nb);
+  FE_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, in.size, hipMemcpyHostToDevice, c->stream));
+  fe::CandParams P;
+  P.desc_a = (const uint8_t*)(c->d_stage + o_da), P.desc_b = (const uint8_t*)(c->d_stage + o_db);
+  P.skip_a = skip_a ? (const uint8_t*)(c->d_stage + o_sa) : nullptr, P.skip_b = skip_b ? (const uint8_t*)(c->d_stage + o_sb) : nullptr;
+  P.n_a = n_a, P.n_b = n_b, P.threshold = threshold;
+  P.counts = (int32_t*)(c->d_stage + o_cnt), P.offsets = (const unsigned long long*)(c->d_stage + o_off);
+  P.capacity = capacity, P.pairs = (int32_t*)(c->d_stage + o_pairs), P.dist = (float*)(c->d_stage + o_dist);
+  launch_hamming_rows<false>(desc_bytes / 16, P, c->stream);
+  FE_TRY(hipGetLastError());
+  hipLaunchKernelGGL(fe::row_offsets_kernel, dim3(1), dim3(fe::SCAN_THREADS), 0, c->stream, (const int32_t*)P.counts,
+                     (unsigned long long*)(c->d_stage + o_off), (unsigned long long*)(c->d_stage + o_tot), n_a);
+  FE_TRY(hipGetLastError());
+  if (capacity > 0) {
+    launch_hamming_rows<true>(desc_bytes / 16, P, c->stream);
+    FE_TRY(hipGetLastError());
+  }
+  FE_TRY(hipMemcpyAsync(c->h_stage + o_tot, c->d_stage + o_tot, all.size - o_tot, hipMemcpyDeviceToHost, c->stream));
+  FE_TRY(hipStreamSynchronize(c->stream));
+  unsigned long long total = 0;
+  std::memcpy(&total, c->h_stage + o_tot, sizeof(total));
+  *n_pairs = total > (unsigned long long)INT32_MAX ? INT32_MAX : (int32_t)total;
+  const size_t n = total < cap ? (size_t)total : cap;
+  if (n) std::memcpy(pairs, c->h_stage + o_pairs, sizeof(int32_t) * 2 * n);
+  if (n && dist) std::memcpy(dist, c->h_stage + o_dist, sizeof(float) * n);
+  return OKVIS_BA_OK;
+}
+
+int okvis_fe_match_descriptors(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_match_job* jobs, int32_t desc_bytes, float threshold,
+                               int32_t num_best, int32_t use_ratio, float ratio_threshold) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && !jobs) || !desc_bytes_ok(desc_bytes) || num_best < 1 || num_best > fe::MATCH_MAX_BEST ||
+      (use_ratio && num_best < 2))
+    return OKVIS_BA_ERR_ARG;
+  size_t rows = 0, blocks = 0, n_live = 0;  // n_live: jobs with keypoints on both sides; the others yield nothing
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_match_job& J = jobs[j];
+    if (J.n_a < 0 || J.n_b < 0 || J.n_a > MATCH_MAX_KEYPOINTS || J.n_b > MATCH_MAX_KEYPOINTS) return OKVIS_BA_ERR_ARG;
+    if ((J.n_a > 0 && !J.desc_a) || (J.n_b > 0 && (!J.desc_b || !J.pair_a || !J.pair_dist || !J.accepted))) return OKVIS_BA_ERR_ARG;
+    if (J.n_a > 0 && J.n_b > 0) ++n_live, rows += (size_t)J.n_a, blocks += (size_t)(J.n_a + fe::MATCH_WAVES - 1) / fe::MATCH_WAVES;
+  }
+  if (blocks > (size_t)INT32_MAX || rows > (size_t)INT32_MAX) return OKVIS_BA_ERR_ARG;
+  const size_t db = (size_t)desc_bytes, nbest = (size_t)num_best;
+  Layout in, all;
+  size_t o_lidx = 0, o_ldist = 0;
+  if (rows > 0) {
+    FE_TRY(hipSetDevice(c->device));
+    // every job's descriptors and masks, then the job table
+    struct Offsets {
+      size_t da, db, sa, sb;
+    };
+    std::vector<Offsets> off((size_t)n_jobs);
+    std::vector<fe::MatchJob> table;
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_match_job& J = jobs[j];
+      if (J.n_a == 0 || J.n_b == 0) continue;
+      off[j].da = in.add(db * J.n_a), off[j].db = in.add(db * J.n_b);
+      off[j].sa = J.skip_a ? in.add((size_t)J.n_a) : 0, off[j].sb = J.skip_b ? in.add((size_t)J.n_b) : 0;
+    }
+    const size_t o_table = in.add(sizeof(fe::MatchJob) * n_live);
+    all = in;
+    o_lidx = all.add(sizeof(int32_t) * rows * nbest), o_ldist = all.add(sizeof(float) * rows * nbest);
+    if (int rc = reserve(c, all.size)) return rc;
+    int32_t block0 = 0, row0 = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_match_job& J = jobs[j];
+      if (J.n_a == 0 || J.n_b == 0) continue;
+      std::memcpy(c->h_stage + off[j].da, J.desc_a, db * J.n_a);
+      std::memcpy(c->h_stage + off[j].db, J.desc_b, db * J.n_b);
+      if (J.skip_a) std::memcpy(c->h_stage + off[j].sa, J.skip_a, (size_t)J.n_a);
+      if (J.skip_b) std::memcpy(c->h_stage + off[j].sb, J.skip_b, (size_t)J.n_b);
+      fe::MatchJob D;
+      D.desc_a = (const uint8_t*)(c->d_stage + off[j].da), D.desc_b = (const uint8_t*)(c->d_stage + off[j].db);
+      D.skip_a = J.skip_a ? (const uint8_t*)(c->d_stage + off[j].sa) : nullptr;
+      D.skip_b = J.skip_b ? (const uint8_t*)(c->d_stage + off[j].sb) : nullptr;
+      D.n_a = J.n_a, D.n_b = J.n_b, D.block0 = block0, D.row0 = row0;
+      table.push_back(D);
+      block0 += (J.n_a + fe::MATCH_WAVES - 1) / fe::MATCH_WAVES, row0 += J.n_a;
+    }
+    std::memcpy(c->h_stage + o_table, table.data(), sizeof(fe::MatchJob) * n_live);
+    FE_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, in.size, hipMemcpyHostToDevice, c->stream));
+    fe::BestParams P;
+    P.jobs = (const fe::MatchJob*)(c->d_stage + o_table), P.n_jobs = (int32_t)n_live;
+    P.threshold = threshold, P.initial = use_ratio ? FLT_MAX : threshold, P.num_best = num_best;
+    P.list_idx = (int32_t*)(c->d_stage + o_lidx), P.list_dist = (float*)(c->d_stage + o_ldist);
+    launch_best_lists(desc_bytes / 16, (int)blocks, P, c->stream);
+    FE_TRY(hipGetLastError());
+    FE_TRY(hipMemcpyAsync(c->h_stage + o_lidx, c->d_stage + o_lidx, all.size - o_lidx, hipMemcpyDeviceToHost, c->stream));
+    FE_TRY(hipStreamSynchronize(c->stream));
+  }
+  // the assignment chains (sequential by nature, O(n_a * num_best)) and matchBody's final loop (DenseMatcher.hpp:92-122) on the host
+  size_t row0 = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_match_job& J = jobs[j];
+    for (int b = 0; b < J.n_b; ++b) J.pair_a[b] = -1, J.pair_dist[b] = FLT_MAX, J.accepted[b] = 0;
+    if (J.n_a == 0 || J.n_b == 0) continue;
+    const int32_t* li = (const int32_t*)(c->h_stage + o_lidx) + row0 * nbest;
+    const float* ld = (const float*)(c->h_stage + o_ldist) + row0 * nbest;
+    row0 += (size_t)J.n_a;
+    for (int a = 0; a < J.n_a; ++a)
+      if (!(J.skip_a && J.skip_a[a])) assign_best(a, num_best, li, ld, J.pair_a, J.pair_dist);
+    for (int b = 0; b < J.n_b; ++b) {
+      if (!(J.pair_dist[b] < threshold)) continue;
+      if (use_ratio) {
+        const size_t o = (size_t)J.pair_a[b] * nbest;
+        if (li[o + 1] != -1) {
+          const float best = ld[o], second = ld[o + 1];
+          J.accepted[b] = (best == 0 || second / best > ratio_threshold) ? 1 : 0;
+        } else {
+          J.accepted[b] = 1;
+        }
+      } else {
+        J.accepted[b] = 1;
+      }
+    }
+  }
   return OKVIS_BA_OK;
 }
 

@@ -14,7 +14,9 @@
 //   okvis_fe_project_landmarks   the projection loop of doSetup (:165-213),
 //   okvis_fe_gate_3d2d           the gates of verifyMatch and setBestMatch for every pair within the descriptor threshold,
 //   okvis_fe_stereo_triangulate  stereoTriangulate + getUncertainty for every such pair (ProbabilisticStereoTriangulator.cpp:178-355)
-// and verifyMatch / setBestMatch read their pair's result from a table.  Compiled only where the OKVIS headers exist
+// and verifyMatch / setBestMatch read their pair's result from a table.  The pairs themselves — every (a, b) in play whose
+// descriptors are within the threshold — come from the device too (okvis_fe_hamming_candidates, in the ascending (a, b) order of the
+// host's double loop, which remains for descriptor lengths the device does not take and for deviceCandidates = false).  Compiled only where the OKVIS headers exist
 // (oracle/ref/matcher_runtime.cpp runs it next to the reference's class on the same frames: tests/test_gpu_matcher_binding.py).
 #pragma once
 #if __has_include(<okvis/MatchingAlgorithm.hpp>) && __has_include(<okvis/Estimator.hpp>)
@@ -47,10 +49,11 @@ class BatchedKeyframeWindowMatching : public okvis::MatchingAlgorithm {
   enum MatchingTypes { Match3D2D = 1, Match2D2D = 2 };   // (VioKeyframeWindowMatchingAlgorithm.hpp:74-77)
 
   // descriptorBytes: 48 for BRISK (what specificDescriptorDistance compares, VioKeyframeWindowMatchingAlgorithm.hpp:245-253)
+  // deviceCandidates: the pairs within the descriptor threshold from okvis_fe_hamming_candidates (false: the host's double loop)
   BatchedKeyframeWindowMatching(okvis::Estimator& estimator, int matchingType, float distanceThreshold, bool usePoseUncertainty = true,
-                                int device = 0, int descriptorBytes = 48)
+                                int device = 0, int descriptorBytes = 48, bool deviceCandidates = true)
       : est_(&estimator), type_(matchingType), threshold_(distanceThreshold), usePoseUncertainty_(usePoseUncertainty),
-        descBytes_(descriptorBytes) {
+        descBytes_(descriptorBytes), deviceCandidates_(deviceCandidates) {
     const int rc = okvis_fe_create(&fe_, device);
     if (rc != OKVIS_BA_OK) throw std::runtime_error(std::string("okvis_fe_create: ") + okvis_ba_error_string(rc));
   }
@@ -198,15 +201,46 @@ class BatchedKeyframeWindowMatching : public okvis::MatchingAlgorithm {
     // ---- every pair the matcher can ask about: both keypoints in play, descriptors within the threshold
     pairs_.clear();
     pair_.clear();
-    for (size_t a = 0; a < nA; ++a) {
-      if (skipA_[a]) continue;
-      const unsigned char* da = A_->keypointDescriptor(camA_, a);
+    const bool onDevice = deviceCandidates_ && (descBytes_ == 16 || descBytes_ == 32 || descBytes_ == 48 || descBytes_ == 64) &&
+                          nA <= 65536 && nB <= 65536;
+    if (onDevice) {
+      // the descriptors row by row into contiguous buffers, the masks as bytes; the device returns the pairs in the host loop's order
+      descA_.resize((size_t)descBytes_ * nA);
+      descB_.resize((size_t)descBytes_ * nB);
+      maskA_.resize(nA);
+      maskB_.resize(nB);
+      for (size_t a = 0; a < nA; ++a) {
+        std::memcpy(&descA_[(size_t)descBytes_ * a], A_->keypointDescriptor(camA_, a), (size_t)descBytes_);
+        maskA_[a] = skipA_[a] ? 1 : 0;
+      }
       for (size_t b = 0; b < nB; ++b) {
-        if (skipB_[b]) continue;
-        if ((float)hamming(da, B_->keypointDescriptor(camB_, b)) < threshold_) {
-          pair_[key(a, b)] = (int)(pairs_.size() / 2);
-          pairs_.push_back((int32_t)a);
-          pairs_.push_back((int32_t)b);
+        std::memcpy(&descB_[(size_t)descBytes_ * b], B_->keypointDescriptor(camB_, b), (size_t)descBytes_);
+        maskB_[b] = skipB_[b] ? 1 : 0;
+      }
+      int32_t total = 0;
+      size_t capacity = std::max<size_t>(pairs_.capacity() / 2, 4 * (nA + nB));
+      for (int attempt = 0; attempt < 2; ++attempt) {   // a second call when the first one's buffer was too small
+        pairs_.resize(2 * capacity);
+        check(okvis_fe_hamming_candidates(fe_, descBytes_, (int32_t)nA, descA_.data(), maskA_.data(), (int32_t)nB, descB_.data(), maskB_.data(),
+                                          threshold_, (int32_t)capacity, pairs_.data(), nullptr, &total),
+              "okvis_fe_hamming_candidates");
+        if ((size_t)total <= capacity) break;
+        if (total == std::numeric_limits<int32_t>::max()) throw std::runtime_error("okvis_fe_hamming_candidates: too many pairs");
+        capacity = (size_t)total;
+      }
+      pairs_.resize(2 * (size_t)total);
+      for (int i = 0; i < total; ++i) pair_[key((size_t)pairs_[2 * i], (size_t)pairs_[2 * i + 1])] = i;
+    } else {
+      for (size_t a = 0; a < nA; ++a) {
+        if (skipA_[a]) continue;
+        const unsigned char* da = A_->keypointDescriptor(camA_, a);
+        for (size_t b = 0; b < nB; ++b) {
+          if (skipB_[b]) continue;
+          if ((float)hamming(da, B_->keypointDescriptor(camB_, b)) < threshold_) {
+            pair_[key(a, b)] = (int)(pairs_.size() / 2);
+            pairs_.push_back((int32_t)a);
+            pairs_.push_back((int32_t)b);
+          }
         }
       }
     }
@@ -327,6 +361,8 @@ class BatchedKeyframeWindowMatching : public okvis::MatchingAlgorithm {
   float threshold_;
   bool usePoseUncertainty_;
   int descBytes_;
+  bool deviceCandidates_;
+  std::vector<uint8_t> descA_, descB_, maskA_, maskB_;
   uint64_t idA_ = 0, idB_ = 0;
   size_t camA_ = 0, camB_ = 0;
   std::shared_ptr<okvis::MultiFrame> A_, B_;

@@ -1,5 +1,6 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
-with uncertainty, 3D-2D projection and chi-square gating) on the MI355X.  No CPU path."""
+with uncertainty, 3D-2D projection and chi-square gating) and its descriptor matching (Hamming candidates, the dense matcher's
+best-match search) on the MI355X.  No CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,13 +13,19 @@ TRI_VALID, TRI_NOT_PARALLEL, TRI_CAN_INIT, TRI_RANK_DEFICIENT = 1, 2, 4, 8
 PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = range(5)
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
-           "okvis_fe_gate_3d2d"]
+           "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors"]
 
 
 class CameraC(C.Structure):
     """okvis_fe_camera"""
     _fields_ = [("intr", C.c_double * 12), ("model", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MatchJobC(C.Structure):
+    """okvis_fe_match_job"""
+    _fields_ = [("n_a", C.c_int32), ("n_b", C.c_int32), ("desc_a", C.c_void_p), ("desc_b", C.c_void_p), ("skip_a", C.c_void_p),
+                ("skip_b", C.c_void_p), ("pair_a", C.c_void_p), ("pair_dist", C.c_void_p), ("accepted", C.c_void_p)]
 
 
 def camera(intr, model, width=752, height=480) -> CameraC:
@@ -39,6 +46,26 @@ def _f64(a, shape=None):
     return a if shape is None else a.reshape(shape)
 
 
+def _desc(a):
+    a = np.ascontiguousarray(a, np.uint8)
+    if a.ndim != 2:
+        raise ValueError("descriptors are [n][bytes] uint8")
+    return a
+
+
+def _skip(m, n):
+    if m is None:
+        return None
+    m = np.ascontiguousarray(np.asarray(m).astype(bool), np.uint8)
+    if m.shape != (n,):
+        raise ValueError("a skip mask has one entry per keypoint")
+    return m
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
 def declare(L, prefix="okvis_fe_", with_context=True):
     """signatures of the three batch entries under `prefix` (the reference build exports them as ref_fe_* without a context)"""
     vp = C.c_void_p
@@ -51,6 +78,10 @@ def declare(L, prefix="okvis_fe_", with_context=True):
                                                                        C.c_int32, vp, vp, vp, vp]
     getattr(L, prefix + "project_landmarks").argtypes = ctx + [cam, vp, vp, C.c_int32, vp, vp, vp, vp]
     getattr(L, prefix + "gate_3d2d").argtypes = ctx + [C.c_int32, vp, vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    if with_context:   # the matching entries: the reference build has no such entries
+        i32 = C.c_int32
+        L.okvis_fe_hamming_candidates.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, C.c_float, i32, vp, vp, C.POINTER(i32)]
+        L.okvis_fe_match_descriptors.argtypes = [vp, i32, C.POINTER(MatchJobC), i32, C.c_float, i32, i32, C.c_float]
 
 
 class Frontend:
@@ -132,3 +163,45 @@ class Frontend:
         self._call("gate_3d2d", len(uv), uv.ctypes.data, U.ctypes.data, len(kp_b), kp_b.ctypes.data, n, pairs.ctypes.data,
                    chi2.ctypes.data, flags.ctypes.data)
         return chi2, flags
+
+    def hamming_candidates(self, desc_a, desc_b, threshold, skip_a=None, skip_b=None):
+        """-> pairs [n][2] int32 in ascending (a, b) order, dist [n] float32: the keypoints in play whose descriptors
+        ([n][16 | 32 | 48 | 64] uint8) differ in fewer than `threshold` bits.  Two calls: one counts, one fills."""
+        desc_a, desc_b = _desc(desc_a), _desc(desc_b)
+        if desc_a.shape[1] != desc_b.shape[1]:
+            raise ValueError("descriptors of different lengths")
+        skip_a, skip_b = _skip(skip_a, len(desc_a)), _skip(skip_b, len(desc_b))
+        n = C.c_int32(0)
+        args = (desc_a.shape[1], len(desc_a), desc_a.ctypes.data, _ptr(skip_a), len(desc_b), desc_b.ctypes.data, _ptr(skip_b),
+                float(threshold))
+        self._call("hamming_candidates", *args, 0, None, None, C.byref(n))
+        pairs, dist = np.zeros((n.value, 2), np.int32), np.zeros(n.value, np.float32)
+        if n.value:
+            self._call("hamming_candidates", *args, n.value, pairs.ctypes.data, dist.ctypes.data, C.byref(n))
+            assert n.value == len(pairs)
+        return pairs, dist
+
+    def match_descriptors(self, jobs, threshold, num_best=4, use_ratio=False, ratio_threshold=0.0):
+        """jobs: (desc_a, desc_b) or (desc_a, desc_b, skip_a, skip_b) per image pair.  -> per job (pair_a [n_b] int32, pair_dist
+        [n_b] float32, accepted [n_b] bool): what okvis::DenseMatcher(1, num_best, use_ratio).match leaves in vpairs, and where it
+        calls setBestMatch.  All jobs go through one call."""
+        keep, out = [], []
+        table = (MatchJobC * max(1, len(jobs)))()
+        width = None
+        for j, job in enumerate(jobs):
+            da, db = _desc(job[0]), _desc(job[1])
+            sa = _skip(job[2], len(da)) if len(job) > 2 else None
+            sb = _skip(job[3], len(db)) if len(job) > 3 else None
+            if da.shape[1] != db.shape[1] or width not in (None, da.shape[1]):
+                raise ValueError("descriptors of different lengths")
+            width = da.shape[1]
+            pa, pd, acc = np.zeros(len(db), np.int32), np.zeros(len(db), np.float32), np.zeros(len(db), np.uint8)
+            keep.append((da, db, sa, sb))
+            out.append((pa, pd, acc))
+            t = table[j]
+            t.n_a, t.n_b = len(da), len(db)
+            t.desc_a, t.desc_b, t.skip_a, t.skip_b = da.ctypes.data, db.ctypes.data, _ptr(sa), _ptr(sb)
+            t.pair_a, t.pair_dist, t.accepted = pa.ctypes.data, pd.ctypes.data, acc.ctypes.data
+        self._call("match_descriptors", len(jobs), table, 48 if width is None else width, float(threshold), int(num_best),
+                   int(bool(use_ratio)), float(ratio_threshold))
+        return [(pa, pd, acc.astype(bool)) for pa, pd, acc in out]
