@@ -356,38 +356,12 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   // (the control records follow the records of the windows that are there: n_windows of them, not the capacity)
   s->d_ctrl = reinterpret_cast<CtrlSlot*>(reinterpret_cast<unsigned char*>(s->d_opt) + ctrl_off((size_t)n_windows));
   std::vector<WinPtrs> ptrs(n_windows);
-  BatchMax M;
-  M.group_chunks = M.spec_schur = true;
   for (int i = 0; i < n_windows; ++i) {
     relocate(wins[i].ptrs, s->d_arena, zbase, s->opt.debug_arrays);
     wins[i].ptrs.ctrl = (decltype(wins[i].ptrs.ctrl))(&s->d_ctrl[i].c);   // (not the arena's slot: see CtrlSlot)
     ptrs[i] = wins[i].ptrs;
-    const WinPtrs& P = ptrs[i];
-    M.group = std::max(M.group, P.n_group);
-    M.imu = std::max(M.imu, P.n_imu);
-    M.schur_blocks = std::max(M.schur_blocks, P.n_chunk * (P.n_tile * (P.n_tile + 1) / 2));
-    M.lm = std::max(M.lm, P.n_lm);
-    M.Dp = std::max(M.Dp, P.Dp);
-    M.chunks = std::max(M.chunks, P.n_chunk);
-    if (P.D <= MAX_D_LDS) {
-      M.Dpad_small = std::max(M.Dpad_small, ((P.D + 5) / 6) * 6);
-      if (P.chain) {
-        M.chain = true;
-        M.chain_doubles = std::max(M.chain_doubles, LChain::make(P.D, P.Dp).total);
-      }
-    } else
-      M.Dpad_large = std::max(M.Dpad_large, ((P.D + 5) / 6) * 6);
-    M.any_ext = M.any_ext || P.has_ext;
-    M.group_chunks = M.group_chunks && wins[i].group_chunks;
-    M.spec_schur = M.spec_schur && wins[i].spec_ok;
   }
-  // a batch is fused as a whole or not at all; a batch that is not takes the decision-free Schur launch as a whole or not at all;
-  // otherwise one set of partials for everybody
-  if (M.group_chunks) M.spec_schur = false;
-  if (!M.group_chunks)
-    for (int i = 0; i < n_windows; ++i) ptrs[i].fuse_fast = 0;
-  if (!M.group_chunks && !M.spec_schur)
-    for (int i = 0; i < n_windows; ++i) ptrs[i].spart_buf_stride = 0;
+  const BatchMax M = batch_max(wins.data(), ptrs.data(), n_windows);
   {
     // one copy: option record, window records and the (zeroed) control records behind them
     const size_t wb = sizeof(WinPtrs) * (size_t)n_windows, all = records_bytes((size_t)n_windows);

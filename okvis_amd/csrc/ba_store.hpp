@@ -21,6 +21,50 @@
 
 namespace ba {
 
+// The argument check of a caller's window that the container (WindowStore::assign) and the index build (build_window,
+// capi_index_build.inc) share, made before either reads an index array: counts, null arrays against non-zero counts, and the range
+// of every block index outside the observation list.  The observation list belongs to who walks it (assign / the index build's
+// observation pass), the camera arrays to the caller too (the container wants them with n_cam > 0, the index build with
+// observations), and so does what only the index build requires (structure limits, at least two IMU samples that reach t1, ...).
+inline int check_window_args(const okvis_ba_window& w) {
+  if (w.n_pose < 0 || w.n_sb < 0 || w.n_lm < 0 || w.n_obs < 0 || w.n_imu < 0 || w.n_cam < 0 || w.n_pprior < 0 || w.n_sbprior < 0 ||
+      w.n_relpose < 0 || w.marg_dim < 0)
+    return OKVIS_BA_ERR_ARG;
+  if ((w.n_pose && (!w.pose || !w.pose_fixed)) || (w.n_sb && (!w.sb || !w.sb_fixed)) || (w.n_lm && !w.lm)) return OKVIS_BA_ERR_ARG;
+  if (w.n_imu && (!w.imu_pose0 || !w.imu_sb0 || !w.imu_pose1 || !w.imu_sb1 || !w.imu_t0 || !w.imu_t1 || !w.imu_s_begin ||
+                  !w.imu_s_count || !w.imu_s_t || !w.imu_s_gyr || !w.imu_s_acc))
+    return OKVIS_BA_ERR_ARG;
+  if ((w.n_pprior && (!w.pprior_pose || !w.pprior_meas || !w.pprior_sqrtinfo)) ||
+      (w.n_sbprior && (!w.sbprior_sb || !w.sbprior_meas || !w.sbprior_sqrtinfo)) ||
+      (w.n_relpose && (!w.rel_pose0 || !w.rel_pose1 || !w.rel_sqrtinfo)))
+    return OKVIS_BA_ERR_ARG;
+  if (w.marg_dim && (!w.marg_block_type || !w.marg_block_idx || !w.marg_block_off || !w.marg_J || !w.marg_e0 || !w.marg_lin ||
+                     w.marg_nblocks <= 0))
+    return OKVIS_BA_ERR_ARG;
+  auto in = [](int v, int n) { return v >= 0 && v < n; };
+  for (int f = 0; f < w.n_imu; ++f) {
+    if (!in(w.imu_pose0[f], w.n_pose) || !in(w.imu_pose1[f], w.n_pose) || !in(w.imu_sb0[f], w.n_sb) || !in(w.imu_sb1[f], w.n_sb))
+      return OKVIS_BA_ERR_ARG;
+    const int64_t b = w.imu_s_begin[f], c = w.imu_s_count[f];   // (64-bit: b + c must not wrap)
+    if (b < 0 || c < 0 || b + c > (int64_t)w.n_imu_samples) return OKVIS_BA_ERR_ARG;
+  }
+  for (int i = 0; i < w.n_pprior; ++i)
+    if (!in(w.pprior_pose[i], w.n_pose)) return OKVIS_BA_ERR_ARG;
+  for (int i = 0; i < w.n_sbprior; ++i)
+    if (!in(w.sbprior_sb[i], w.n_sb)) return OKVIS_BA_ERR_ARG;
+  for (int i = 0; i < w.n_relpose; ++i)
+    if (!in(w.rel_pose0[i], w.n_pose) || !in(w.rel_pose1[i], w.n_pose)) return OKVIS_BA_ERR_ARG;
+  for (int b = 0; b < (w.marg_dim > 0 ? w.marg_nblocks : 0); ++b) {
+    const int t = w.marg_block_type[b];
+    if (t != OKVIS_BA_BLOCK_POSE && t != OKVIS_BA_BLOCK_SPEEDBIAS) return OKVIS_BA_ERR_ARG;
+    const bool pose = t == OKVIS_BA_BLOCK_POSE;
+    if (!in(w.marg_block_idx[b], pose ? w.n_pose : w.n_sb) || w.marg_block_off[b] < 0 ||
+        (int64_t)w.marg_block_off[b] + (pose ? 6 : 9) > (int64_t)w.marg_dim)
+      return OKVIS_BA_ERR_ARG;
+  }
+  return OKVIS_BA_OK;
+}
+
 struct WindowStore {
   // parameter blocks
   std::vector<double> pose, sb, lm;
@@ -81,50 +125,15 @@ struct WindowStore {
 
   // deep copy of a caller's window (pointers are only read here)
   int assign(const okvis_ba_window& w) {
-    if (w.n_pose < 0 || w.n_sb < 0 || w.n_lm < 0 || w.n_obs < 0 || w.n_imu < 0 || w.n_cam < 0 || w.n_pprior < 0 || w.n_sbprior < 0 ||
-        w.n_relpose < 0 || w.marg_dim < 0 || w.n_imu_samples < 0)
-      return OKVIS_BA_ERR_ARG;
-    if ((w.n_pose && (!w.pose || !w.pose_fixed)) || (w.n_sb && (!w.sb || !w.sb_fixed)) || (w.n_lm && !w.lm)) return OKVIS_BA_ERR_ARG;
-    if (w.n_obs && (!w.obs_lm || !w.obs_pose || !w.obs_ext || !w.obs_cam || !w.obs_uv || !w.obs_sqrtw)) return OKVIS_BA_ERR_ARG;
-    if (w.n_cam && (!w.cam_intr || !w.cam_model)) return OKVIS_BA_ERR_ARG;
-    if (w.n_imu && (!w.imu_pose0 || !w.imu_sb0 || !w.imu_pose1 || !w.imu_sb1 || !w.imu_t0 || !w.imu_t1 || !w.imu_s_begin ||
-                    !w.imu_s_count || !w.imu_s_t || !w.imu_s_gyr || !w.imu_s_acc))
-      return OKVIS_BA_ERR_ARG;
-    if ((w.n_pprior && (!w.pprior_pose || !w.pprior_meas || !w.pprior_sqrtinfo)) ||
-        (w.n_sbprior && (!w.sbprior_sb || !w.sbprior_meas || !w.sbprior_sqrtinfo)) ||
-        (w.n_relpose && (!w.rel_pose0 || !w.rel_pose1 || !w.rel_sqrtinfo)))
-      return OKVIS_BA_ERR_ARG;
-    if (w.marg_dim && (!w.marg_block_type || !w.marg_block_idx || !w.marg_block_off || !w.marg_J || !w.marg_e0 || !w.marg_lin ||
-                       w.marg_nblocks <= 0))
-      return OKVIS_BA_ERR_ARG;
     // every index array is range-checked before anything is copied: the container is usable without a device, so
     // okvis_ba_upload's validation never sees these windows, and apply() indexes its remap tables with them
+    if (int rc = check_window_args(w)) return rc;
+    if (w.n_imu_samples < 0 || (w.n_cam && (!w.cam_intr || !w.cam_model))) return OKVIS_BA_ERR_ARG;
+    if (w.n_obs && (!w.obs_lm || !w.obs_pose || !w.obs_ext || !w.obs_cam || !w.obs_uv || !w.obs_sqrtw)) return OKVIS_BA_ERR_ARG;
     for (int o = 0; o < w.n_obs; ++o)
       if (w.obs_lm[o] < 0 || w.obs_lm[o] >= w.n_lm || w.obs_pose[o] < 0 || w.obs_pose[o] >= w.n_pose || w.obs_ext[o] < 0 ||
           w.obs_ext[o] >= w.n_pose || w.obs_cam[o] < 0 || w.obs_cam[o] >= w.n_cam)
         return OKVIS_BA_ERR_ARG;
-    for (int f = 0; f < w.n_imu; ++f) {
-      if (w.imu_pose0[f] < 0 || w.imu_pose0[f] >= w.n_pose || w.imu_pose1[f] < 0 || w.imu_pose1[f] >= w.n_pose || w.imu_sb0[f] < 0 ||
-          w.imu_sb0[f] >= w.n_sb || w.imu_sb1[f] < 0 || w.imu_sb1[f] >= w.n_sb)
-        return OKVIS_BA_ERR_ARG;
-      const int64_t b = w.imu_s_begin[f], c = w.imu_s_count[f];   // (64-bit: b + c must not wrap)
-      if (b < 0 || c < 0 || b + c > (int64_t)w.n_imu_samples) return OKVIS_BA_ERR_ARG;
-    }
-    for (int i = 0; i < w.n_pprior; ++i)
-      if (w.pprior_pose[i] < 0 || w.pprior_pose[i] >= w.n_pose) return OKVIS_BA_ERR_ARG;
-    for (int i = 0; i < w.n_sbprior; ++i)
-      if (w.sbprior_sb[i] < 0 || w.sbprior_sb[i] >= w.n_sb) return OKVIS_BA_ERR_ARG;
-    for (int i = 0; i < w.n_relpose; ++i)
-      if (w.rel_pose0[i] < 0 || w.rel_pose0[i] >= w.n_pose || w.rel_pose1[i] < 0 || w.rel_pose1[i] >= w.n_pose) return OKVIS_BA_ERR_ARG;
-    if (w.marg_dim > 0)
-      for (int b = 0; b < w.marg_nblocks; ++b) {
-        const int t = w.marg_block_type[b];
-        if (t != OKVIS_BA_BLOCK_POSE && t != OKVIS_BA_BLOCK_SPEEDBIAS) return OKVIS_BA_ERR_ARG;
-        const int lim = t == OKVIS_BA_BLOCK_POSE ? w.n_pose : w.n_sb, dim = t == OKVIS_BA_BLOCK_POSE ? 6 : 9;
-        if (w.marg_block_idx[b] < 0 || w.marg_block_idx[b] >= lim || w.marg_block_off[b] < 0 ||
-            (int64_t)w.marg_block_off[b] + dim > (int64_t)w.marg_dim)
-          return OKVIS_BA_ERR_ARG;
-      }
     put(pose, w.pose, 7 * (size_t)w.n_pose); put(pose_fixed, w.pose_fixed, (size_t)w.n_pose);
     put(sb, w.sb, 9 * (size_t)w.n_sb); put(sb_fixed, w.sb_fixed, (size_t)w.n_sb);
     put(lm, w.lm, 4 * (size_t)w.n_lm);
@@ -138,11 +147,10 @@ struct WindowStore {
       Imu& m = imu[f];
       m.pose0 = w.imu_pose0[f]; m.sb0 = w.imu_sb0[f]; m.pose1 = w.imu_pose1[f]; m.sb1 = w.imu_sb1[f];
       m.t0 = w.imu_t0[f]; m.t1 = w.imu_t1[f];
-      const int64_t b = w.imu_s_begin[f], c = w.imu_s_count[f];   // (64-bit: b + c must not wrap)
-      if (b < 0 || c < 0 || b + c > (int64_t)w.n_imu_samples) return OKVIS_BA_ERR_ARG;
-      put(m.s_t, w.imu_s_t + b, (size_t)c);
-      put(m.s_gyr, w.imu_s_gyr + 3 * (size_t)b, 3 * (size_t)c);
-      put(m.s_acc, w.imu_s_acc + 3 * (size_t)b, 3 * (size_t)c);
+      const size_t b = (size_t)w.imu_s_begin[f], c = (size_t)w.imu_s_count[f];
+      put(m.s_t, w.imu_s_t + b, c);
+      put(m.s_gyr, w.imu_s_gyr + 3 * b, 3 * c);
+      put(m.s_acc, w.imu_s_acc + 3 * b, 3 * c);
       m.ref_valid = (w.imu_sb_ref && w.imu_sb_ref_valid) ? w.imu_sb_ref_valid[f] : 0;
       if (m.ref_valid > 2 || (m.ref_valid == 2 && !w.imu_cache)) return OKVIS_BA_ERR_ARG;
       for (int k = 0; k < 9; ++k) m.sb_ref[k] = (m.ref_valid && w.imu_sb_ref) ? w.imu_sb_ref[9 * (size_t)f + k] : 0.0;

@@ -1,6 +1,15 @@
 // Part of ba_capi.hip (see capi_solver.inc).  The index build: everything okvis_ba_upload / okvis_ba_patch_window / okvis_ba_check_window
 // derive from a window description on the host — the arrays that replace okvis::ceres::Map's pointer graph (groups, pieces, pairs,
 // chunks, Schur tile lists, IMU / prior assembly lists, the solver layouts) appended to the arena as OFFSETS.
+// build_window is the list of its stages, member functions of one BuildCtx that carries what a stage derives to the ones behind it:
+//   check_window_args (ba_store.hpp, shared with the window container) + check_build_limits: every argument check that is not part
+//     of the observation walk, before anything is read through an index.  So the order of precedence of the status is: a malformed
+//     argument (OKVIS_BA_ERR_ARG), what only the index build requires (limits: OKVIS_BA_ERR_UNSUPPORTED; samples: _ARG), the size
+//     of the reduced system, then the observation walk, where the first offending observation decides, in list order;
+//   ordering, observations (records written in place, pairs), form_groups (with the piece layout), lists_pieces OR lists_staged,
+//   form_chunks, imu_colouring, prior_h0, layout (chain fit, ldl_comp, fuse_fast, sizes);
+//   the arena in its order: put_lists, put_imu_tables, put_zeroed, put_caller_arrays; host_record (sizes, algorithmic bytes).
+// The order of the put / put_n / put_zero calls IS the arena layout.
 namespace {
 
 // ---------------------------------------------------------------------------------------------------
@@ -56,6 +65,21 @@ struct BuildTimes {
   }
 };
 BuildTimes g_build_times;
+// the host time since the previous mark (or the start of the call) goes to the named section
+struct BuildTimer {
+  std::chrono::steady_clock::time_point t0;
+  BuildTimer() {
+    if (!g_build_times.on) return;
+    g_build_times.calls++;
+    t0 = std::chrono::steady_clock::now();
+  }
+  void mark(const char* name) {
+    if (!g_build_times.on) return;
+    const auto t = std::chrono::steady_clock::now();
+    g_build_times.ms[name] += std::chrono::duration<double, std::milli>(t - t0).count();
+    t0 = t;
+  }
+};
 
 constexpr int GROUP_LM_DEFAULT = 32;   // landmarks the index build puts into one linearise group (see build_window) ...
 constexpr int GROUP_LM_FEW = 16, GROUP_LM_FEW_WINDOWS = 8;   // ... and when at most this many windows share the device
@@ -84,6 +108,19 @@ __global__ __launch_bounds__(256) void marg_h0_kernel(const WinPtrs* __restrict_
 
 // Work vectors of build_window, one set per host thread, kept between calls (capacity only: every call assigns what it reads)
 struct BuildScratch {
+  // destination of every entry of the IMU factors' H | g records (BuildCtx::put_imu_tables).  The tables only depend on where the terms'
+  // blocks sit in the reduced system: a window that slides keeps them from frame to frame (9 us of a 70 us upload).  Four
+  // entries, replaced in turn: the estimator alternates between the window it optimises and the sub-window it marginalises.
+  struct ImuAsmCache {
+    int D = -1, Dp = -1, chain = -1;
+    std::vector<int> coloff, color;
+    std::vector<int4> table;
+    std::vector<int> fastw, pos;
+  } asm_caches[4];
+  int asm_next = 0;
+  // block -> observations of the current group (own role), staged path.  Every list is left empty: the lists grow to a few hundred
+  // entries each, once, instead of through ten reallocations per block in every upload
+  std::vector<std::vector<uint16_t>> blk_obs;
   std::vector<int> pose_off, sb_off, role, lm_obs_begin, pair_lm, pair_block, pair_off, pair_role, lm_pair_begin, blocks, seen;
   std::vector<int> chunk_diag_begin, chunk_diag_out, chunk_cross_begin, chunk_cross, chunk_desc, blk_cursor;
   std::vector<int> pair_list_begin, blk_slot, touched, lm_piece_begin, pair_piece, blk_cnt;
@@ -158,54 +195,118 @@ BatchLayout batch_layout(const okvis_ba_options& o, int n_windows) {
   return L;
 }
 
-int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const BatchLayout& lay, Arena& A, HostWin& H) {
-  const bool lin2 = lay.lin2;
-  auto bw_t0 = std::chrono::steady_clock::now();
-  if (g_build_times.on) g_build_times.calls++;
-#define BW_T(name)                                                                                       \
-  do {                                                                                                   \
-    if (g_build_times.on) {                                                                              \
-      const auto t_ = std::chrono::steady_clock::now();                                                  \
-      g_build_times.ms[name] += std::chrono::duration<double, std::milli>(t_ - bw_t0).count();           \
-      bw_t0 = t_;                                                                                        \
-    }                                                                                                    \
-  } while (0)
-  if (w.n_pose < 0 || w.n_sb < 0 || w.n_lm < 0 || w.n_obs < 0 || w.n_imu < 0 || w.n_cam < 0) return OKVIS_BA_ERR_ARG;
-  if ((w.n_pose && (!w.pose || !w.pose_fixed)) || (w.n_sb && (!w.sb || !w.sb_fixed)) || (w.n_lm && !w.lm))
-    return OKVIS_BA_ERR_ARG;
+// What only the index build requires of a window that check_window_args (ba_store.hpp) has passed, and what needs no derived
+// quantity: checked in front of the first use of what it guards
+int check_build_limits(const okvis_ba_window& w) {
   if (w.n_obs && (!w.obs_lm || !w.obs_pose || !w.obs_ext || !w.obs_cam || !w.obs_uv || !w.obs_sqrtw || !w.cam_intr ||
                   !w.cam_model))
     return OKVIS_BA_ERR_ARG;
   if (w.n_pose > 65535 || w.n_lm >= (1 << 24) || w.n_cam > 255) return OKVIS_BA_ERR_UNSUPPORTED;
-  const int npose = w.n_pose, nsb = w.n_sb, nlm = w.n_lm, nobs = w.n_obs;
-  // (the index lists live in one set of vectors per host thread: a frame's upload allocates nothing once they have grown)
-  BuildScratch& S = build_scratch();
-  // ---- reduced ordering: free pose blocks (6 each) then free speed/bias blocks (9 each) ----
-  std::vector<int>&pose_off = S.pose_off, &sb_off = S.sb_off;
-  pose_off.assign(npose, -1);
-  sb_off.assign(nsb, -1);
+  for (int f = 0; f < w.n_imu; ++f) {
+    if (w.imu_s_count[f] < 2) return OKVIS_BA_ERR_ARG;
+    if (w.imu_s_count[f] > MAX_IMU_SAMPLES) return OKVIS_BA_ERR_UNSUPPORTED;
+    // ImuError::redoPreintegration returns -1 when the samples do not cover [t0,t1] (ImuError.cpp:87-89)
+    if (!(w.imu_s_t[w.imu_s_begin[f] + w.imu_s_count[f] - 1] >= w.imu_t1[f])) return OKVIS_BA_ERR_ARG;
+  }
+  if (w.marg_dim > MAX_MARG_DIM) return OKVIS_BA_ERR_UNSUPPORTED;
+  for (int b = 1; b < (w.marg_dim > 0 ? w.marg_nblocks : 0); ++b)
+    if (w.marg_block_off[b] <= w.marg_block_off[b - 1]) return OKVIS_BA_ERR_ARG;
+  if (w.imu_sb_ref && w.imu_sb_ref_valid)
+    for (int f = 0; f < w.n_imu; ++f) {
+      // (the rule of WindowStore::assign: a window a patchable solver refuses is refused here as well)
+      if (w.imu_sb_ref_valid[f] > 2 || (w.imu_sb_ref_valid[f] == 2 && !w.imu_cache)) return OKVIS_BA_ERR_ARG;
+      if (w.imu_sb_ref_valid[f] != 2) continue;
+      ImuCacheD rec;   // the preintegration itself (okvis_ba_fetch_imu_caches): taken as it stands by BuildCtx::put_caller_arrays
+      std::memcpy(&rec, w.imu_cache + (size_t)OKVIS_BA_IMU_CACHE_DOUBLES * f, sizeof(ImuCacheD));
+      if (rec.valid != 1) return OKVIS_BA_ERR_ARG;   // (a record of a term that was never evaluated)
+      for (int k = 0; k < 225; ++k)
+        if (!std::isfinite(rec.sqrt_info[k])) return OKVIS_BA_ERR_ARG;
+      for (int k = 0; k < 4; ++k)
+        if (!std::isfinite(rec.Delta_q[k])) return OKVIS_BA_ERR_ARG;
+    }
+  return OKVIS_BA_OK;
+}
+
+// What the stages of build_window share: the arguments, and what a stage derives for the stages behind it (named with the stage
+// that sets it).  The index lists themselves live in BuildScratch.
+struct BuildCtx {
+  const okvis_ba_window& w;
+  const okvis_ba_options& opt;
+  const BatchLayout& lay;
+  Arena& A;
+  HostWin& H;
+  WinPtrs& P;        // = H.ptrs; the pointer members hold arena OFFSETS until relocate()
+  BuildScratch& S;   // (one set of vectors per host thread: a frame's upload allocates nothing once they have grown)
+  std::vector<int>&pose_off, &sb_off, &lm_obs_begin, &lm_pair_begin, &pair_block;   // (of S: read by most stages)
+  std::vector<Group>& groups;
+  std::vector<Task>& tasks;
+  const bool lin2;
+  const int npose, nsb, nlm, nobs;
+  int D = 0, Dp = 0;                      // ordering
+  int npair = 0;                          // observations
+  bool has_ext = false;
+  int ngroup = 0;                         // form_groups
+  int gpart_size = 0;                     // lists_pieces / lists_staged
+  int nchunk = 0;                         // form_chunks
+  int n_imu_color = 0;                    // imu_colouring
+  std::vector<int> imu_color, imu_order, imu_color_begin, imu_coloff;
+  int Dm = 0, nmb = 0;                    // prior_h0
+  std::vector<double> H0;
+  int ntile = 1, spart_stride = 0;        // layout
+  bool use_chain = false;
+  BuildCtx(const okvis_ba_window& w_, const okvis_ba_options& opt_, const BatchLayout& lay_, Arena& A_, HostWin& H_)
+      : w(w_), opt(opt_), lay(lay_), A(A_), H(H_), P(H_.ptrs), S(build_scratch()), pose_off(S.pose_off), sb_off(S.sb_off),
+        lm_obs_begin(S.lm_obs_begin), lm_pair_begin(S.lm_pair_begin), pair_block(S.pair_block), groups(S.groups), tasks(S.tasks),
+        lin2(lay_.lin2), npose(w_.n_pose), nsb(w_.n_sb), nlm(w_.n_lm), nobs(w_.n_obs) {}
+  // the stages, in the order build_window runs them
+  int ordering();
+  int observations();
+  int form_groups();
+  void lists_reset();
+  void lists_pieces();
+  void lists_staged();
+  void form_chunks();
+  void imu_colouring();
+  void prior_h0();
+  int layout();
+  void put_lists();
+  int put_imu_tables();
+  void put_zeroed();
+  void put_caller_arrays();
+  void host_record();
+};
+
+// ---- reduced ordering: free pose blocks (6 each) then free speed/bias blocks (9 each) ----
+int BuildCtx::ordering() {
+  pose_off.assign(w.n_pose, -1);
+  sb_off.assign(w.n_sb, -1);
   int off = 0;
-  for (int i = 0; i < npose; ++i)
+  for (int i = 0; i < w.n_pose; ++i)
     if (!w.pose_fixed[i]) {
       pose_off[i] = off;
       off += 6;
     }
-  const int Dp = off;
-  for (int i = 0; i < nsb; ++i)
+  Dp = off;
+  for (int i = 0; i < w.n_sb; ++i)
     if (!w.sb_fixed[i]) {
       sb_off[i] = off;
       off += 9;
     }
-  const int D = off;
-  if (D > MAX_D || D == 0) return OKVIS_BA_ERR_UNSUPPORTED;
-  // ---- one pass over the observations, landmark by landmark: validation, roles, observation records and the
-  //      (landmark, free block) pairs ----
+  D = off;
+  return (D > MAX_D || D == 0) ? OKVIS_BA_ERR_UNSUPPORTED : OKVIS_BA_OK;
+}
+
+// ---- one pass over the observations, landmark by landmark: validation, roles, observation records and the
+//      (landmark, free block) pairs ----
+int BuildCtx::observations() {
+  // (locals and local references, here and in form_groups: their loops are the bulk of the build's time)
+  const int npose = w.n_pose, nsb = w.n_sb, nlm = w.n_lm, nobs = w.n_obs;
+  std::vector<int>&pose_off = S.pose_off, &sb_off = S.sb_off;
   std::vector<int>&role = S.role, &lm_obs_begin = S.lm_obs_begin;   // role: 0 pose role, 1 extrinsics role
   role.assign(npose, -1);
   lm_obs_begin.resize((size_t)nlm + 1);
   // The arena's first arrays have sizes known by now, so the observation records are written where they stay (the arena is not
   // touched again before the pass below ends; a failed or unfit window's bytes are discarded by the caller).
-  WinPtrs& P = H.ptrs;
   std::memset(&P, 0, sizeof(P));
   for (int b = 0; b < 2; ++b) {
     OFF(pose[b], put_n(A, w.pose, 7 * (size_t)npose));
@@ -305,9 +406,16 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     if (pairs_over) return OKVIS_BA_ERR_UNSUPPORTED;
   }
   lm_pair_begin[nlm] = npair_run;
-  const int npair = npair_run;
-  BW_T("observations + pairs");
-  // ---- groups ----
+  npair = npair_run;
+  this->has_ext = has_ext;
+  return OKVIS_BA_OK;
+}
+
+// ---- groups, with the piece layout of the piece path ----
+int BuildCtx::form_groups() {
+  const bool lin2 = lay.lin2;
+  const int nlm = w.n_lm, npair = this->npair;
+  std::vector<int>&pose_off = S.pose_off, &lm_obs_begin = S.lm_obs_begin, &lm_pair_begin = S.lm_pair_begin;
   std::vector<Group>& groups = S.groups;
   groups.clear();
   // okvis_ba_tuning::group_work (sweeps): a group also closes when the block products of its landmark elimination, sum of
@@ -398,67 +506,75 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     }
     if (lin2) lm_piece_begin[nlm] = piece_total;
   }
-  const int ngroup = (int)groups.size();
-  BW_T("groups");
-  // ---- per-pair observation lists, per-group tasks ----
-  std::vector<int>& pair_list_begin = S.pair_list_begin;
-  pair_list_begin.assign((size_t)npair + 1, 0);
+  ngroup = (int)groups.size();
+  return OKVIS_BA_OK;
+}
+
+// ---- per-group tasks and their lists: empty lists for both paths to start from ----
+void BuildCtx::lists_reset() {
+  S.pair_list_begin.assign((size_t)npair + 1, 0);
+  S.pair_list.clear(), S.task_list.clear(), S.tasks.clear();
+  S.pair_list.reserve(2 * (size_t)nobs);
+  S.task_list.reserve(3 * (size_t)nobs);
+  S.touched.clear();
+  gpart_size = 0;
+}
+
+// ---- piece path (ba_linearize2.hpp): one task per free block of a group, the slots of its pairs' block records; no
+//      per-observation lists ----
+void BuildCtx::lists_pieces() {
+  lists_reset();
+  std::vector<int>& touched = S.touched;
+  std::vector<uint16_t>& task_list = S.task_list;
+  std::vector<int>& blk_cnt = S.blk_cnt;   // pairs of the current group per block, then the next slot of the block
+  blk_cnt.assign(npose, 0);
+  for (Group& G : S.groups) {
+    G.tlist_begin = (int)task_list.size();
+    // tasks: one per free block seen by the group, ascending; its list = the group-local pairs of that block
+    G.task_begin = (int)tasks.size();
+    touched.clear();
+    for (int p = G.pair_begin; p < G.pair_end; ++p) {
+      const int b = pair_block[p];
+      if (blk_cnt[b]++ == 0) touched.push_back(b);
+    }
+    std::sort(touched.begin(), touched.end());
+    task_list.resize(task_list.size() + (size_t)(G.pair_end - G.pair_begin));
+    int slot = 0;
+    for (int b : touched) {
+      Task T;
+      T.type = 0;
+      T.off_a = pose_off[b];
+      T.off_b = -1;
+      // task_list holds, per group-local pair, the SLOT of its block record: the records of one block are contiguous
+      // [list_begin, list_end) in slot order (pairs ascending), which is the order they are summed in
+      T.list_begin = G.tlist_begin + slot;
+      const int n = blk_cnt[b];
+      blk_cnt[b] = slot;   // from here on: the slot the block's next pair takes
+      slot += n;
+      T.list_end = G.tlist_begin + slot;
+      T.out = gpart_size;
+      gpart_size += 27;
+      tasks.push_back(T);
+    }
+    for (int p = G.pair_begin; p < G.pair_end; ++p) task_list[(size_t)G.tlist_begin + (p - G.pair_begin)] = (uint16_t)blk_cnt[pair_block[p]]++;
+    for (int b : touched) blk_cnt[b] = 0;
+    G.task_end = (int)tasks.size();
+    G.tlist_end = (int)task_list.size();
+  }
+}
+
+// ---- staged path (ba_linearize.hpp): per-pair observation lists; tasks per block (own role), then one per (pose, extrinsics)
+//      pair of free blocks ----
+void BuildCtx::lists_staged() {
+  lists_reset();
+  std::vector<int>&role = S.role, &pair_list_begin = S.pair_list_begin, &touched = S.touched;
   std::vector<uint16_t>&pair_list = S.pair_list, &task_list = S.task_list;
-  std::vector<Task>& tasks = S.tasks;
-  pair_list.clear(), task_list.clear(), tasks.clear();
-  int gpart_size = 0;
-  pair_list.reserve(2 * (size_t)nobs);
-  task_list.reserve(3 * (size_t)nobs);
   std::vector<int>& blk_slot = S.blk_slot;              // scratch: block -> pair of the current landmark / task of the group
   blk_slot.assign(npose, -1);
-  // scratch: block -> observations of the current group (own role).  Kept between calls (every list is left empty): the lists
-  // grow to a few hundred entries each, once, instead of through ten reallocations per block in every upload
-  static thread_local std::vector<std::vector<uint16_t>> blk_obs;
+  std::vector<std::vector<uint16_t>>& blk_obs = S.blk_obs;
   if ((int)blk_obs.size() < npose) blk_obs.resize(npose);
   for (auto& v : blk_obs) v.clear();   // (whatever an interrupted call may have left)
-  std::vector<int>& touched = S.touched;
-  touched.clear();
-  // piece path (ba_linearize2.hpp): pieces instead of per-observation lists
-  if (lin2) {
-    std::vector<int>& blk_cnt = S.blk_cnt;   // pairs of the current group per block, then the next slot of the block
-    blk_cnt.assign(npose, 0);
-    for (int g = 0; g < ngroup; ++g) {
-      Group& G = groups[g];
-      G.tlist_begin = (int)task_list.size();
-      // tasks: one per free block seen by the group, ascending; its list = the group-local pairs of that block
-      G.task_begin = (int)tasks.size();
-      touched.clear();
-      for (int p = G.pair_begin; p < G.pair_end; ++p) {
-        const int b = pair_block[p];
-        if (blk_cnt[b]++ == 0) touched.push_back(b);
-      }
-      std::sort(touched.begin(), touched.end());
-      task_list.resize(task_list.size() + (size_t)(G.pair_end - G.pair_begin));
-      int slot = 0;
-      for (int b : touched) {
-        Task T;
-        T.type = 0;
-        T.off_a = pose_off[b];
-        T.off_b = -1;
-        // task_list holds, per group-local pair, the SLOT of its block record: the records of one block are contiguous
-        // [list_begin, list_end) in slot order (pairs ascending), which is the order they are summed in
-        T.list_begin = G.tlist_begin + slot;
-        const int n = blk_cnt[b];
-        blk_cnt[b] = slot;   // from here on: the slot the block's next pair takes
-        slot += n;
-        T.list_end = G.tlist_begin + slot;
-        T.out = gpart_size;
-        gpart_size += 27;
-        tasks.push_back(T);
-      }
-      for (int p = G.pair_begin; p < G.pair_end; ++p) task_list[(size_t)G.tlist_begin + (p - G.pair_begin)] = (uint16_t)blk_cnt[pair_block[p]]++;
-      for (int b : touched) blk_cnt[b] = 0;
-      G.task_end = (int)tasks.size();
-      G.tlist_end = (int)task_list.size();
-    }
-  }
-  for (int g = 0; g < ngroup && !lin2; ++g) {
-    Group& G = groups[g];
+  for (Group& G : S.groups) {
     G.plist_begin = (int)pair_list.size();
     G.tlist_begin = (int)task_list.size();
     // per-pair observation lists: one pass over a landmark's observations (two-pass counting fill)
@@ -477,7 +593,6 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
         pair_list_begin[p] = run;
         run += c;
       }
-      const size_t base = pair_list.size();
       pair_list.resize((size_t)run);
       std::vector<int>& cur = touched;   // reuse as the per-pair fill cursor
       cur.assign(p1 - p0, 0);
@@ -486,7 +601,6 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
         for (int c = 0; c < 2; ++c)
           if (cand[c] >= 0) pair_list[(size_t)pair_list_begin[cand[c]] + cur[cand[c] - p0]++] = (uint16_t)(o - G.obs_begin);
       }
-      (void)base;
       for (int p = p0; p < p1; ++p) blk_slot[pair_block[p]] = -1;
     }
     G.task_begin = (int)tasks.size();
@@ -534,8 +648,10 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     G.tlist_end = (int)task_list.size();
   }
   pair_list_begin[npair] = (int)pair_list.size();
-  BW_T("lists+tasks");
-  // ---- chunks (Schur workgroups) ----
+}
+
+// ---- chunks (Schur workgroups), their diag / cross lists and descriptors ----
+void BuildCtx::form_chunks() {
   std::vector<Chunk>& chunks = S.chunks;
   chunks.clear();
   {
@@ -558,10 +674,8 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
       C.group_end = g;
       chunks.push_back(C);
     }
-    if (chunks.empty()) {  // no landmarks: one empty chunk is not representable; handled by n_chunk = 0
-    }
-  }
-  const int nchunk = (int)chunks.size();
+  }   // (no landmarks: one empty chunk is not representable; handled by n_chunk = 0)
+  nchunk = (int)chunks.size();
   // ---- per-chunk lists: which per-group partials sum into which pose block / cross block ----
   const int npose_blk_c = Dp / 6;
   std::vector<int>&chunk_diag_begin = S.chunk_diag_begin, &chunk_diag_out = S.chunk_diag_out, &chunk_cross_begin = S.chunk_cross_begin,
@@ -614,10 +728,11 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     d[1] = le;
     for (int i = 0; i <= SCHUR_CHUNK_LM_MAX / 4; ++i) d[2 + i] = lm_pair_begin[std::min(lb + 4 * i, le)];
   }
-  BW_T("chunks");
-  // ---- greedy colouring of the IMU factors: factors of one colour share no parameter block ----
-  std::vector<int> imu_color(w.n_imu, 0);
-  int n_imu_color = 0;
+}
+
+// ---- greedy colouring of the IMU factors: factors of one colour share no parameter block ----
+void BuildCtx::imu_colouring() {
+  imu_color.assign(w.n_imu, 0);
   for (int f = 0; f < w.n_imu; ++f) {
     int col = 0;
     for (;; ++col) {
@@ -634,7 +749,8 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     imu_color[f] = col;
     n_imu_color = std::max(n_imu_color, col + 1);
   }
-  std::vector<int> imu_order, imu_color_begin(n_imu_color + 1, 0), imu_coloff(30 * (size_t)w.n_imu, -1);
+  imu_color_begin.assign(n_imu_color + 1, 0);
+  imu_coloff.assign(30 * (size_t)w.n_imu, -1);
   for (int c = 0; c < n_imu_color; ++c) {
     imu_color_begin[c] = (int)imu_order.size();
     for (int f = 0; f < w.n_imu; ++f)
@@ -647,37 +763,13 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     for (int b = 0; b < 4; ++b)
       for (int k = 0; k < dims[b]; ++k) imu_coloff[30 * (size_t)f + start[b] + k] = offs[b] < 0 ? -1 : offs[b] + k;
   }
-  BW_T("imu colouring");
-  const int npose_blk = Dp / 6;
-  const int spart_stride = npose_blk * (npose_blk + 1) / 2 * 36 + 3 * Dp;
-  const int ntile = std::max(1, (Dp / 6 + SCHUR_TILE_BLOCKS - 1) / SCHUR_TILE_BLOCKS);
-  // ---- IMU ----
-  for (int f = 0; f < w.n_imu; ++f) {
-    if (w.imu_pose0[f] < 0 || w.imu_pose0[f] >= npose || w.imu_pose1[f] < 0 || w.imu_pose1[f] >= npose ||
-        w.imu_sb0[f] < 0 || w.imu_sb0[f] >= nsb || w.imu_sb1[f] < 0 || w.imu_sb1[f] >= nsb)
-      return OKVIS_BA_ERR_ARG;
-    if (w.imu_s_begin[f] < 0 || w.imu_s_count[f] < 2 || w.imu_s_begin[f] + w.imu_s_count[f] > w.n_imu_samples)
-      return OKVIS_BA_ERR_ARG;
-    if (w.imu_s_count[f] > MAX_IMU_SAMPLES) return OKVIS_BA_ERR_UNSUPPORTED;
-    // ImuError::redoPreintegration returns -1 when the samples do not cover [t0,t1] (ImuError.cpp:87-89)
-    if (!(w.imu_s_t[w.imu_s_begin[f] + w.imu_s_count[f] - 1] >= w.imu_t1[f])) return OKVIS_BA_ERR_ARG;
-  }
-  BW_T("imu checks");
-  // ---- marginalisation prior: H0 = J^T J ----
-  const int Dm = w.marg_dim;
-  if (Dm < 0 || Dm > MAX_MARG_DIM) return OKVIS_BA_ERR_UNSUPPORTED;
-  std::vector<double> H0((size_t)Dm * Dm, 0.0);
+}
+
+// ---- marginalisation prior: H0 = J^T J ----
+void BuildCtx::prior_h0() {
+  Dm = w.marg_dim;
+  H0.assign((size_t)Dm * Dm, 0.0);
   if (Dm > 0) {
-    if (!w.marg_J || !w.marg_e0 || !w.marg_lin || !w.marg_block_type || !w.marg_block_idx || !w.marg_block_off ||
-        w.marg_nblocks <= 0)
-      return OKVIS_BA_ERR_ARG;
-    for (int b = 0; b < w.marg_nblocks; ++b) {
-      const int lim = w.marg_block_type[b] == OKVIS_BA_BLOCK_POSE ? npose : nsb;
-      if (w.marg_block_idx[b] < 0 || w.marg_block_idx[b] >= lim || w.marg_block_off[b] < 0 ||
-          w.marg_block_off[b] + (w.marg_block_type[b] == OKVIS_BA_BLOCK_POSE ? 6 : 9) > Dm)
-        return OKVIS_BA_ERR_ARG;
-      if (b > 0 && w.marg_block_off[b] <= w.marg_block_off[b - 1]) return OKVIS_BA_ERR_ARG;
-    }
     // a prior of more than H0_DEVICE_MIN rows: the O(Dm^3) product is left to the device (marg_h0_kernel, launched behind the
     // upload: the same sums in the same order)
     H.h0_on_device = Dm > H0_DEVICE_MIN && !(opt.tuning.flags & OKVIS_BA_TUNE_H0_ON_HOST);   // (the switch: A/B test of the two)
@@ -685,19 +777,23 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     // column-by-column dot products), but the inner loop runs along a row of J (contiguous: 10 us -> 3 us at 45 rows)
     if (!H.h0_on_device) marg_h0_host(w.marg_J, Dm, H0.data());
   }
-  const int nmb = Dm > 0 ? w.marg_nblocks : 0;
+  nmb = Dm > 0 ? w.marg_nblocks : 0;
+}
 
-  // ---- fill sizes ----
+// ---- layout decisions: the sizes of the window record, the chain solver's fit, ldl_comp, fuse_fast ----
+int BuildCtx::layout() {
+  const int npose_blk = Dp / 6;
+  spart_stride = npose_blk * (npose_blk + 1) / 2 * 36 + 3 * Dp;
+  ntile = std::max(1, (Dp / 6 + SCHUR_TILE_BLOCKS - 1) / SCHUR_TILE_BLOCKS);
   P.n_pose = npose; P.n_sb = nsb; P.n_lm = nlm; P.n_cam = w.n_cam; P.n_obs = nobs; P.n_imu = w.n_imu;
   P.n_pprior = w.n_pprior; P.n_sbprior = w.n_sbprior; P.n_rel = w.n_relpose;
   P.marg_dim = Dm; P.marg_nb = nmb;
-  P.D = D; P.Dp = Dp; P.n_pair = npair; P.n_group = ngroup; P.n_chunk = nchunk; P.n_task = (int)tasks.size();
+  P.D = D; P.Dp = Dp; P.n_pair = npair; P.n_group = ngroup; P.n_chunk = nchunk; P.n_task = (int)S.tasks.size();
   P.has_ext = has_ext ? 1 : 0;
   P.lin2 = lin2 ? 1 : 0;
   // ---- chain solver (ba_chain.hpp): the speed/bias blocks must couple only to their neighbours in the order of the reduced
   //      system (an IMU term links consecutive blocks; a marginalisation prior may span two adjacent ones) — what a sliding
   //      window's blocks do, in time order.  Windows solved in HBM (D > MAX_D_LDS) are not concerned.
-  bool use_chain = false;
   if (D <= MAX_D_LDS) {
     const int Ks = (D - Dp) / 9;
     bool fits = Dp >= 6 && Ks >= lay.chain_min && Ks <= CH_MAX_KS && LChain::tiles_fit(Dp) &&
@@ -761,28 +857,31 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
   P.imu.sigma_g_c = w.imu_params.sigma_g_c; P.imu.sigma_a_c = w.imu_params.sigma_a_c;
   P.imu.sigma_gw_c = w.imu_params.sigma_gw_c; P.imu.sigma_aw_c = w.imu_params.sigma_aw_c;
   P.imu.g = w.imu_params.g; P.imu.g_max = w.imu_params.g_max; P.imu.a_max = w.imu_params.a_max;
+  return OKVIS_BA_OK;
+}
 
-  BW_T("prior + sizes");
-  // ---- arena: index lists (the state arrays and the observation records are in place, see above) ----
-  OFF(groups, put(A, groups));
-  OFF(pair_lm, put_n(A, pair_lm.data(), (size_t)npair));
+// ---- arena: index lists (the state arrays and the observation records are in place, see BuildCtx::observations) ----
+void BuildCtx::put_lists() {
+  std::vector<int>& pair_off = S.pair_off;
+  OFF(groups, put(A, S.groups));
+  OFF(pair_lm, put_n(A, S.pair_lm.data(), (size_t)npair));
   OFF(pair_off, put_n(A, pair_off.data(), (size_t)npair));
-  OFF(pair_role, put_n(A, pair_role.data(), (size_t)npair));
-  OFF(pair_list_begin, put(A, pair_list_begin));
-  OFF(pair_list, put(A, pair_list));
+  OFF(pair_role, put_n(A, S.pair_role.data(), (size_t)npair));
+  OFF(pair_list_begin, put(A, S.pair_list_begin));
+  OFF(pair_list, put(A, S.pair_list));
   OFF(lm_pair_begin, put(A, lm_pair_begin));
-  OFF(lm_obs_begin, put(A, lm_obs_begin));
-  OFF(lm_piece_begin, put_n(A, lm_piece_begin.data(), lin2 ? (size_t)nlm + 1 : 0));
-  OFF(pair_piece, put_n(A, pair_piece.data(), lin2 ? (size_t)npair : 0));
-  OFF(pair_block, put_n(A, pair_block.data(), lin2 ? (size_t)npair : 0));
-  OFF(tasks, put(A, tasks));
-  OFF(task_list, put(A, task_list));
-  OFF(chunks, put(A, chunks));
-  OFF(chunk_diag_begin, put(A, chunk_diag_begin));
-  OFF(chunk_diag_out, put(A, chunk_diag_out));
-  OFF(chunk_cross_begin, put(A, chunk_cross_begin));
-  OFF(chunk_cross, put(A, chunk_cross));
-  OFF(chunk_desc, put(A, chunk_desc));
+  OFF(lm_obs_begin, put(A, S.lm_obs_begin));
+  OFF(lm_piece_begin, put_n(A, S.lm_piece_begin.data(), lin2 ? (size_t)nlm + 1 : 0));
+  OFF(pair_piece, put_n(A, S.pair_piece.data(), lin2 ? (size_t)npair : 0));
+  OFF(pair_block, put_n(A, S.pair_block.data(), lin2 ? (size_t)npair : 0));
+  OFF(tasks, put(A, S.tasks));
+  OFF(task_list, put(A, S.task_list));
+  OFF(chunks, put(A, S.chunks));
+  OFF(chunk_diag_begin, put(A, S.chunk_diag_begin));
+  OFF(chunk_diag_out, put(A, S.chunk_diag_out));
+  OFF(chunk_cross_begin, put(A, S.chunk_cross_begin));
+  OFF(chunk_cross, put(A, S.chunk_cross));
+  OFF(chunk_desc, put(A, S.chunk_desc));
   {
     // several Schur tiles per dimension (pose part beyond 96 rows): where the (landmark, block) pairs of every tile start, so that
     // a tile pair's workgroup touches its own pairs only (the pairs of a landmark are sorted by block)
@@ -802,116 +901,113 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
   OFF(imu_order, put(A, imu_order));
   OFF(imu_color_begin, put(A, imu_color_begin));
   OFF(imu_coloff, put(A, imu_coloff));
-  BW_T("arena: arrays");
-  {
-    // destination of every entry of the IMU factors' H (30x30 lower, packed) | g records in the solve kernel's
-    // matrix layout (SLayout, ba_solve.hpp), so that the kernel can prefetch value + destination in one round trip
-    // (the table only depends on where the terms' blocks sit in the reduced system: a window that slides keeps it from frame to
-    // frame, so the last one is kept — 9 us of a 70 us upload)
-    struct ImuAsmCache {
-      int D = -1, Dp = -1, chain = -1;
-      std::vector<int> coloff, color;
-      std::vector<int4> table;
-      std::vector<int> fastw, pos;
+}
+
+// ---- arena: destination of every entry of the IMU factors' H (30x30 lower, packed) | g records in the solve kernel's matrix
+//      layout (SLayout, ba_solve.hpp), so that the kernel can prefetch value + destination in one round trip; kept from call to
+//      call (BuildScratch::ImuAsmCache) ----
+int BuildCtx::put_imu_tables() {
+  typedef BuildScratch::ImuAsmCache ImuAsmCache;
+  ImuAsmCache* const asm_caches = S.asm_caches;
+  int& asm_next = S.asm_next;
+  int hit = -1;
+  for (int k = 0; k < 4 && hit < 0; ++k)
+    if (asm_caches[k].D == D && asm_caches[k].Dp == Dp && asm_caches[k].chain == (int)use_chain && asm_caches[k].coloff == imu_coloff &&
+        asm_caches[k].color == imu_color)
+      hit = k;
+  const bool asm_hit = hit >= 0;
+  ImuAsmCache& asm_cache = asm_caches[asm_hit ? hit : asm_next];
+  if (!asm_hit) asm_next = (asm_next + 1) & 3;
+  std::vector<int4>& imu_asm = asm_cache.table;
+  std::vector<int>& imu_fastw = asm_cache.fastw;
+  std::vector<int>& imu_pos = asm_cache.pos;
+  if (!asm_hit) {
+    asm_cache.D = D;
+    asm_cache.Dp = Dp;
+    asm_cache.chain = (int)use_chain;
+    asm_cache.coloff = imu_coloff;
+    asm_cache.color = imu_color;
+    const int nbk = (D + 5) / 6;   // (the HBM matrix of the large windows has the same block layout)
+    auto at = [&](int i, int j) {
+      const int bi = i / 6, bj = j / 6;
+      return (bj * nbk - (bj * (bj - 1)) / 2 + (bi - bj)) * SBS + (i - 6 * bi) * 6 + (j - 6 * bj);
     };
-    // (four entries, replaced in turn: the estimator alternates between the window it optimises and the sub-window it marginalises)
-    static thread_local ImuAsmCache asm_caches[4];
-    static thread_local int asm_next = 0;
-    int hit = -1;
-    for (int k = 0; k < 4 && hit < 0; ++k)
-      if (asm_caches[k].D == D && asm_caches[k].Dp == Dp && asm_caches[k].chain == (int)use_chain && asm_caches[k].coloff == imu_coloff &&
-          asm_caches[k].color == imu_color)
-        hit = k;
-    const bool asm_hit = hit >= 0;
-    ImuAsmCache& asm_cache = asm_caches[asm_hit ? hit : asm_next];
-    if (!asm_hit) asm_next = (asm_next + 1) & 3;
-    std::vector<int4>& imu_asm = asm_cache.table;
-    std::vector<int>& imu_fastw = asm_cache.fastw;
-    std::vector<int>& imu_pos = asm_cache.pos;
-    if (!asm_hit) {
-      asm_cache.D = D;
-      asm_cache.Dp = Dp;
-      asm_cache.chain = (int)use_chain;
-      asm_cache.coloff = imu_coloff;
-      asm_cache.color = imu_color;
-      const int nbk = (D + 5) / 6;   // (the HBM matrix of the large windows has the same block layout)
-      auto at = [&](int i, int j) {
-        const int bi = i / 6, bj = j / 6;
-        return (bj * nbk - (bj * (bj - 1)) / 2 + (bi - bj)) * SBS + (i - 6 * bi) * 6 + (j - 6 * bj);
-      };
-      // the same entry in the LDS layout of the LDL^T solver (L16::at, ba_ldl16.hpp): i >= j, stored at the mirrored position
-      const L16 ly16{ldl16_nb(D), D - Dp, D};   // (the solver's ordering: speed/bias part first)
-      const LChain lych = LChain::make(D, Dp);  // (chain solver: ba_chain.hpp)
-      auto at16 = [&](int i, int j) { return use_chain ? lych.at(i, j) : ly16.at(i, j); };
-      imu_asm.assign(512 * (size_t)w.n_imu, make_int4(-1, -1, 0, 0));
-      imu_fastw.assign(512 * (size_t)w.n_imu, -1);
-      // (the solve kernel's dynamic LDS: matrix area, then rhs, gradient, diagonal, solution — Dpad doubles each, ba_solve.hpp)
-      const bool lds_system = D <= MAX_D_LDS;
-      const int goff16 = lds_system ? (use_chain ? lych.total : ldl16_area_doubles(D)) + ((D + 5) / 6) * 6 : 0;
-      // Where the entries of a factor's H | g record sit in the record (imu_pos, read by the factor workgroup that writes it): for a
-      // system solved in LDS in the order of their places there, so that the lanes of a wave of the solve kernel — consecutive
-      // record entries — add to ascending, mostly consecutive LDS addresses.  (In the packed order of the triangle the 64 entries
-      // of a wave landed on one bank pair — a row of a 16x16 block lies 128 bytes behind the previous one — and the scatter
-      // took 4 us.)  Windows solved in HBM keep the packed order.
-      imu_pos.assign(512 * (size_t)w.n_imu, 0);
-      std::vector<std::pair<int, int>> keys(495);
-      for (int f = 0; f < w.n_imu; ++f) {
-        const int* co = imu_coloff.data() + 30 * (size_t)f;
-        int e = 0;
-        for (int a = 0; a < 30; ++a)
-          for (int b = 0; b <= a; ++b, ++e) {
-            const int ra = co[a], rb = co[b];
-            keys[e] = {(ra < 0 || rb < 0) ? INT_MAX : (lds_system ? at16(ra, rb) : e), e};
-          }
-        for (int a = 0; a < 30; ++a) keys[465 + a] = {co[a] < 0 ? INT_MAX : (lds_system ? goff16 + co[a] : 465 + a), 465 + a};
-        if (lds_system) std::sort(keys.begin(), keys.end());
-        int* pos = imu_pos.data() + 512 * (size_t)f;
-        for (int rank = 0; rank < 495; ++rank) pos[keys[rank].second] = rank;
-        for (int k = 495; k < 512; ++k) pos[k] = k;
-        e = 0;
-        for (int a = 0; a < 30; ++a)
-          for (int b = 0; b <= a; ++b, ++e) {
-            const int ra = co[a], rb = co[b];
-            if (ra < 0 || rb < 0) continue;
-            const size_t at_rec = 512 * (size_t)f + pos[e];
-            imu_asm[at_rec] = make_int4((ra >= rb ? at(ra, rb) : at(rb, ra)) | (imu_color[f] << 24), a == b ? ra : -1,
-                                        ra >= rb ? (ra << 16 | rb) : (rb << 16 | ra),   // z: the reduced indices
-                                        0);
-            if (lds_system && imu_color[f] < 16) imu_fastw[at_rec] = at16(ra, rb) | ((a == b ? ra + 1 : 0) << 16) | (imu_color[f] << 24);
-          }
-        for (int a = 0; a < 30; ++a)
-          if (co[a] >= 0) {
-            const size_t at_rec = 512 * (size_t)f + pos[465 + a];
-            imu_asm[at_rec] = make_int4(co[a] | (1 << 20) | (imu_color[f] << 24), -1, 0, 0);
-            if (lds_system && imu_color[f] < 16) imu_fastw[at_rec] = (goff16 + co[a]) | (imu_color[f] << 24);
-          }
-      }
+    // the same entry in the LDS layout of the LDL^T solver (L16::at, ba_ldl16.hpp): i >= j, stored at the mirrored position
+    const L16 ly16{ldl16_nb(D), D - Dp, D};   // (the solver's ordering: speed/bias part first)
+    const LChain lych = LChain::make(D, Dp);  // (chain solver: ba_chain.hpp)
+    auto at16 = [&](int i, int j) { return use_chain ? lych.at(i, j) : ly16.at(i, j); };
+    imu_asm.assign(512 * (size_t)w.n_imu, make_int4(-1, -1, 0, 0));
+    imu_fastw.assign(512 * (size_t)w.n_imu, -1);
+    // (the solve kernel's dynamic LDS: matrix area, then rhs, gradient, diagonal, solution — Dpad doubles each, ba_solve.hpp)
+    const bool lds_system = D <= MAX_D_LDS;
+    const int goff16 = lds_system ? (use_chain ? lych.total : ldl16_area_doubles(D)) + ((D + 5) / 6) * 6 : 0;
+    // Where the entries of a factor's H | g record sit in the record (imu_pos, read by the factor workgroup that writes it): for a
+    // system solved in LDS in the order of their places there, so that the lanes of a wave of the solve kernel — consecutive
+    // record entries — add to ascending, mostly consecutive LDS addresses.  (In the packed order of the triangle the 64 entries
+    // of a wave landed on one bank pair — a row of a 16x16 block lies 128 bytes behind the previous one — and the scatter
+    // took 4 us.)  Windows solved in HBM keep the packed order.
+    imu_pos.assign(512 * (size_t)w.n_imu, 0);
+    std::vector<std::pair<int, int>> keys(495);
+    for (int f = 0; f < w.n_imu; ++f) {
+      const int* co = imu_coloff.data() + 30 * (size_t)f;
+      int e = 0;
+      for (int a = 0; a < 30; ++a)
+        for (int b = 0; b <= a; ++b, ++e) {
+          const int ra = co[a], rb = co[b];
+          keys[e] = {(ra < 0 || rb < 0) ? INT_MAX : (lds_system ? at16(ra, rb) : e), e};
+        }
+      for (int a = 0; a < 30; ++a) keys[465 + a] = {co[a] < 0 ? INT_MAX : (lds_system ? goff16 + co[a] : 465 + a), 465 + a};
+      if (lds_system) std::sort(keys.begin(), keys.end());
+      int* pos = imu_pos.data() + 512 * (size_t)f;
+      for (int rank = 0; rank < 495; ++rank) pos[keys[rank].second] = rank;
+      for (int k = 495; k < 512; ++k) pos[k] = k;
+      e = 0;
+      for (int a = 0; a < 30; ++a)
+        for (int b = 0; b <= a; ++b, ++e) {
+          const int ra = co[a], rb = co[b];
+          if (ra < 0 || rb < 0) continue;
+          const size_t at_rec = 512 * (size_t)f + pos[e];
+          imu_asm[at_rec] = make_int4((ra >= rb ? at(ra, rb) : at(rb, ra)) | (imu_color[f] << 24), a == b ? ra : -1,
+                                      ra >= rb ? (ra << 16 | rb) : (rb << 16 | ra),   // z: the reduced indices
+                                      0);
+          if (lds_system && imu_color[f] < 16) imu_fastw[at_rec] = at16(ra, rb) | ((a == b ? ra + 1 : 0) << 16) | (imu_color[f] << 24);
+        }
+      for (int a = 0; a < 30; ++a)
+        if (co[a] >= 0) {
+          const size_t at_rec = 512 * (size_t)f + pos[465 + a];
+          imu_asm[at_rec] = make_int4(co[a] | (1 << 20) | (imu_color[f] << 24), -1, 0, 0);
+          if (lds_system && imu_color[f] < 16) imu_fastw[at_rec] = (goff16 + co[a]) | (imu_color[f] << 24);
+        }
     }
-    if (imu_asm.empty()) OFF(imu_asm, put(A, std::vector<int4>(1, make_int4(-1, -1, 0, 0))));
-    else OFF(imu_asm, put(A, imu_asm));
-    if (imu_fastw.empty()) OFF(imu_fastw, put(A, std::vector<int>(1, -1)));
-    else OFF(imu_fastw, put(A, imu_fastw));
-    if (imu_pos.empty()) OFF(imu_pos, put(A, std::vector<int>(1, 0)));
-    else OFF(imu_pos, put(A, imu_pos));
-    // large windows: the reverse map, so that the tile export (many workgroups) gathers the IMU contributions instead of one
-    // workgroup scattering them into HBM.  At most two factors meet in one entry (the chain couples consecutive states).
-    std::vector<int2> imu_rev;
-    if (D > MAX_D_LDS) {
-      const size_t nbk = (D + 5) / 6;
-      imu_rev.assign(nbk * (nbk + 1) / 2 * SBS, make_int2(-1, -1));
-      for (size_t idx = 0; idx < 512 * (size_t)w.n_imu; ++idx) {
-        const int4 d = imu_asm[idx];
-        if (d.x < 0 || (d.x & (1 << 20))) continue;   // nothing / an entry of g
-        int2& r = imu_rev[d.x & 0xFFFFF];
-        if (r.x < 0) r.x = (int)idx;
-        else if (r.y < 0) r.y = (int)idx;
-        else return OKVIS_BA_ERR_UNSUPPORTED;   // three IMU factors on one block: not a chain
-      }
-    }
-    if (imu_rev.empty()) imu_rev.push_back(make_int2(-1, -1));
-    OFF(imu_rev, put(A, imu_rev));
   }
-  BW_T("arena: imu tables");
+  if (imu_asm.empty()) OFF(imu_asm, put(A, std::vector<int4>(1, make_int4(-1, -1, 0, 0))));
+  else OFF(imu_asm, put(A, imu_asm));
+  if (imu_fastw.empty()) OFF(imu_fastw, put(A, std::vector<int>(1, -1)));
+  else OFF(imu_fastw, put(A, imu_fastw));
+  if (imu_pos.empty()) OFF(imu_pos, put(A, std::vector<int>(1, 0)));
+  else OFF(imu_pos, put(A, imu_pos));
+  // large windows: the reverse map, so that the tile export (many workgroups) gathers the IMU contributions instead of one
+  // workgroup scattering them into HBM.  At most two factors meet in one entry (the chain couples consecutive states).
+  std::vector<int2> imu_rev;
+  if (D > MAX_D_LDS) {
+    const size_t nbk = (D + 5) / 6;
+    imu_rev.assign(nbk * (nbk + 1) / 2 * SBS, make_int2(-1, -1));
+    for (size_t idx = 0; idx < 512 * (size_t)w.n_imu; ++idx) {
+      const int4 d = imu_asm[idx];
+      if (d.x < 0 || (d.x & (1 << 20))) continue;   // nothing / an entry of g
+      int2& r = imu_rev[d.x & 0xFFFFF];
+      if (r.x < 0) r.x = (int)idx;
+      else if (r.y < 0) r.y = (int)idx;
+      else return OKVIS_BA_ERR_UNSUPPORTED;   // three IMU factors on one block: not a chain
+    }
+  }
+  if (imu_rev.empty()) imu_rev.push_back(make_int2(-1, -1));
+  OFF(imu_rev, put(A, imu_rev));
+  return OKVIS_BA_OK;
+}
+
+// ---- arena: the zeroed part (everything the device writes before it reads) ----
+void BuildCtx::put_zeroed() {
   for (int b = 0; b < 2; ++b) {
     OFF(V[b], put_zero(A, 48 * (size_t)nlm));
     OFF(bl[b], put_zero(A, 24 * (size_t)nlm));
@@ -956,9 +1052,13 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
   OFF(lm_scale, put_zero(A, 24 * (size_t)nlm));
   OFF(grad, put_zero(A, 8 * (size_t)D));
   OFF(quality, put_zero(A, 8 * (size_t)nlm));
-  OFF(results, put_zero(A, results_bytes(npose, nsb, nlm, w.n_imu) + 8));
+  OFF(results, put_zero(A, results_bytes(w.n_pose, w.n_sb, nlm, w.n_imu) + 8));
   if (opt.debug_arrays) OFF(prof, put_zero(A, 8 * (64 + 4 * 160)));   // clock64() phase stamps + tile task timeline: diagnostics only
   OFF(ctrl, put_zero(A, sizeof(Ctrl)));
+}
+
+// ---- arena: the caller's arrays (IMU terms with their preintegration records, priors, the marginalisation prior) ----
+void BuildCtx::put_caller_arrays() {
   OFF(imu_pose0, put_n(A, w.imu_pose0, (size_t)w.n_imu));
   OFF(imu_sb0, put_n(A, w.imu_sb0, (size_t)w.n_imu));
   OFF(imu_pose1, put_n(A, w.imu_pose1, (size_t)w.n_imu));
@@ -983,16 +1083,10 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     if (!caches.empty()) std::memset(caches.data(), 0, sizeof(ImuCacheD) * caches.size());
     if (w.imu_sb_ref && w.imu_sb_ref_valid) {
       for (int f = 0; f < w.n_imu; ++f) {
-        // (the rule of WindowStore::assign: a window a patchable solver refuses is refused here as well)
-        if (w.imu_sb_ref_valid[f] > 2 || (w.imu_sb_ref_valid[f] == 2 && !w.imu_cache)) return OKVIS_BA_ERR_ARG;
-        if (w.imu_sb_ref_valid[f] == 2 && w.imu_cache) {
-          // the preintegration itself (okvis_ba_fetch_imu_caches): valid as it stands, nothing is rebuilt on first use
+        if (w.imu_sb_ref_valid[f] == 2) {
+          // the preintegration itself (okvis_ba_fetch_imu_caches, checked by check_build_limits): valid as it stands, nothing is
+          // rebuilt on first use
           std::memcpy(&caches[f], w.imu_cache + (size_t)OKVIS_BA_IMU_CACHE_DOUBLES * f, sizeof(ImuCacheD));
-          if (caches[f].valid != 1) return OKVIS_BA_ERR_ARG;   // (a record of a term that was never evaluated)
-          for (int k = 0; k < 225; ++k)
-            if (!std::isfinite(caches[f].sqrt_info[k])) return OKVIS_BA_ERR_ARG;
-          for (int k = 0; k < 4; ++k)
-            if (!std::isfinite(caches[f].Delta_q[k])) return OKVIS_BA_ERR_ARG;
           caches[f].redo_count = 0;
         } else if (w.imu_sb_ref_valid[f]) {
           caches[f].valid = 2;
@@ -1019,12 +1113,6 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
   OFF(marg_H0, put(A, H0));
   OFF(marg_e0, put_n(A, w.marg_e0, (size_t)Dm));
   OFF(marg_lin, put_n(A, w.marg_lin, 9 * (size_t)nmb));
-  for (int i = 0; i < w.n_pprior; ++i)
-    if (w.pprior_pose[i] < 0 || w.pprior_pose[i] >= npose) return OKVIS_BA_ERR_ARG;
-  for (int i = 0; i < w.n_sbprior; ++i)
-    if (w.sbprior_sb[i] < 0 || w.sbprior_sb[i] >= nsb) return OKVIS_BA_ERR_ARG;
-  for (int i = 0; i < w.n_relpose; ++i)
-    if (w.rel_pose0[i] < 0 || w.rel_pose0[i] >= npose || w.rel_pose1[i] < 0 || w.rel_pose1[i] >= npose) return OKVIS_BA_ERR_ARG;
   {
     // where the columns of the pose / speed-bias priors sit in the reduced system (the solve kernel used to look this up
     // through two dependent loads per column)
@@ -1039,15 +1127,16 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
     }
     OFF(prior_col, put(A, prior_col));
   }
+}
 
+// ---- what the host keeps of the window, and its algorithmic (compulsory) bytes per iteration, DESIGN.md §4 ----
+void BuildCtx::host_record() {
   H.n_pose = npose; H.n_sb = nsb; H.n_lm = nlm; H.n_obs = nobs; H.n_imu = w.n_imu; H.D = D; H.Dp = Dp;
-  H.pose_off = pose_off; H.sb_off = sb_off; H.marg_dim = Dm;
+  H.pose_off = S.pose_off; H.sb_off = S.sb_off; H.marg_dim = Dm;
   H.n_pair = npair; H.n_group = ngroup; H.n_chunk = nchunk;
-  H.pair_lm.assign(pair_lm.data(), pair_lm.data() + npair);
-  H.pair_block.assign(pair_block.data(), pair_block.data() + npair);
+  H.pair_lm.assign(S.pair_lm.data(), S.pair_lm.data() + npair);
+  H.pair_block.assign(S.pair_block.data(), S.pair_block.data() + npair);
   H.acc = 0;
-  BW_T("arena");
-  // ---- algorithmic (compulsory) bytes per iteration, DESIGN.md §4 ----
   const int64_t O = nobs, L = nlm, Pn = npair;
   H.bytes_lin = 32 * O + 56 * (int64_t)npose + 32 * L + 8 * (int64_t)D + 72 * L + 144 * Pn  // reads
                 + 32 * L + 120 * L + 144 * Pn + 8 * (int64_t)gpart_size + 8 * GS_COUNT * (int64_t)ngroup;  // writes
@@ -1056,6 +1145,37 @@ int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const Ba
                   8 * (int64_t)Dm * Dm + 8 * (int64_t)D + 2 * (56 * (int64_t)npose + 72 * (int64_t)nsb);
   H.bytes_small = (int64_t)w.n_imu * (8 * IMU_LIN_STRIDE + (int64_t)sizeof(ImuCacheD) + 2 * 56 + 2 * 72) +
                   8 * (int64_t)Dm * Dm * 2;
+}
+
+int build_window(const okvis_ba_window& w, const okvis_ba_options& opt, const BatchLayout& lay, Arena& A, HostWin& H) {
+  BuildTimer T;   // (the sections OKVIS_BA_DEBUG=build prints)
+  if (int rc = check_window_args(w)) return rc;
+  if (int rc = check_build_limits(w)) return rc;
+  T.mark("imu checks");
+  BuildCtx cx(w, opt, lay, A, H);
+  if (int rc = cx.ordering()) return rc;
+  if (int rc = cx.observations()) return rc;   // (or BW_LIN2_UNFIT: free extrinsics)
+  T.mark("observations + pairs");
+  if (int rc = cx.form_groups()) return rc;   // (BW_LIN2_UNFIT: a landmark with more than LIN2_PIECES pieces)
+  T.mark("groups");
+  if (lay.lin2) cx.lists_pieces();
+  else cx.lists_staged();
+  T.mark("lists+tasks");
+  cx.form_chunks();
+  T.mark("chunks");
+  cx.imu_colouring();
+  T.mark("imu colouring");
+  cx.prior_h0();
+  if (int rc = cx.layout()) return rc;   // (BW_CHAIN_UNFIT)
+  T.mark("prior + sizes");
+  cx.put_lists();
+  T.mark("arena: arrays");
+  if (int rc = cx.put_imu_tables()) return rc;   // (OKVIS_BA_ERR_UNSUPPORTED: three IMU factors on one block of a large window)
+  T.mark("arena: imu tables");
+  cx.put_zeroed();
+  cx.put_caller_arrays();
+  cx.host_record();
+  T.mark("arena");
   return OKVIS_BA_OK;
 }
 
@@ -1073,6 +1193,41 @@ int build_batch(const okvis_ba_window* w, int n, const okvis_ba_options& o, Batc
   }
   L.split_small = L.split_small && L.lin2;
   return OKVIS_BA_OK;
+}
+
+// What the batch's windows ask of make_plan (BatchMax), the other half of what the index build tells it; the records P of a batch
+// that is not fused / not decision-free as a whole lose what only such a batch uses
+BatchMax batch_max(const HostWin* H, WinPtrs* P, int n) {
+  BatchMax M;
+  M.group_chunks = M.spec_schur = true;
+  for (int i = 0; i < n; ++i) {
+    const WinPtrs& Pi = P[i];
+    M.group = std::max(M.group, Pi.n_group);
+    M.imu = std::max(M.imu, Pi.n_imu);
+    M.schur_blocks = std::max(M.schur_blocks, Pi.n_chunk * (Pi.n_tile * (Pi.n_tile + 1) / 2));
+    M.lm = std::max(M.lm, Pi.n_lm);
+    M.Dp = std::max(M.Dp, Pi.Dp);
+    M.chunks = std::max(M.chunks, Pi.n_chunk);
+    if (Pi.D <= MAX_D_LDS) {
+      M.Dpad_small = std::max(M.Dpad_small, ((Pi.D + 5) / 6) * 6);
+      if (Pi.chain) {
+        M.chain = true;
+        M.chain_doubles = std::max(M.chain_doubles, LChain::make(Pi.D, Pi.Dp).total);
+      }
+    } else
+      M.Dpad_large = std::max(M.Dpad_large, ((Pi.D + 5) / 6) * 6);
+    M.any_ext = M.any_ext || Pi.has_ext;
+    M.group_chunks = M.group_chunks && H[i].group_chunks;
+    M.spec_schur = M.spec_schur && H[i].spec_ok;
+  }
+  // a batch is fused as a whole or not at all; a batch that is not takes the decision-free Schur launch as a whole or not at all;
+  // otherwise one set of partials for everybody
+  if (M.group_chunks) M.spec_schur = false;
+  if (!M.group_chunks)
+    for (int i = 0; i < n; ++i) P[i].fuse_fast = 0;
+  if (!M.group_chunks && !M.spec_schur)
+    for (int i = 0; i < n; ++i) P[i].spart_buf_stride = 0;
+  return M;
 }
 
 // convert the arena offsets stored in the pointer fields to device addresses

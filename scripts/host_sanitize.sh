@@ -22,7 +22,7 @@ done
 gcc -c -fPIC $OUT/stub.c -o $OUT/stub.o
 $HIPCC $SAN -shared -fPIC $OUT/ba_capi.o $OUT/store_capi.o $OUT/dist_capi.o $OUT/fe_capi.o $OUT/stub.o -ldl -o $OUT/libokvis_amd_ba.so
 $CLANG $SAN -std=c++17 -fPIC -shared -w $R/okvis_amd/csrc/host/estimator.cpp $R/okvis_amd/csrc/host/estimator_capi.cpp \
-  $R/okvis_amd/csrc/host/replay.cpp -o $OUT/libokvis_amd_estimator.so -L$OUT -lokvis_amd_ba -Wl,-rpath,'$ORIGIN'
+  $R/okvis_amd/csrc/host/replay.cpp $R/okvis_amd/csrc/host/okvis_config.cpp -o $OUT/libokvis_amd_estimator.so -L$OUT -lokvis_amd_ba -Wl,-rpath,'$ORIGIN'
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 cd $R
 OKVIS_AMD_LIB_DIR=$OUT LD_PRELOAD=$RT ASAN_OPTIONS=detect_leaks=0:abort_on_error=0:halt_on_error=1:log_path=$OUT/asan UBSAN_OPTIONS=print_stacktrace=0:log_path=$OUT/ubsan \

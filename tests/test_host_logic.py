@@ -133,6 +133,68 @@ def test_upload_validation_errors():
     assert status(synthetic.make_window(64, 30, 0.5, 2, frame_dt=0.05)) == -3    # D = 960 > 900
 
 
+def test_malformed_windows_are_refused_before_they_are_read():
+    """The argument check the index build (okvis_ba_check_window / okvis_ba_upload) and the window container (okvis_ba_store_*) share
+    (check_window_args, ba_store.hpp) runs before either reads anything through an index: every window below is
+    OKVIS_BA_ERR_ARG (-1) from both.  The index build used to read pose_off / sb_off with the IMU terms' and the pose priors' block
+    indices before it checked them, and took a null array with a non-zero count for an empty one."""
+    import copy
+    L = _lib.lib()
+
+    def both(win, edit=None):
+        wc, keep = win.as_c()
+        if edit is not None:
+            edit(wc)
+        h = C.c_void_p()
+        rs = L.okvis_ba_store_create(C.byref(wc), C.byref(h))
+        if rs == 0:
+            L.okvis_ba_store_destroy(h)
+        return L.okvis_ba_check_window(C.byref(wc), None, None), rs
+
+    w = synthetic.small_window(seed=6)
+    rng = np.random.default_rng(6)
+    w.rel_pose0, w.rel_pose1, w.rel_sqrtinfo = np.array([0], np.int32), np.array([1], np.int32), np.eye(6).reshape(1, 36)
+    w.marg_J, w.marg_e0 = np.triu(rng.standard_normal((15, 15))), rng.standard_normal(15) * 0.1   # a prior over pose 0 and speed/bias 0
+    w.marg_block_type, w.marg_block_idx, w.marg_block_off = (np.array(a, np.int32) for a in ([0, 1], [0, 0], [0, 6]))
+    w.marg_lin = np.zeros((2, 9)); w.marg_lin[0, :7] = w.pose[0]; w.marg_lin[1] = w.sb[0]
+    assert both(w) == (0, 0) and w.n_imu > 0 and len(w.pprior_pose) > 0 and len(w.sbprior_sb) > 0
+
+    def with_entry(name, i, v):
+        bad = copy.deepcopy(w)
+        a = np.array(getattr(bad, name)); a[i] = v; setattr(bad, name, a)
+        return bad
+    # block indices out of range, above and below
+    for name, n in (("imu_pose0", w.n_pose), ("imu_pose1", w.n_pose), ("imu_sb0", w.n_sb), ("imu_sb1", w.n_sb), ("pprior_pose", w.n_pose),
+                    ("sbprior_sb", w.n_sb), ("rel_pose0", w.n_pose), ("rel_pose1", w.n_pose)):
+        for v in (n, 50_000_000, -1, -3):
+            assert both(with_entry(name, 0, v)) == (-1, -1), (name, v)
+    for i, n in ((0, w.n_pose), (1, w.n_sb)):
+        for v in (n, -1):
+            assert both(with_entry("marg_block_idx", i, v)) == (-1, -1), (i, v)
+    assert both(with_entry("marg_block_off", 1, 7)) == (-1, -1)      # the block's columns end behind marg_dim
+    assert both(with_entry("marg_block_type", 1, 7)) == (-1, -1)     # neither OKVIS_BA_BLOCK_POSE nor _SPEEDBIAS
+    # IMU samples outside the sample arrays (64-bit: begin + count does not wrap)
+    assert both(with_entry("imu_s_begin", 0, 2**31 - 1)) == (-1, -1) and both(with_entry("imu_s_begin", 0, -1)) == (-1, -1)
+    # a null array with a non-zero count
+    for field in ("imu_pose0", "imu_sb1", "imu_t0", "imu_s_count", "imu_s_t", "imu_s_gyr", "imu_s_acc", "pprior_pose", "pprior_meas",
+                  "pprior_sqrtinfo", "sbprior_sb", "sbprior_meas", "sbprior_sqrtinfo", "rel_pose0", "rel_pose1", "rel_sqrtinfo",
+                  "marg_J", "marg_e0", "marg_lin", "marg_block_off"):
+        assert both(w, lambda wc: setattr(wc, field, None)) == (-1, -1), field
+    # negative counts
+    for field in ("n_pprior", "n_sbprior", "n_relpose", "n_imu", "marg_dim"):
+        assert both(w, lambda wc: setattr(wc, field, -1)) == (-1, -1), field
+    # two defects: the argument check comes first (capi_index_build.inc), so a malformed argument decides although the observation
+    # walk alone would report a block in both roles (-3, see test_upload_validation_errors)
+    bad = with_entry("obs_ext", -1, w.obs_pose[0])
+    assert both(bad)[0] == -3
+    for name in ("imu_pose0", "pprior_pose"):
+        worse = copy.deepcopy(bad)
+        a = np.array(getattr(worse, name)); a[0] = w.n_pose; setattr(worse, name, a)
+        assert both(worse) == (-1, -1)
+    # ... and what only the index build requires comes behind it: fewer than two samples is its rule, not the container's
+    assert both(with_entry("imu_s_count", 0, 1)) == (-1, 0)
+
+
 def test_window_validate_rejects_bad_input():
     w = synthetic.small_window(seed=7)
     w.obs_lm = w.obs_lm.copy(); w.obs_lm[3] = 10**6
