@@ -18,6 +18,19 @@
  *   okvis_fe_match_descriptors   okvis::DenseMatcher::match with ONE matcher thread, for many image pairs per call
  *                                (okvis_matcher/include/okvis/implementation/DenseMatcher.hpp:47-225, okvis_matcher/src/DenseMatcher.cpp:69-111)
  *
+ * and the arithmetic of the outlier rejection that follows the matching (Frontend::runRansac3d2d / runRansac2d2d,
+ * okvis_frontend/src/Frontend.cpp:575-642, 645-810):
+ *
+ *   okvis_fe_bearing_vectors     what the two RANSAC adapters hold per keypoint: backProject, normalize(), sigmaAngle
+ *                                (okvis_frontend/src/FrameNoncentralAbsoluteAdapter.cpp:51-162, FrameRelativeAdapter.cpp:52-245)
+ *   okvis_fe_sac_consensus       getSelectedDistancesToModel / countWithinDistance / selectWithinDistance of the three sample-consensus
+ *                                problems, for all hypotheses of many problems per call
+ *                                (okvis_frontend/include/opengv/sac_problems/absolute_pose/FrameAbsolutePoseSacProblem.hpp:129-161,
+ *                                 .../relative_pose/FrameRotationOnlySacProblem.hpp:122-144, .../relative_pose/FrameRelativePoseSacProblem.hpp:126-161)
+ *
+ * The minimal solvers (GP3P, five-point, two-point rotation), the sampler and the RANSAC loop are OpenGV's and are not here:
+ * hypotheses come in from the caller.
+ *
  * What stays with the caller is what needs the estimator's book-keeping or image data: which keypoints carry a landmark,
  * addLandmark / addObservation.  G = PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
@@ -131,6 +144,58 @@ typedef struct okvis_fe_match_job { /* one (image A, image B) */
  * num_best is 1..8; use_ratio needs num_best >= 2 (the rule reads list entry 1). */
 int okvis_fe_match_descriptors(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_match_job* jobs, int32_t desc_bytes,
                                float threshold, int32_t num_best, int32_t use_ratio, float ratio_threshold);
+
+/* kp [n][3] float (x, y, size) through cam: bearing [n][3] = backProject(kp) (implementation/PinholeCamera.hpp:426-446 and the
+ * distortion's undistort), normalised; sigma_angle [n] = sqrt(2) (0.8 size / 12)^2 / fu^2 with fu = cam->intr[0]; ok [n] =
+ * backProject's return value (the adapters ignore it).  FrameNoncentralAbsoluteAdapter.cpp:96-149, FrameRelativeAdapter.cpp:168-244.
+ * All four OKVIS_BA_DIST_* models (the reference adapters throw on NoDistortion).  Any output may be NULL; n = 0 is valid. */
+int okvis_fe_bearing_vectors(okvis_fe_context* ctx, const okvis_fe_camera* cam, int32_t n, const float* kp, double* bearing,
+                             double* sigma_angle, uint8_t* ok);
+
+#define OKVIS_FE_SAC_ABSOLUTE 0      /* FrameAbsolutePoseSacProblem: world points against bearing vectors, several cameras       */
+#define OKVIS_FE_SAC_ROTATION_ONLY 1 /* FrameRotationOnlySacProblem: bearing vectors of two frames under a rotation              */
+#define OKVIS_FE_SAC_RELATIVE 2      /* FrameRelativePoseSacProblem: bearing vectors of two frames under a relative pose         */
+
+typedef struct okvis_fe_sac_job { /* one sample-consensus problem with its hypotheses */
+  int32_t kind;     /* OKVIS_FE_SAC_*                                                                           */
+  int32_t n;        /* correspondences, 0..65536                                                                */
+  int32_t n_models; /* hypotheses, 1..1024 (the reference runs at most 50 iterations)                           */
+  int32_t n_cams;   /* absolute: 1..8                                                                           */
+  double threshold; /* the reference uses 9                                                                     */
+  const double* models; /* [n_models][12] row-major 3x4 transformation_t (absolute, relative) or [n_models][9] rotation_t */
+  /* absolute only */
+  const double* points;        /* [n][3]      getPoint                                     */
+  const double* bearing;       /* [n][3]      getBearingVector                             */
+  const double* sigma;         /* [n]         getSigmaAngle                                */
+  const int32_t* cam_index;    /* [n]         0..n_cams-1                                  */
+  const double* cam_offsets;   /* [n_cams][3] getCamOffset: r of T_SC                      */
+  const double* cam_rotations; /* [n_cams][9] getCamRotation: C of T_SC, row-major         */
+  /* rotation only and relative */
+  const double *bearing1, *bearing2; /* [n][3] getBearingVector1 / 2 */
+  const double *sigma1, *sigma2;     /* [n]    getSigmaAngle1 / 2    */
+  /* out, each may be NULL */
+  int32_t* counts;    /* [n_models] countWithinDistance: the number of scores < threshold (strictly)                                 */
+  int32_t* best;      /* the lowest index among the hypotheses with the largest count (the loop replaces its best only on a
+                         strictly larger count)                                                                                       */
+  int32_t* n_inliers; /* counts[best]                                                                                                */
+  int32_t* inliers;   /* [n], the first n_inliers written: selectWithinDistance of hypothesis best, ascending                        */
+  double* scores;     /* [n_models][n] every score; for referees: without it no score leaves the device                               */
+} okvis_fe_sac_job;
+
+/* For every job, the scores of all (hypothesis, correspondence) cells as the reference's getSelectedDistancesToModel computes them,
+ * operation for operation in IEEE double without fused multiply-adds, and what Ransac::computeModel derives from them.
+ *   absolute       the point through the inverse hypothesis into the body frame, minus the camera's offset, through the camera's
+ *                  rotation transposed, normalised; score = |reprojection - bearing|^2 / sigma
+ *   rotation only  score = |R f2 - f1|^2 0.5 / sigma1 + |R^T f1 - f2|^2 0.5 / sigma2
+ *   relative       p = opengv::triangulation::triangulate2 under (R12, t12) = the hypothesis; score = |p/|p| - f1|^2 0.5 / sigma1 +
+ *                  |q/|q| - f2|^2 0.5 / sigma2 with q = the inverse hypothesis applied to p.
+ *                  triangulate2 is OpenGV's, and OpenGV's source is not part of the reference tree: this one function is stated
+ *                  from the published two-view midpoint method (the closest points of the two rays, then their mean) and is NOT
+ *                  pinned to reference lines; everything around it is.
+ * One launch and one copy back per call: the device returns the counts and one 64-bit inlier ballot per (hypothesis, 64
+ * correspondences); best and inliers are read off them on the host.  A cam_index entry outside 0..n_cams-1 is OKVIS_BA_ERR_ARG.
+ * What is not here: the minimal solvers, the sampler, the loop (see INTEGRATION.md for the recipe). */
+int okvis_fe_sac_consensus(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_job* jobs);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,7 @@
 
 #include "fe_kernels.hpp"
 #include "fe_match.hpp"
+#include "fe_sac.hpp"
 
 struct okvis_fe_context {
   int device = 0;
@@ -429,6 +430,162 @@ int okvis_fe_match_descriptors(okvis_fe_context* c, int32_t n_jobs, const okvis_
         J.accepted[b] = 1;
       }
     }
+  }
+  return OKVIS_BA_OK;
+}
+
+int okvis_fe_bearing_vectors(okvis_fe_context* c, const okvis_fe_camera* cam, int32_t n, const float* kp, double* bearing,
+                             double* sigma_angle, uint8_t* ok) {
+  if (!c || !camera_ok(cam) || n < 0) return OKVIS_BA_ERR_ARG;
+  if (n == 0) return OKVIS_BA_OK;
+  if (!kp) return OKVIS_BA_ERR_ARG;
+  fe::BearingParams P;
+  P.cam = to_device(cam), P.n = n;
+  FE_TRY(hipSetDevice(c->device));
+  Layout in, all;
+  const size_t o_kp = in.add(sizeof(float) * 3 * n);
+  all = in;
+  const size_t o_b = all.add(sizeof(double) * 3 * n), o_s = all.add(sizeof(double) * n), o_ok = all.add(n);
+  if (int rc = reserve(c, all.size)) return rc;
+  std::memcpy(c->h_stage + o_kp, kp, sizeof(float) * 3 * n);
+  FE_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, in.size, hipMemcpyHostToDevice, c->stream));
+  P.kp = (const float*)(c->d_stage + o_kp);
+  P.bearing = (double*)(c->d_stage + o_b), P.sigma = (double*)(c->d_stage + o_s), P.ok = (uint8_t*)(c->d_stage + o_ok);
+  hipLaunchKernelGGL(fe::bearing_vectors_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, P);
+  FE_TRY(hipGetLastError());
+  FE_TRY(hipMemcpyAsync(c->h_stage + o_b, c->d_stage + o_b, all.size - o_b, hipMemcpyDeviceToHost, c->stream));
+  FE_TRY(hipStreamSynchronize(c->stream));
+  if (bearing) std::memcpy(bearing, c->h_stage + o_b, sizeof(double) * 3 * n);
+  if (sigma_angle) std::memcpy(sigma_angle, c->h_stage + o_s, sizeof(double) * n);
+  if (ok) std::memcpy(ok, c->h_stage + o_ok, n);
+  return OKVIS_BA_OK;
+}
+
+int okvis_fe_sac_consensus(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_sac_job* jobs) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && !jobs)) return OKVIS_BA_ERR_ARG;
+  size_t blocks = 0, n_live = 0, n_counts = 0, n_words = 0, n_scores = 0;  // n_live: jobs with correspondences
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_job& J = jobs[j];
+    if (J.kind < OKVIS_FE_SAC_ABSOLUTE || J.kind > OKVIS_FE_SAC_RELATIVE || J.n < 0 || J.n > fe::SAC_MAX_N || J.n_models < 1 ||
+        J.n_models > fe::SAC_MAX_MODELS || !J.models)
+      return OKVIS_BA_ERR_ARG;
+    if (J.kind == OKVIS_FE_SAC_ABSOLUTE) {
+      if (J.n_cams < 1 || J.n_cams > fe::SAC_MAX_CAMS) return OKVIS_BA_ERR_ARG;
+      if (J.n > 0 && (!J.points || !J.bearing || !J.sigma || !J.cam_index || !J.cam_offsets || !J.cam_rotations)) return OKVIS_BA_ERR_ARG;
+      for (int i = 0; i < J.n; ++i)
+        if (J.cam_index[i] < 0 || J.cam_index[i] >= J.n_cams) return OKVIS_BA_ERR_ARG;
+    } else if (J.n > 0 && (!J.bearing1 || !J.bearing2 || !J.sigma1 || !J.sigma2)) {
+      return OKVIS_BA_ERR_ARG;
+    }
+    if (J.n == 0) continue;
+    const size_t tiles = ((size_t)J.n + fe::SAC_THREADS - 1) / fe::SAC_THREADS;
+    ++n_live, blocks += tiles * (((size_t)J.n_models + fe::SAC_MODEL_TILE - 1) / fe::SAC_MODEL_TILE);
+    n_counts += (size_t)J.n_models, n_words += (size_t)J.n_models * (((size_t)J.n + 63) / 64);
+    if (J.scores) n_scores += (size_t)J.n_models * (size_t)J.n;
+  }
+  if (blocks > (size_t)INT32_MAX || n_counts > (size_t)INT32_MAX) return OKVIS_BA_ERR_ARG;
+  Layout in, all;
+  size_t o_counts = 0, o_ballots = 0;
+  struct Offsets {
+    size_t models, a, b, s1, s2, ci, cams, scores;
+  };
+  std::vector<Offsets> off((size_t)n_jobs);
+  if (n_live > 0) {
+    FE_TRY(hipSetDevice(c->device));
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_sac_job& J = jobs[j];
+      if (J.n == 0) continue;
+      const size_t n = (size_t)J.n, dbl = sizeof(double);
+      const bool absolute = J.kind == OKVIS_FE_SAC_ABSOLUTE;
+      off[j].models = in.add(dbl * (J.kind == OKVIS_FE_SAC_ROTATION_ONLY ? 9 : 12) * J.n_models);
+      off[j].a = in.add(dbl * 3 * n), off[j].b = in.add(dbl * 3 * n), off[j].s1 = in.add(dbl * n);
+      off[j].s2 = absolute ? 0 : in.add(dbl * n);
+      off[j].ci = absolute ? in.add(sizeof(int32_t) * n) : 0, off[j].cams = absolute ? in.add(dbl * 12 * J.n_cams) : 0;
+    }
+    const size_t o_table = in.add(sizeof(fe::SacJob) * n_live);
+    all = in;
+    o_counts = all.add(sizeof(int32_t) * n_counts), o_ballots = all.add(sizeof(unsigned long long) * n_words);
+    const size_t back = all.size;  // the normal call copies back [o_counts, back): no score matrix
+    for (int j = 0; j < n_jobs; ++j)
+      if (jobs[j].n > 0 && jobs[j].scores) off[j].scores = all.add(sizeof(double) * jobs[j].n_models * (size_t)jobs[j].n);
+    if (int rc = reserve(c, all.size)) return rc;
+    std::vector<fe::SacJob> table;
+    size_t block0 = 0, count0 = 0, word0 = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_sac_job& J = jobs[j];
+      if (J.n == 0) continue;
+      const size_t n = (size_t)J.n;
+      const bool absolute = J.kind == OKVIS_FE_SAC_ABSOLUTE;
+      std::memcpy(c->h_stage + off[j].models, J.models, sizeof(double) * (J.kind == OKVIS_FE_SAC_ROTATION_ONLY ? 9 : 12) * J.n_models);
+      // the [n][3] arrays go to the device as [3][n], so that a wave reads 64 consecutive doubles
+      const double *src_a = absolute ? J.points : J.bearing1, *src_b = absolute ? J.bearing : J.bearing2;
+      double *dst_a = (double*)(c->h_stage + off[j].a), *dst_b = (double*)(c->h_stage + off[j].b);
+      for (size_t i = 0; i < n; ++i)
+        for (int k = 0; k < 3; ++k) dst_a[k * n + i] = src_a[3 * i + k], dst_b[k * n + i] = src_b[3 * i + k];
+      std::memcpy(c->h_stage + off[j].s1, absolute ? J.sigma : J.sigma1, sizeof(double) * n);
+      if (absolute) {
+        std::memcpy(c->h_stage + off[j].ci, J.cam_index, sizeof(int32_t) * n);
+        double* cams = (double*)(c->h_stage + off[j].cams);
+        for (int k = 0; k < J.n_cams; ++k) {
+          std::memcpy(cams + 12 * k, J.cam_offsets + 3 * k, sizeof(double) * 3);
+          std::memcpy(cams + 12 * k + 3, J.cam_rotations + 9 * k, sizeof(double) * 9);
+        }
+      } else {
+        std::memcpy(c->h_stage + off[j].s2, J.sigma2, sizeof(double) * n);
+      }
+      fe::SacJob D;
+      D.models = (const double*)(c->d_stage + off[j].models);
+      D.a = (const double*)(c->d_stage + off[j].a), D.b = (const double*)(c->d_stage + off[j].b);
+      D.sigma1 = (const double*)(c->d_stage + off[j].s1), D.sigma2 = absolute ? nullptr : (const double*)(c->d_stage + off[j].s2);
+      D.cam_index = absolute ? (const int32_t*)(c->d_stage + off[j].ci) : nullptr;
+      D.cams = absolute ? (const double*)(c->d_stage + off[j].cams) : nullptr;
+      D.scores = J.scores ? (double*)(c->d_stage + off[j].scores) : nullptr;
+      D.threshold = J.threshold, D.kind = J.kind, D.n = J.n, D.n_models = J.n_models;
+      D.block0 = (int32_t)block0, D.tiles = (int32_t)((n + fe::SAC_THREADS - 1) / fe::SAC_THREADS);
+      D.count0 = (int32_t)count0, D.word0 = (int64_t)word0;
+      table.push_back(D);
+      block0 += (size_t)D.tiles * (((size_t)J.n_models + fe::SAC_MODEL_TILE - 1) / fe::SAC_MODEL_TILE);
+      count0 += (size_t)J.n_models, word0 += (size_t)J.n_models * ((n + 63) / 64);
+    }
+    std::memcpy(c->h_stage + o_table, table.data(), sizeof(fe::SacJob) * n_live);
+    FE_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, in.size, hipMemcpyHostToDevice, c->stream));
+    FE_TRY(hipMemsetAsync(c->d_stage + o_counts, 0, sizeof(int32_t) * n_counts, c->stream));
+    fe::SacParams P;
+    P.jobs = (const fe::SacJob*)(c->d_stage + o_table), P.n_jobs = (int32_t)n_live;
+    P.counts = (int32_t*)(c->d_stage + o_counts), P.ballots = (unsigned long long*)(c->d_stage + o_ballots);
+    hipLaunchKernelGGL(fe::sac_consensus_kernel, dim3((unsigned)blocks), dim3(fe::SAC_THREADS), 0, c->stream, P);
+    FE_TRY(hipGetLastError());
+    FE_TRY(hipMemcpyAsync(c->h_stage + o_counts, c->d_stage + o_counts, (n_scores ? all.size : back) - o_counts, hipMemcpyDeviceToHost,
+                          c->stream));
+    FE_TRY(hipStreamSynchronize(c->stream));
+  }
+  // Ransac::computeModel's book-keeping on the counts (a hypothesis replaces the best only with strictly more inliers), and the
+  // best hypothesis's row of ballot words expanded into indices
+  size_t count0 = 0, word0 = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_job& J = jobs[j];
+    if (J.n == 0) {
+      if (J.counts) std::memset(J.counts, 0, sizeof(int32_t) * J.n_models);
+      if (J.best) *J.best = 0;
+      if (J.n_inliers) *J.n_inliers = 0;
+      continue;
+    }
+    const size_t words = ((size_t)J.n + 63) / 64;
+    const int32_t* counts = (const int32_t*)(c->h_stage + o_counts) + count0;
+    const unsigned long long* ballots = (const unsigned long long*)(c->h_stage + o_ballots) + word0;
+    count0 += (size_t)J.n_models, word0 += (size_t)J.n_models * words;
+    int best = 0;
+    for (int m = 1; m < J.n_models; ++m)
+      if (counts[m] > counts[best]) best = m;
+    if (J.counts) std::memcpy(J.counts, counts, sizeof(int32_t) * J.n_models);
+    if (J.best) *J.best = best;
+    if (J.n_inliers) *J.n_inliers = counts[best];
+    if (J.inliers) {
+      int32_t k = 0;
+      for (size_t w = 0; w < words; ++w)
+        for (unsigned long long m = ballots[(size_t)best * words + w]; m; m &= m - 1) J.inliers[k++] = (int32_t)(64 * w) + __builtin_ctzll(m);
+    }
+    if (J.scores) std::memcpy(J.scores, c->h_stage + off[j].scores, sizeof(double) * J.n_models * (size_t)J.n);
   }
   return OKVIS_BA_OK;
 }

@@ -13,7 +13,9 @@ TRI_VALID, TRI_NOT_PARALLEL, TRI_CAN_INIT, TRI_RANK_DEFICIENT = 1, 2, 4, 8
 PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = range(5)
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
-           "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors"]
+           "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
+           "okvis_fe_sac_consensus"]
+SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 
 
 class CameraC(C.Structure):
@@ -26,6 +28,15 @@ class MatchJobC(C.Structure):
     """okvis_fe_match_job"""
     _fields_ = [("n_a", C.c_int32), ("n_b", C.c_int32), ("desc_a", C.c_void_p), ("desc_b", C.c_void_p), ("skip_a", C.c_void_p),
                 ("skip_b", C.c_void_p), ("pair_a", C.c_void_p), ("pair_dist", C.c_void_p), ("accepted", C.c_void_p)]
+
+
+class SacJobC(C.Structure):
+    """okvis_fe_sac_job"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("n_models", C.c_int32), ("n_cams", C.c_int32), ("threshold", C.c_double),
+                ("models", C.c_void_p), ("points", C.c_void_p), ("bearing", C.c_void_p), ("sigma", C.c_void_p), ("cam_index", C.c_void_p),
+                ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("bearing1", C.c_void_p), ("bearing2", C.c_void_p),
+                ("sigma1", C.c_void_p), ("sigma2", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("inliers", C.c_void_p), ("scores", C.c_void_p)]
 
 
 def camera(intr, model, width=752, height=480) -> CameraC:
@@ -82,6 +93,8 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         i32 = C.c_int32
         L.okvis_fe_hamming_candidates.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, C.c_float, i32, vp, vp, C.POINTER(i32)]
         L.okvis_fe_match_descriptors.argtypes = [vp, i32, C.POINTER(MatchJobC), i32, C.c_float, i32, i32, C.c_float]
+        L.okvis_fe_bearing_vectors.argtypes = [vp, cam, i32, vp, vp, vp, vp]
+        L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
 
 
 class Frontend:
@@ -205,3 +218,67 @@ class Frontend:
         self._call("match_descriptors", len(jobs), table, 48 if width is None else width, float(threshold), int(num_best),
                    int(bool(use_ratio)), float(ratio_threshold))
         return [(pa, pd, acc.astype(bool)) for pa, pd, acc in out]
+
+    def bearing_vectors(self, cam: CameraC, kp):
+        """kp [n][3] (x, y, size) -> bearing [n][3] unit vectors, sigma_angle [n], ok [n] bool: what the two RANSAC adapters hold
+        per keypoint"""
+        kp = _f32(kp, 3)
+        n = len(kp)
+        bearing, sigma, ok = np.zeros((n, 3)), np.zeros(n), np.zeros(n, np.uint8)
+        self._call("bearing_vectors", C.byref(cam), n, kp.ctypes.data, bearing.ctypes.data, sigma.ctypes.data, ok.ctypes.data)
+        return bearing, sigma, ok.astype(bool)
+
+    def sac_consensus(self, jobs, want_scores=False):
+        """jobs: dicts with kind (SAC_*), models [K][3][4] (or [K][3][3] for SAC_ROTATION_ONLY), threshold (default 9) and
+        SAC_ABSOLUTE: points, bearing [n][3], sigma [n], cam_index [n], cam_offsets [c][3], cam_rotations [c][3][3];
+        the other kinds: bearing1, bearing2 [n][3], sigma1, sigma2 [n].
+        -> per job a dict: counts [K] int32, best, n_inliers, inliers [n_inliers] int32 (ascending), and scores [K][n] under
+        want_scores.  All jobs go through one call."""
+        table, keep, out = sac_job_table(jobs, want_scores)
+        self._call("sac_consensus", len(jobs), table)
+        res = []
+        for counts, scalars, inl, sc in out:
+            r = {"counts": counts, "best": int(scalars[0]), "n_inliers": int(scalars[1]), "inliers": inl[:int(scalars[1])].copy()}
+            if want_scores:
+                r["scores"] = sc
+            res.append(r)
+        return res
+
+
+def sac_job_table(jobs, want_scores=False):
+    """-> (okvis_fe_sac_job array, the input arrays it points into, per job the output arrays (counts, [best, n_inliers], inliers,
+    scores)); both lists have to outlive the call"""
+    keep, out = [], []
+    table = (SacJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        kind = int(job["kind"])
+        if kind not in (SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE):
+            raise ValueError("kind is one of SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE")
+        models = _f64(job["models"]).reshape(-1, 9 if kind == SAC_ROTATION_ONLY else 12)
+        t = table[j]
+        t.kind, t.n_models, t.threshold, t.models = kind, len(models), float(job.get("threshold", 9.0)), models.ctypes.data
+        if kind == SAC_ABSOLUTE:
+            a, b = _f64(job["points"]).reshape(-1, 3), _f64(job["bearing"]).reshape(-1, 3)
+            s1, ci = _f64(job["sigma"]).reshape(-1), np.ascontiguousarray(job["cam_index"], np.int32).reshape(-1)
+            off, rot = _f64(job["cam_offsets"]).reshape(-1, 3), _f64(job["cam_rotations"]).reshape(-1, 9)
+            if not (len(a) == len(b) == len(s1) == len(ci)) or len(off) != len(rot):
+                raise ValueError("arrays of different lengths")
+            t.n, t.n_cams = len(a), len(off)
+            t.points, t.bearing, t.sigma, t.cam_index = a.ctypes.data, b.ctypes.data, s1.ctypes.data, ci.ctypes.data
+            t.cam_offsets, t.cam_rotations = off.ctypes.data, rot.ctypes.data
+            keep.append((models, a, b, s1, ci, off, rot))
+        else:
+            a, b = _f64(job["bearing1"]).reshape(-1, 3), _f64(job["bearing2"]).reshape(-1, 3)
+            s1, s2 = _f64(job["sigma1"]).reshape(-1), _f64(job["sigma2"]).reshape(-1)
+            if not (len(a) == len(b) == len(s1) == len(s2)):
+                raise ValueError("arrays of different lengths")
+            t.n = len(a)
+            t.bearing1, t.bearing2, t.sigma1, t.sigma2 = a.ctypes.data, b.ctypes.data, s1.ctypes.data, s2.ctypes.data
+            keep.append((models, a, b, s1, s2))
+        n, K = t.n, len(models)
+        counts, scalars, inl = np.zeros(K, np.int32), np.zeros(2, np.int32), np.zeros(max(n, 1), np.int32)
+        sc = np.zeros((K, n)) if want_scores else None
+        t.counts, t.best, t.n_inliers, t.inliers = counts.ctypes.data, scalars.ctypes.data, scalars.ctypes.data + 4, inl.ctypes.data
+        t.scores = _ptr(sc)
+        out.append((counts, scalars, inl, sc))
+    return table, keep, out
