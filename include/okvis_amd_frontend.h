@@ -17,6 +17,10 @@
  *                                (the double loop a matching algorithm's doSetup would run on the host)
  *   okvis_fe_match_descriptors   okvis::DenseMatcher::match with ONE matcher thread, for many image pairs per call
  *                                (okvis_matcher/include/okvis/implementation/DenseMatcher.hpp:47-225, okvis_matcher/src/DenseMatcher.cpp:69-111)
+ *   okvis_fe_match_verified      the same matcher under the distance the frontend really uses, "Hamming distance under the threshold
+ *                                and verifyMatch(a, b)": whole 3D-2D and 2D-2D matching steps, projection, gating / triangulation and
+ *                                the accepted pairs' setBestMatch quantities included, many steps per call
+ *                                (okvis_frontend/src/VioKeyframeWindowMatchingAlgorithm.cpp:165-213, 307-337, 377-394, 485-508)
  *
  * and the arithmetic of the outlier rejection that follows the matching (Frontend::runRansac3d2d / runRansac2d2d,
  * okvis_frontend/src/Frontend.cpp:575-642, 645-810):
@@ -144,6 +148,59 @@ typedef struct okvis_fe_match_job { /* one (image A, image B) */
  * num_best is 1..8; use_ratio needs num_best >= 2 (the rule reads list entry 1). */
 int okvis_fe_match_descriptors(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_match_job* jobs, int32_t desc_bytes,
                                float threshold, int32_t num_best, int32_t use_ratio, float ratio_threshold);
+
+#define OKVIS_FE_MATCH_3D2D 1 /* VioKeyframeWindowMatchingAlgorithm::Match3D2D */
+#define OKVIS_FE_MATCH_2D2D 2 /* ... ::Match2D2D */
+
+typedef struct okvis_fe_vmatch_job { /* one matching step: (frame A, camera) against (frame B, camera) */
+  int32_t kind;                      /* OKVIS_FE_MATCH_* */
+  int32_t n_a, n_b;                  /* 0..65536 each; 0 is valid */
+  const uint8_t *desc_a, *desc_b;    /* [n][desc_bytes] */
+  const uint8_t *skip_a, *skip_b;    /* skipA / skipB as the host's doSetup book-keeping decided them; NULL = none */
+  const float *kp_a, *kp_b;          /* [n][3] x, y, size (kp_a may be NULL for 3D2D) */
+  okvis_fe_camera cam_a, cam_b;
+  /* 3D2D: doSetup's projection loop (:165-213) runs inside the call */
+  const double* hp_W; /* [n_a][4]; rows with skip_a set are not read */
+  double T_CbW[7], P3[9];
+  /* 2D2D */
+  double T_AB[7], UOplus[36];
+  /* out; every pointer may be NULL except pair_a / pair_dist / accepted when n_b > 0 */
+  int32_t* pair_a;      /* [n_b], as okvis_fe_match_job */
+  float* pair_dist;
+  uint8_t* accepted;
+  uint8_t* proj_status; /* 3D2D, [n_a]: what okvis_fe_project_landmarks returns for the rows in play, zeros for rows with skip_a set */
+  double *uv, *U;       /*       [n_a][2], [n_a][4] */
+  double* chi2;         /* 3D2D, [n_b]: okvis_fe_gate_3d2d of (pair_a[b], b) where accepted, zero elsewhere */
+  uint8_t* gate_flags;
+  double *hp_a, *cov;   /* 2D2D, [n_b][4], [n_b][9]: okvis_fe_stereo_triangulate(want_uncertainty = 1, sigma_ray = the pair's ray
+                           sigma) of (pair_a[b], b) where accepted, zero elsewhere */
+  uint8_t* tri_flags;
+} okvis_fe_vmatch_job;
+
+/* Whole matching steps of the frontend: matcher_->match<VioKeyframeWindowMatchingAlgorithm<G>>(alg) for every job.  The semantics
+ * are those of okvis_fe_match_descriptors (ONE matcher thread, the same list and tie rules, assignbest and matchBody's final loop on
+ * the host inside this entry, num_best 1..8, the ratio rule needs num_best >= 2) under the distance the reference's algorithm defines
+ * (VioKeyframeWindowMatchingAlgorithm.hpp, distance): the Hamming distance d if d < threshold AND verifyMatch(a, b), FLT_MAX otherwise.
+ *   2D2D  verifyMatch = stereoTriangulate(a, b, ., ., sigma) returns valid (OKVIS_FE_TRI_VALID of the 5-argument path,
+ *         ProbabilisticStereoTriangulator.cpp:178-236) with sigma = max(raySigmaA[a], raySigmaB[b]) and
+ *         raySigma[k] = sqrt(sqrt(2)) * (0.8 * size_k / 12) / fu in double, in this operation order (:210-221, :251-261).
+ *   3D2D  a row a is in play only if skip_a[a] is clear and its projection is OKVIS_FE_PROJ_SUCCESSFUL (:186-192); verifyMatch =
+ *         OKVIS_FE_GATE_VERIFIED of the gate on uv[a], U[a], kp_b[b]: (int)chi2 < 4 (:318-337).  proj_status lets the caller apply
+ *         doSetup's side effect setLandmarkInitialized(id, false) for rows with fewer than two observations (:194-198); the caller
+ *         knows those rows beforehand and also sets them in skip_a.
+ * For every b with accepted[b] the outputs carry what setBestMatch computes again for that pair (:377-394, :485-508), so that the
+ * caller goes on with addLandmark / addObservation / setLandmark without another call.
+ * Jobs of one call are INDEPENDENT of each other: the caller batches only steps whose skip masks do not depend on each other's
+ * result — the two cameras of matchToKeyframes against one keyframe, the same step of several sequences.  Kinds may be mixed.
+ * The per-keypoint work, the distances, the verification and the per-row lists run on the device (two launches for all jobs of the
+ * call); the uncertainty of the accepted 2D2D pairs (at most n_b per job) is one more launch per such job, after the host's chains.
+ * OKVIS_BA_ERR_ARG before the context is read or the device is touched: NULL context, desc_bytes outside {16, 32, 48, 64}, sizes
+ * outside 0..65536, num_best outside 1..8, use_ratio with num_best < 2, kind outside {1, 2}, a camera with a non-positive focal
+ * length or image size or an unknown model, a NULL required pointer (kp_b always, kp_a for 2D2D, hp_W for 3D2D with n_a > 0, the
+ * descriptors, pair_a / pair_dist / accepted with n_b > 0), UOplus not positive definite for 2D2D when hp_a, cov or tri_flags is
+ * wanted. */
+int okvis_fe_match_verified(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_vmatch_job* jobs, int32_t desc_bytes,
+                            float threshold, int32_t num_best, int32_t use_ratio, float ratio_threshold);
 
 /* kp [n][3] float (x, y, size) through cam: bearing [n][3] = backProject(kp) (implementation/PinholeCamera.hpp:426-446 and the
  * distortion's undistort), normalised; sigma_angle [n] = sqrt(2) (0.8 size / 12)^2 / fu^2 with fu = cam->intr[0]; ok [n] =

@@ -3,6 +3,7 @@
 // copy.  No CPU path: every entry fails with OKVIS_BA_ERR_NO_DEVICE / a HIP status when there is no GPU.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
 #include <cstdlib>
@@ -13,6 +14,7 @@
 #include "fe_kernels.hpp"
 #include "fe_match.hpp"
 #include "fe_sac.hpp"
+#include "fe_vmatch.hpp"
 
 struct okvis_fe_context {
   int device = 0;
@@ -117,6 +119,23 @@ void launch_best_lists(int words, int blocks, const fe::BestParams& P, hipStream
     case 3: hipLaunchKernelGGL(fe::best_lists_kernel<3>, grid, block, 0, stream, P); break;
     default: hipLaunchKernelGGL(fe::best_lists_kernel<4>, grid, block, 0, stream, P); break;
   }
+}
+
+void launch_verified_lists(int words, int blocks, const fe::VListParams& P, hipStream_t stream) {
+  const dim3 grid(blocks), block(fe::MATCH_THREADS);
+  switch (words) {
+    case 1: hipLaunchKernelGGL(fe::verified_lists_kernel<1>, grid, block, 0, stream, P); break;
+    case 2: hipLaunchKernelGGL(fe::verified_lists_kernel<2>, grid, block, 0, stream, P); break;
+    case 3: hipLaunchKernelGGL(fe::verified_lists_kernel<3>, grid, block, 0, stream, P); break;
+    default: hipLaunchKernelGGL(fe::verified_lists_kernel<4>, grid, block, 0, stream, P); break;
+  }
+}
+
+// raySigmasA_ / raySigmasB_ of doSetup (VioKeyframeWindowMatchingAlgorithm.cpp:210-221, :251-261) in the reference's operation
+// order; products and quotients only, so the host and any IEEE device give the same bits
+double ray_sigma(float size, double fu) {
+  const double sd = 0.8 * (double)size / 12.0;
+  return std::sqrt(std::sqrt(2.0)) * sd / fu;
 }
 
 // DenseMatcher::assignbest (okvis_matcher/src/DenseMatcher.cpp:69-111) for row a, its recursion written as a loop: a taker has to
@@ -428,6 +447,237 @@ int okvis_fe_match_descriptors(okvis_fe_context* c, int32_t n_jobs, const okvis_
         }
       } else {
         J.accepted[b] = 1;
+      }
+    }
+  }
+  return OKVIS_BA_OK;
+}
+
+int okvis_fe_match_verified(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_vmatch_job* jobs, int32_t desc_bytes, float threshold,
+                            int32_t num_best, int32_t use_ratio, float ratio_threshold) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && !jobs) || !desc_bytes_ok(desc_bytes) || num_best < 1 || num_best > fe::MATCH_MAX_BEST ||
+      (use_ratio && num_best < 2))
+    return OKVIS_BA_ERR_ARG;
+  // per job: live = keypoints on both sides (lists are built); pre = the per-keypoint pass has something to do (a 3D2D step
+  // reports its projections even against an empty image B); tri = the accepted pairs' uncertainty is wanted
+  struct Plan {
+    bool live, pre, tri;
+    size_t da, db, sa, sb, ka, kb, hp, sga, sgb, ra, rb, uv, U, st;  // offsets, phase one
+    size_t t_pairs, t_sig, t_hp, t_cov, t_fl;                         // offsets, the uncertainty launch
+    double info6[36];
+  };
+  std::vector<Plan> plan((size_t)n_jobs);
+  size_t rows = 0, blocks = 0, pre_blocks = 0, n_work = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_vmatch_job& J = jobs[j];
+    Plan& p = plan[j];
+    const bool is2d = J.kind == OKVIS_FE_MATCH_2D2D;
+    if (!is2d && J.kind != OKVIS_FE_MATCH_3D2D) return OKVIS_BA_ERR_ARG;
+    if (J.n_a < 0 || J.n_b < 0 || J.n_a > MATCH_MAX_KEYPOINTS || J.n_b > MATCH_MAX_KEYPOINTS) return OKVIS_BA_ERR_ARG;
+    if (!camera_ok(&J.cam_a) || !camera_ok(&J.cam_b)) return OKVIS_BA_ERR_ARG;
+    if (!J.kp_b || (is2d && !J.kp_a) || (!is2d && J.n_a > 0 && !J.hp_W)) return OKVIS_BA_ERR_ARG;
+    if ((J.n_a > 0 && !J.desc_a) || (J.n_b > 0 && (!J.desc_b || !J.pair_a || !J.pair_dist || !J.accepted))) return OKVIS_BA_ERR_ARG;
+    p.live = J.n_a > 0 && J.n_b > 0;
+    p.pre = is2d ? p.live : J.n_a > 0;
+    p.tri = is2d && (J.hp_a || J.cov || J.tri_flags);
+    if (p.tri && !spd_inverse6(J.UOplus, p.info6)) return OKVIS_BA_ERR_ARG;
+    p.tri = p.tri && p.live;
+    if (p.live) rows += (size_t)J.n_a, blocks += (size_t)(J.n_a + fe::MATCH_WAVES - 1) / fe::MATCH_WAVES;
+    if (p.pre) ++n_work, pre_blocks += ((size_t)J.n_a + (is2d ? (size_t)J.n_b : 0) + fe::VMATCH_PRE_THREADS - 1) / fe::VMATCH_PRE_THREADS;
+  }
+  if (blocks > (size_t)INT32_MAX || rows > (size_t)INT32_MAX || pre_blocks > (size_t)INT32_MAX) return OKVIS_BA_ERR_ARG;
+  const size_t db = (size_t)desc_bytes, nbest = (size_t)num_best, dbl = sizeof(double);
+  size_t o_lidx = 0, o_ldist = 0, o_lchi = 0, o_lfl = 0;
+  if (n_work > 0) {
+    FE_TRY(hipSetDevice(c->device));
+    // in: every job's descriptors, masks, keypoints, landmarks and ray sigmas, then the job table; device only: the rays;
+    // back: the projections and the lists; then what the uncertainty launches take and give
+    Layout in, all;
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_vmatch_job& J = jobs[j];
+      Plan& p = plan[j];
+      if (!p.pre) continue;
+      const bool is2d = J.kind == OKVIS_FE_MATCH_2D2D;
+      const size_t na = (size_t)J.n_a, nb = (size_t)J.n_b;
+      if (p.live) p.da = in.add(db * na), p.db = in.add(db * nb), p.kb = in.add(sizeof(float) * 3 * nb);
+      p.sa = J.skip_a ? in.add(na) : 0, p.sb = (p.live && J.skip_b) ? in.add(nb) : 0;
+      if (is2d) p.ka = in.add(sizeof(float) * 3 * na), p.sga = in.add(dbl * na), p.sgb = in.add(dbl * nb);
+      else p.hp = in.add(dbl * 4 * na);
+    }
+    const size_t o_table = in.add(sizeof(fe::VJob) * n_work);
+    all = in;
+    for (int j = 0; j < n_jobs; ++j)
+      if (plan[j].pre && jobs[j].kind == OKVIS_FE_MATCH_2D2D)
+        plan[j].ra = all.add(dbl * 3 * jobs[j].n_a), plan[j].rb = all.add(dbl * 3 * jobs[j].n_b);
+    const size_t o_back = all.size;
+    for (int j = 0; j < n_jobs; ++j)
+      if (plan[j].pre && jobs[j].kind == OKVIS_FE_MATCH_3D2D) {
+        const size_t na = (size_t)jobs[j].n_a;
+        plan[j].uv = all.add(dbl * 2 * na), plan[j].U = all.add(dbl * 4 * na), plan[j].st = all.add(na);
+      }
+    o_lidx = all.add(sizeof(int32_t) * rows * nbest), o_ldist = all.add(sizeof(float) * rows * nbest);
+    o_lchi = all.add(dbl * rows * nbest), o_lfl = all.add(rows * nbest);
+    const size_t o_back_end = all.size;
+    for (int j = 0; j < n_jobs; ++j)
+      if (plan[j].tri) plan[j].t_pairs = all.add(sizeof(int32_t) * 2 * jobs[j].n_b), plan[j].t_sig = all.add(dbl * jobs[j].n_b);
+    for (int j = 0; j < n_jobs; ++j)
+      if (plan[j].tri) {
+        const size_t nb = (size_t)jobs[j].n_b;
+        plan[j].t_hp = all.add(dbl * 4 * nb), plan[j].t_cov = all.add(dbl * 9 * nb), plan[j].t_fl = all.add(nb);
+      }
+    if (int rc = reserve(c, all.size)) return rc;
+    std::vector<fe::VJob> table;
+    int32_t block0 = 0, row0 = 0, pre0 = 0;
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_vmatch_job& J = jobs[j];
+      const Plan& p = plan[j];
+      if (!p.pre) continue;
+      const bool is2d = J.kind == OKVIS_FE_MATCH_2D2D;
+      const size_t na = (size_t)J.n_a, nb = (size_t)J.n_b;
+      char *h = c->h_stage, *d = c->d_stage;
+      fe::VJob D;
+      std::memset(&D, 0, sizeof(D));
+      if (p.live) {
+        std::memcpy(h + p.da, J.desc_a, db * na);
+        std::memcpy(h + p.db, J.desc_b, db * nb);
+        std::memcpy(h + p.kb, J.kp_b, sizeof(float) * 3 * nb);
+        D.desc_a = (const uint8_t*)(d + p.da), D.desc_b = (const uint8_t*)(d + p.db), D.kp_b = (const float*)(d + p.kb);
+      }
+      if (J.skip_a) std::memcpy(h + p.sa, J.skip_a, na), D.skip_a = (const uint8_t*)(d + p.sa);
+      if (p.live && J.skip_b) std::memcpy(h + p.sb, J.skip_b, nb), D.skip_b = (const uint8_t*)(d + p.sb);
+      if (is2d) {
+        std::memcpy(h + p.ka, J.kp_a, sizeof(float) * 3 * na);
+        double *sga = (double*)(h + p.sga), *sgb = (double*)(h + p.sgb);
+        for (size_t k = 0; k < na; ++k) sga[k] = ray_sigma(J.kp_a[3 * k + 2], J.cam_a.intr[0]);
+        for (size_t k = 0; k < nb; ++k) sgb[k] = ray_sigma(J.kp_b[3 * k + 2], J.cam_b.intr[0]);
+        D.kp_a = (const float*)(d + p.ka), D.sig_a = (const double*)(d + p.sga), D.sig_b = (const double*)(d + p.sgb);
+        D.ray_a = (double*)(d + p.ra), D.ray_b = (double*)(d + p.rb);
+        std::memcpy(D.T, J.T_AB, sizeof(D.T));
+      } else {
+        std::memcpy(h + p.hp, J.hp_W, dbl * 4 * na);
+        D.hp_W = (const double*)(d + p.hp);
+        D.uv = (double*)(d + p.uv), D.U = (double*)(d + p.U), D.status = (uint8_t*)(d + p.st);
+        std::memcpy(D.T, J.T_CbW, sizeof(D.T));
+        std::memcpy(D.P3, J.P3, sizeof(D.P3));
+      }
+      D.cam_a = to_device(&J.cam_a), D.cam_b = to_device(&J.cam_b);
+      D.kind = J.kind, D.n_a = J.n_a, D.n_b = J.n_b, D.block0 = block0, D.row0 = row0, D.pre0 = pre0;
+      table.push_back(D);
+      if (p.live) block0 += (J.n_a + fe::MATCH_WAVES - 1) / fe::MATCH_WAVES, row0 += J.n_a;
+      pre0 += (int32_t)((na + (is2d ? nb : 0) + fe::VMATCH_PRE_THREADS - 1) / fe::VMATCH_PRE_THREADS);
+    }
+    std::memcpy(c->h_stage + o_table, table.data(), sizeof(fe::VJob) * n_work);
+    FE_TRY(hipMemcpyAsync(c->d_stage, c->h_stage, in.size, hipMemcpyHostToDevice, c->stream));
+    const fe::VJob* d_table = (const fe::VJob*)(c->d_stage + o_table);
+    hipLaunchKernelGGL(fe::vmatch_prepass_kernel, dim3((unsigned)pre_blocks), dim3(fe::VMATCH_PRE_THREADS), 0, c->stream, d_table,
+                       (int)n_work);
+    FE_TRY(hipGetLastError());
+    if (blocks > 0) {
+      fe::VListParams P;
+      P.jobs = d_table, P.n_jobs = (int32_t)n_work;
+      P.threshold = threshold, P.initial = use_ratio ? FLT_MAX : threshold, P.num_best = num_best;
+      P.list_idx = (int32_t*)(c->d_stage + o_lidx), P.list_dist = (float*)(c->d_stage + o_ldist);
+      P.list_chi2 = (double*)(c->d_stage + o_lchi), P.list_flags = (uint8_t*)(c->d_stage + o_lfl);
+      launch_verified_lists(desc_bytes / 16, (int)blocks, P, c->stream);
+      FE_TRY(hipGetLastError());
+    }
+    FE_TRY(hipMemcpyAsync(c->h_stage + o_back, c->d_stage + o_back, o_back_end - o_back, hipMemcpyDeviceToHost, c->stream));
+    FE_TRY(hipStreamSynchronize(c->stream));
+  }
+  // the assignment chains and matchBody's final loop on the host, as okvis_fe_match_descriptors; then what setBestMatch computes
+  // again for the accepted pairs: 3D2D from the list entry, 2D2D through one launch of stereo_triangulate_kernel per job
+  size_t row0 = 0, tri_lo = SIZE_MAX, tri_hi = 0, tri_out_lo = SIZE_MAX, tri_out_hi = 0;
+  std::vector<int32_t> n_acc((size_t)n_jobs, 0);
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_vmatch_job& J = jobs[j];
+    const Plan& p = plan[j];
+    const bool is2d = J.kind == OKVIS_FE_MATCH_2D2D;
+    const size_t na = (size_t)J.n_a, nb = (size_t)J.n_b;
+    for (int b = 0; b < J.n_b; ++b) J.pair_a[b] = -1, J.pair_dist[b] = FLT_MAX, J.accepted[b] = 0;
+    if (J.chi2) std::memset(J.chi2, 0, dbl * nb);
+    if (J.gate_flags) std::memset(J.gate_flags, 0, nb);
+    if (J.hp_a) std::memset(J.hp_a, 0, dbl * 4 * nb);
+    if (J.cov) std::memset(J.cov, 0, dbl * 9 * nb);
+    if (J.tri_flags) std::memset(J.tri_flags, 0, nb);
+    if (!is2d && p.pre) {
+      if (J.proj_status) std::memcpy(J.proj_status, c->h_stage + p.st, na);
+      if (J.uv) std::memcpy(J.uv, c->h_stage + p.uv, dbl * 2 * na);
+      if (J.U) std::memcpy(J.U, c->h_stage + p.U, dbl * 4 * na);
+    } else {
+      if (J.proj_status) std::memset(J.proj_status, 0, na);
+      if (J.uv) std::memset(J.uv, 0, dbl * 2 * na);
+      if (J.U) std::memset(J.U, 0, dbl * 4 * na);
+    }
+    if (!p.live) continue;
+    const int32_t* li = (const int32_t*)(c->h_stage + o_lidx) + row0 * nbest;
+    const float* ld = (const float*)(c->h_stage + o_ldist) + row0 * nbest;
+    const double* lc = (const double*)(c->h_stage + o_lchi) + row0 * nbest;
+    const uint8_t* lf = (const uint8_t*)(c->h_stage + o_lfl) + row0 * nbest;
+    row0 += na;
+    for (int a = 0; a < J.n_a; ++a)
+      if (!(J.skip_a && J.skip_a[a])) assign_best(a, num_best, li, ld, J.pair_a, J.pair_dist);
+    int32_t* t_pairs = p.tri ? (int32_t*)(c->h_stage + p.t_pairs) : nullptr;
+    double* t_sig = p.tri ? (double*)(c->h_stage + p.t_sig) : nullptr;
+    for (int b = 0; b < J.n_b; ++b) {
+      if (!(J.pair_dist[b] < threshold)) continue;
+      const size_t o = (size_t)J.pair_a[b] * nbest;
+      if (use_ratio && li[o + 1] != -1) {
+        const float best = ld[o], second = ld[o + 1];
+        J.accepted[b] = (best == 0 || second / best > ratio_threshold) ? 1 : 0;
+      } else {
+        J.accepted[b] = 1;
+      }
+      if (!J.accepted[b]) continue;
+      if (!is2d) {
+        for (size_t k = 0; k < nbest; ++k)
+          if (li[o + k] == b) {
+            if (J.chi2) J.chi2[b] = lc[o + k];
+            if (J.gate_flags) J.gate_flags[b] = lf[o + k];
+            break;
+          }
+      } else if (p.tri) {
+        const int32_t a = J.pair_a[b], i = n_acc[j]++;
+        t_pairs[2 * i] = a, t_pairs[2 * i + 1] = b;
+        t_sig[i] = std::fmax(ray_sigma(J.kp_a[3 * a + 2], J.cam_a.intr[0]), ray_sigma(J.kp_b[3 * b + 2], J.cam_b.intr[0]));
+      }
+    }
+    if (n_acc[j] > 0) {
+      tri_lo = std::min(tri_lo, p.t_pairs), tri_hi = std::max(tri_hi, p.t_sig + dbl * nb);
+      tri_out_lo = std::min(tri_out_lo, p.t_hp), tri_out_hi = std::max(tri_out_hi, p.t_fl + nb);
+    }
+  }
+  if (tri_hi > 0) {
+    FE_TRY(hipMemcpyAsync(c->d_stage + tri_lo, c->h_stage + tri_lo, tri_hi - tri_lo, hipMemcpyHostToDevice, c->stream));
+    for (int j = 0; j < n_jobs; ++j) {
+      if (n_acc[j] == 0) continue;
+      const okvis_fe_vmatch_job& J = jobs[j];
+      const Plan& p = plan[j];
+      fe::TriParams P;
+      P.cam_a = to_device(&J.cam_a), P.cam_b = to_device(&J.cam_b);
+      std::memcpy(P.T_AB, J.T_AB, sizeof(P.T_AB));
+      std::memcpy(P.info6, p.info6, sizeof(P.info6));
+      P.sigma_ray_own = 0.5 / std::fmin(J.cam_a.intr[0], J.cam_b.intr[0]);
+      P.n_a = J.n_a, P.n_b = J.n_b, P.n_pairs = n_acc[j], P.want_uncertainty = 1;
+      P.kp_a = (const float*)(c->d_stage + p.ka), P.kp_b = (const float*)(c->d_stage + p.kb);
+      P.pairs = (const int32_t*)(c->d_stage + p.t_pairs), P.sigma_ray = (const double*)(c->d_stage + p.t_sig);
+      P.hp = (double*)(c->d_stage + p.t_hp), P.cov = (double*)(c->d_stage + p.t_cov), P.flags = (uint8_t*)(c->d_stage + p.t_fl);
+      P.gn = nullptr;
+      FE_TRY(hipMemsetAsync(P.cov, 0, dbl * 9 * n_acc[j], c->stream));
+      hipLaunchKernelGGL(fe::stereo_triangulate_kernel, dim3((n_acc[j] + fe::TRI_THREADS - 1) / fe::TRI_THREADS), dim3(fe::TRI_THREADS), 0,
+                         c->stream, P);
+      FE_TRY(hipGetLastError());
+    }
+    FE_TRY(hipMemcpyAsync(c->h_stage + tri_out_lo, c->d_stage + tri_out_lo, tri_out_hi - tri_out_lo, hipMemcpyDeviceToHost, c->stream));
+    FE_TRY(hipStreamSynchronize(c->stream));
+    for (int j = 0; j < n_jobs; ++j) {
+      const okvis_fe_vmatch_job& J = jobs[j];
+      const Plan& p = plan[j];
+      const int32_t* t_pairs = (const int32_t*)(c->h_stage + p.t_pairs);
+      for (int i = 0; i < n_acc[j]; ++i) {
+        const size_t b = (size_t)t_pairs[2 * i + 1];
+        if (J.hp_a) std::memcpy(J.hp_a + 4 * b, c->h_stage + p.t_hp + dbl * 4 * i, dbl * 4);
+        if (J.cov) std::memcpy(J.cov + 9 * b, c->h_stage + p.t_cov + dbl * 9 * i, dbl * 9);
+        if (J.tri_flags) J.tri_flags[b] = *(const uint8_t*)(c->h_stage + p.t_fl + i);
       }
     }
   }

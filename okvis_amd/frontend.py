@@ -1,6 +1,7 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
-with uncertainty, 3D-2D projection and chi-square gating) and its descriptor matching (Hamming candidates, the dense matcher's
-best-match search) on the MI355X.  No CPU path."""
+with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
+best-match search) and whole verified matching steps (the matcher under "Hamming distance and verifyMatch") on the MI355X.  No CPU
+path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,7 +15,8 @@ PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = ra
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
-           "okvis_fe_sac_consensus"]
+           "okvis_fe_sac_consensus", "okvis_fe_match_verified"]
+MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 
 
@@ -28,6 +30,16 @@ class MatchJobC(C.Structure):
     """okvis_fe_match_job"""
     _fields_ = [("n_a", C.c_int32), ("n_b", C.c_int32), ("desc_a", C.c_void_p), ("desc_b", C.c_void_p), ("skip_a", C.c_void_p),
                 ("skip_b", C.c_void_p), ("pair_a", C.c_void_p), ("pair_dist", C.c_void_p), ("accepted", C.c_void_p)]
+
+
+class VMatchJobC(C.Structure):
+    """okvis_fe_vmatch_job"""
+    _fields_ = [("kind", C.c_int32), ("n_a", C.c_int32), ("n_b", C.c_int32), ("desc_a", C.c_void_p), ("desc_b", C.c_void_p),
+                ("skip_a", C.c_void_p), ("skip_b", C.c_void_p), ("kp_a", C.c_void_p), ("kp_b", C.c_void_p), ("cam_a", CameraC),
+                ("cam_b", CameraC), ("hp_W", C.c_void_p), ("T_CbW", C.c_double * 7), ("P3", C.c_double * 9), ("T_AB", C.c_double * 7),
+                ("UOplus", C.c_double * 36), ("pair_a", C.c_void_p), ("pair_dist", C.c_void_p), ("accepted", C.c_void_p),
+                ("proj_status", C.c_void_p), ("uv", C.c_void_p), ("U", C.c_void_p), ("chi2", C.c_void_p), ("gate_flags", C.c_void_p),
+                ("hp_a", C.c_void_p), ("cov", C.c_void_p), ("tri_flags", C.c_void_p)]
 
 
 class SacJobC(C.Structure):
@@ -95,6 +107,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_match_descriptors.argtypes = [vp, i32, C.POINTER(MatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_bearing_vectors.argtypes = [vp, cam, i32, vp, vp, vp, vp]
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
+        L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
 
 
 class Frontend:
@@ -219,6 +232,23 @@ class Frontend:
                    int(bool(use_ratio)), float(ratio_threshold))
         return [(pa, pd, acc.astype(bool)) for pa, pd, acc in out]
 
+    def match_verified(self, jobs, threshold, num_best=4, use_ratio=False, ratio_threshold=0.0):
+        """Whole matching steps under the frontend's own distance (Hamming distance under the threshold AND verifyMatch).  jobs: dicts
+        with kind (MATCH_3D2D | MATCH_2D2D), desc_a, desc_b, kp_b [n_b][3], cam_b, optional skip_a / skip_b, and
+        MATCH_2D2D: kp_a [n_a][3], cam_a, T_AB [7], UOplus [6][6];
+        MATCH_3D2D: hp_W [n_a][4], T_CbW [7], P3 [3][3] (kp_a, cam_a optional).
+        -> per job a dict: pair_a [n_b] int32, pair_dist [n_b] float32, accepted [n_b] bool, and for the accepted pairs (zeros
+        elsewhere) MATCH_3D2D: chi2 [n_b], gate_flags [n_b] besides proj_status [n_a], uv [n_a][2], U [n_a][2][2];
+        MATCH_2D2D: hp_a [n_b][4], cov [n_b][3][3], tri_flags [n_b].  All jobs go through one call; they must not depend on each
+        other's result."""
+        table, keep, out = vmatch_job_table(jobs)
+        width = keep[0][0].shape[1] if keep else 48
+        self._call("match_verified", len(jobs), table, width, float(threshold), int(num_best), int(bool(use_ratio)),
+                   float(ratio_threshold))
+        for r in out:
+            r["accepted"] = r["accepted"].astype(bool)
+        return out
+
     def bearing_vectors(self, cam: CameraC, kp):
         """kp [n][3] (x, y, size) -> bearing [n][3] unit vectors, sigma_angle [n], ok [n] bool: what the two RANSAC adapters hold
         per keypoint"""
@@ -281,4 +311,57 @@ def sac_job_table(jobs, want_scores=False):
         t.counts, t.best, t.n_inliers, t.inliers = counts.ctypes.data, scalars.ctypes.data, scalars.ctypes.data + 4, inl.ctypes.data
         t.scores = _ptr(sc)
         out.append((counts, scalars, inl, sc))
+    return table, keep, out
+
+
+def vmatch_job_table(jobs):
+    """-> (okvis_fe_vmatch_job array, the input arrays it points into, per job the dict of output arrays); both lists have to
+    outlive the call"""
+    keep, out = [], []
+    table = (VMatchJobC * max(1, len(jobs)))()
+    width = None
+    for j, job in enumerate(jobs):
+        kind = int(job["kind"])
+        if kind not in (MATCH_3D2D, MATCH_2D2D):
+            raise ValueError("kind is MATCH_3D2D or MATCH_2D2D")
+        da, db = _desc(job["desc_a"]), _desc(job["desc_b"])
+        if da.shape[1] != db.shape[1] or width not in (None, da.shape[1]):
+            raise ValueError("descriptors of different lengths")
+        width = da.shape[1]
+        na, nb = len(da), len(db)
+        sa, sb = _skip(job.get("skip_a"), na), _skip(job.get("skip_b"), nb)
+
+        def rows(a, n, cols, dtype):   # [n][cols], never a NULL pointer
+            a = np.ascontiguousarray(a, dtype).reshape(-1, cols)
+            if len(a) != n:
+                raise ValueError("arrays of different lengths")
+            return a if n else np.zeros((1, cols), dtype)
+
+        kb = rows(job["kp_b"], nb, 3, np.float32)
+        ka = rows(job["kp_a"], na, 3, np.float32) if job.get("kp_a") is not None else None
+        t = table[j]
+        t.kind, t.n_a, t.n_b = kind, na, nb
+        t.desc_a, t.desc_b, t.skip_a, t.skip_b = da.ctypes.data, db.ctypes.data, _ptr(sa), _ptr(sb)
+        t.kp_a, t.kp_b = _ptr(ka), kb.ctypes.data
+        t.cam_b = job["cam_b"]
+        t.cam_a = job.get("cam_a", job["cam_b"])
+        r = {"pair_a": np.zeros(nb, np.int32), "pair_dist": np.zeros(nb, np.float32), "accepted": np.zeros(nb, np.uint8)}
+        hp = None
+        if kind == MATCH_3D2D:
+            hp = rows(job["hp_W"], na, 4, np.float64)
+            t.hp_W = hp.ctypes.data
+            t.T_CbW[:] = list(_f64(job["T_CbW"], 7))
+            t.P3[:] = list(_f64(job["P3"], 9))
+            r.update(proj_status=np.zeros(na, np.uint8), uv=np.zeros((na, 2)), U=np.zeros((na, 2, 2)), chi2=np.zeros(nb),
+                     gate_flags=np.zeros(nb, np.uint8))
+        else:
+            if ka is None:
+                raise ValueError("MATCH_2D2D needs kp_a")
+            t.T_AB[:] = list(_f64(job["T_AB"], 7))
+            t.UOplus[:] = list(_f64(job["UOplus"], 36))
+            r.update(hp_a=np.zeros((nb, 4)), cov=np.zeros((nb, 3, 3)), tri_flags=np.zeros(nb, np.uint8))
+        for name, arr in r.items():
+            setattr(t, name, arr.ctypes.data)
+        keep.append((da, db, sa, sb, ka, kb, hp))
+        out.append(r)
     return table, keep, out
