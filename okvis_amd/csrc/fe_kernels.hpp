@@ -167,6 +167,18 @@ __device__ inline void triangulate_fast(const double* e1, const double* p2, cons
   hp[0] = mid[0] / n, hp[1] = mid[1] / n, hp[2] = mid[2] / n, hp[3] = 1.0 / n;
 }
 
+// The job a workgroup of a batched grid belongs to: the last one whose first workgroup (jobs[j].*first) is not after this one.
+template <class Job>
+__device__ inline int find_job(const Job* jobs, int n_jobs, int32_t Job::*first) {
+  int lo = 0, hi = n_jobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (jobs[mid].*first <= (int)blockIdx.x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
 constexpr int TRI_THREADS = 64;
 
 // Eigen's ColPivHouseholderQR<Matrix<double,9,9>>::rank() on a column-major 9x9 held in LDS as M[(r + 9 c) * TRI_THREADS]
@@ -285,6 +297,34 @@ __device__ inline void point_covariance(const double* H /*row-major 9x9*/, doubl
   cov[8] = (S[0] * S[3] - S[1] * S[1]) * idet;
 }
 
+// stereoTriangulate (ProbabilisticStereoTriangulator.cpp:205-236) behind its two back-projections: from the normalised rays e1 / e2
+// (both in frame A; C_AB the rotation of T_AB) to the test of the two reprojection errors.  -> isValid; hp is the point,
+// *hp_assigned whether the reference hands it out
+__device__ inline bool verify_2d2d(const Camera& cam_a, const Camera& cam_b, const double* T_AB, const double* C_AB, const float* ka,
+                                   const float* kb, const double* e1, const double* e2, double sigma, double* hp, bool* parallel,
+                                   bool* hp_assigned) {
+  bool valid;
+  triangulate_fast(e1, T_AB, e2, sigma, hp, &valid, parallel);
+  *hp_assigned = false;
+  if (valid) {
+    double errA, errB;
+    valid = reprojection_error4(cam_a, ka, hp, &errA);
+    if (valid) {
+      // hp_B = T_BA hp_A = (C_AB^T (p - r w), w)
+      const double d[3] = {hp[0] - T_AB[0] * hp[3], hp[1] - T_AB[1] * hp[3], hp[2] - T_AB[2] * hp[3]};
+      double hb[4];
+      mat3_Tvec(C_AB, d, hb);
+      hb[3] = hp[3];
+      valid = reprojection_error4(cam_b, kb, hb, &errB);
+      if (valid) {
+        *hp_assigned = true;
+        if (errA > 4.0 || errB > 4.0) valid = false;
+      }
+    }
+  }
+  return valid;
+}
+
 __global__ void __launch_bounds__(TRI_THREADS) stereo_triangulate_kernel(const TriParams P) {
   __shared__ double sH[81 * TRI_THREADS];
   const int i = blockIdx.x * TRI_THREADS + threadIdx.x;
@@ -304,26 +344,9 @@ __global__ void __launch_bounds__(TRI_THREADS) stereo_triangulate_kernel(const T
   mat3_vec(C_AB, dB, dBA);
   normalize3(dA);
   normalize3(dBA);
-  bool valid, parallel;
-  triangulate_fast(dA, P.T_AB, dBA, sigma, hp, &valid, &parallel);
+  bool parallel, hp_assigned;
+  const bool valid = verify_2d2d(P.cam_a, P.cam_b, P.T_AB, C_AB, ka, kb, dA, dBA, sigma, hp, &parallel, &hp_assigned);
   if (!parallel) flags |= OKVIS_FE_TRI_NOT_PARALLEL;
-  bool hp_assigned = false;
-  if (valid) {
-    double errA, errB;
-    valid = reprojection_error4(P.cam_a, ka, hp, &errA);
-    if (valid) {
-      // hp_B = T_BA hp_A = (C_AB^T (p - r w), w)
-      const double d[3] = {hp[0] - P.T_AB[0] * hp[3], hp[1] - P.T_AB[1] * hp[3], hp[2] - P.T_AB[2] * hp[3]};
-      double hb[4];
-      mat3_Tvec(C_AB, d, hb);
-      hb[3] = hp[3];
-      valid = reprojection_error4(P.cam_b, kb, hb, &errB);
-      if (valid) {
-        hp_assigned = true;
-        if (errA > 4.0 || errB > 4.0) valid = false;
-      }
-    }
-  }
   if (valid) flags |= OKVIS_FE_TRI_VALID;
   if (P.hp)
     for (int k = 0; k < 4; ++k) P.hp[4 * i + k] = hp_assigned ? hp[k] : 0.0;
@@ -381,18 +404,24 @@ struct ProjParams {
   uint8_t* status;
 };
 
-// doSetup, Match3D2D (VioKeyframeWindowMatchingAlgorithm.cpp:177-205)
+// doSetup, Match3D2D (VioKeyframeWindowMatchingAlgorithm.cpp:177-205) for one landmark h (world frame): its projection uv into the
+// camera at T_CW and the 2x3 Jacobian J of that projection; the caller has zeroed both.  -> the ProjectionStatus.
+// U = J P3 J^T (:196-199) is written out by each caller: behind a function of any shape tried, the contraction of RADTAN8's
+// d(rad)/d(rho) moved in project_landmarks_kernel (profiles/fe_refactor_notes.md)
+__device__ inline int project_landmark(const Camera& cam, const double* T_CW, const double* h, double* uv, double* J) {
+  double C[9], p[3], hc[4];
+  qrot(T_CW + 3, C);
+  mat3_vec(C, h, p);
+  for (int k = 0; k < 3; ++k) hc[k] = p[k] + T_CW[k] * h[3];
+  hc[3] = h[3];
+  return project_homogeneous(cam, hc, uv, J);
+}
+
 __global__ void project_landmarks_kernel(const ProjParams P) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P.n) return;
-  const double* h = P.hp_W + 4 * i;
-  double C[9], p[3], hc[4];
-  qrot(P.T_CbW + 3, C);
-  mat3_vec(C, h, p);
-  for (int k = 0; k < 3; ++k) hc[k] = p[k] + P.T_CbW[k] * h[3];
-  hc[3] = h[3];
   double uv[2] = {0, 0}, J[6] = {0, 0, 0, 0, 0, 0};
-  const int st = project_homogeneous(P.cam, hc, uv, J);
+  const int st = project_landmark(P.cam, P.T_CbW, P.hp_W + 4 * i, uv, J);
   if (P.status) P.status[i] = (uint8_t)st;
   if (P.uv) P.uv[2 * i] = uv[0], P.uv[2 * i + 1] = uv[1];
   if (P.U) {
@@ -414,15 +443,12 @@ struct GateParams {
   uint8_t* flags;
 };
 
-// verifyMatch (:320-337) / setBestMatch (:494-512), Match3D2D
-__global__ void gate_3d2d_kernel(const GateParams P) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P.n_pairs) return;
-  const int a = P.pairs[2 * i], b = P.pairs[2 * i + 1];
-  const float* kb = P.kp_b + 3 * b;
+// verifyMatch (:320-337) / setBestMatch (:494-512), Match3D2D: projection uv with uncertainty U against keypoint kb.
+// -> the OKVIS_FE_GATE_* bits
+__device__ inline unsigned gate_3d2d(const double* uv, const double* U, const float* kb, double* chi2_out) {
   const double sd = 0.8 * (double)kb[2] / 12.0, s2 = sd * sd;
-  const double u00 = s2 + P.U[4 * a], u01 = P.U[4 * a + 1], u10 = P.U[4 * a + 2], u11 = s2 + P.U[4 * a + 3];
-  const double e0 = P.uv[2 * a] - (double)kb[0], e1 = P.uv[2 * a + 1] - (double)kb[1];
+  const double u00 = s2 + U[0], u01 = U[1], u10 = U[2], u11 = s2 + U[3];
+  const double e0 = uv[0] - (double)kb[0], e1 = uv[1] - (double)kb[1];
   const double idet = 1.0 / (u00 * u11 - u01 * u10);
   // err^T U^-1 err with U^-1 = [u11 -u01; -u10 u00] / det
   const double chi2 = e0 * ((u11 * idet) * e0 + (-u01 * idet) * e1) + e1 * ((-u10 * idet) * e0 + (u00 * idet) * e1);
@@ -430,6 +456,16 @@ __global__ void gate_3d2d_kernel(const GateParams P) {
   if (chi2 < 4.0 && chi2 > -1.0) f |= OKVIS_FE_GATE_VERIFIED;  // `const int chi2 = ...; chi2 < 4.0`: truncation towards zero
   if (!(chi2 > 4.0)) f |= OKVIS_FE_GATE_ACCEPTED;
   if (sqrt(u00 * u00 + u01 * u01 + u10 * u10 + u11 * u11) > 25.0 / (s2 * sqrt(2.0))) f |= OKVIS_FE_GATE_UNCERTAIN;
+  *chi2_out = chi2;
+  return f;
+}
+
+__global__ void gate_3d2d_kernel(const GateParams P) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P.n_pairs) return;
+  const int a = P.pairs[2 * i], b = P.pairs[2 * i + 1];
+  double chi2;
+  const unsigned f = gate_3d2d(P.uv + 2 * a, P.U + 4 * a, P.kp_b + 3 * b, &chi2);
   if (P.chi2) P.chi2[i] = chi2;
   if (P.flags) P.flags[i] = (uint8_t)f;
 }

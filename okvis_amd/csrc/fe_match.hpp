@@ -17,6 +17,8 @@
 #include <cfloat>
 #include <cstdint>
 
+#include "fe_kernels.hpp"
+
 namespace fe {
 
 constexpr int MATCH_WAVES = 4;                   // rows of A per workgroup, one wave each
@@ -157,13 +159,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void row_offsets_kernel(const int32_t
 template <int W>
 __global__ __launch_bounds__(MATCH_THREADS) void best_lists_kernel(BestParams P) {
   __shared__ uint4 lds[W * MATCH_TILE];
-  int lo = 0, hi = P.n_jobs - 1;  // the last job whose first workgroup is not after this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (P.jobs[mid].block0 <= (int)blockIdx.x) lo = mid;
-    else hi = mid - 1;
-  }
-  const MatchJob J = P.jobs[lo];
+  const MatchJob J = P.jobs[find_job(P.jobs, P.n_jobs, &MatchJob::block0)];
   const int lane = threadIdx.x & 63;
   const int row = ((int)blockIdx.x - J.block0) * MATCH_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const bool live = row < J.n_a && !(J.skip_a && J.skip_a[row]);

@@ -187,13 +187,7 @@ BA_HD double sac_score_relative(const double* h, const double* f1, const double*
 #if defined(__HIPCC__)
 __global__ __launch_bounds__(SAC_THREADS) void sac_consensus_kernel(SacParams P) {
   __shared__ double hyp[SAC_MODEL_TILE * SAC_MODEL_STRIDE];
-  int lo = 0, hi = P.n_jobs - 1;  // the last job whose first workgroup is not after this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (P.jobs[mid].block0 <= (int)blockIdx.x) lo = mid;
-    else hi = mid - 1;
-  }
-  const SacJob J = P.jobs[lo];
+  const SacJob J = P.jobs[find_job(P.jobs, P.n_jobs, &SacJob::block0)];
   const int local = (int)blockIdx.x - J.block0;
   const int tile = local % J.tiles, m0 = (local / J.tiles) * SAC_MODEL_TILE;
   const int nm = J.n_models - m0 < SAC_MODEL_TILE ? J.n_models - m0 : SAC_MODEL_TILE;

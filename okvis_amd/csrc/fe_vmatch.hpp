@@ -6,8 +6,8 @@
 //   vmatch_prepass_kernel        everything that depends on one keypoint only, for all jobs of a call.
 //                                2D-2D: the normalised ray of every keypoint of A and the normalised C_AB ray of every keypoint of B
 //                                (the first lines of stereoTriangulate, ProbabilisticStereoTriangulator.cpp:191-205).
-//                                3D-2D: uv, U and the projection status of every row of A in play (doSetup :165-213, the arithmetic
-//                                of project_landmarks_kernel).
+//                                3D-2D: uv, U and the projection status of every row of A in play (doSetup :165-213:
+//                                project_landmark, as project_landmarks_kernel).
 //   verified_lists_kernel<W>     layout of best_lists_kernel: one wave per row of A, B staged through LDS in tiles of 256, the list
 //                                wave-uniform in registers.  A pair has to be verified only if it is in play, d < threshold and
 //                                d < the list's last entry at the start of the tile (the last entry only falls).  Those few pairs of
@@ -15,9 +15,10 @@
 //                                lanes busy, and the survivors inserted in slot order = ascending b, each one checked again against the
 //                                last entry it finds: the sequence of the reference.  The fp64 geometry never runs under the sparse
 //                                mask of the distance loop.
-// The geometry is the code of stereo_triangulate_kernel / gate_3d2d_kernel (fe_kernels.hpp), through the same helpers and in the
-// same order, so that a decision here is the decision the stand-alone entries take for that pair.  No atomics; nothing depends on
-// scheduling.
+// The geometry is not restated here: project_landmark, verify_2d2d and gate_3d2d (fe_kernels.hpp) are the functions
+// project_landmarks_kernel, stereo_triangulate_kernel and gate_3d2d_kernel call, so a decision here is the decision the stand-alone
+// entries take for that pair.  One exception, five lines: the product U = J P3 J^T behind project_landmark is written out in both
+// kernels (fe_kernels.hpp says why).  No atomics; nothing depends on scheduling.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -67,13 +68,7 @@ struct VListParams {
 };
 
 __global__ __launch_bounds__(VMATCH_PRE_THREADS) void vmatch_prepass_kernel(const VJob* jobs, int n_jobs) {
-  int lo = 0, hi = n_jobs - 1;  // the last job whose first workgroup is not after this one
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (jobs[mid].pre0 <= (int)blockIdx.x) lo = mid;
-    else hi = mid - 1;
-  }
-  const VJob& J = jobs[lo];
+  const VJob& J = jobs[find_job(jobs, n_jobs, &VJob::pre0)];
   const int i = ((int)blockIdx.x - J.pre0) * VMATCH_PRE_THREADS + (int)threadIdx.x;
   if (J.kind == OKVIS_FE_MATCH_2D2D) {
     if (i < J.n_a) {
@@ -94,21 +89,14 @@ __global__ __launch_bounds__(VMATCH_PRE_THREADS) void vmatch_prepass_kernel(cons
     }
     return;
   }
-  // doSetup, Match3D2D (:177-205): project_landmarks_kernel for the rows in play, zeros for the others
+  // doSetup, Match3D2D (:177-205): the projection for the rows in play, zeros for the others
   if (i >= J.n_a) return;
   double uv[2] = {0, 0}, U[4] = {0, 0, 0, 0};
   int st = 0;
   if (!(J.skip_a && J.skip_a[i])) {
-    const double* h = J.hp_W + 4 * i;
-    double C[9], p[3], hc[4];
-    qrot(J.T + 3, C);
-    mat3_vec(C, h, p);
-    for (int k = 0; k < 3; ++k) hc[k] = p[k] + J.T[k] * h[3];
-    hc[3] = h[3];
-    double Jc[6] = {0, 0, 0, 0, 0, 0};
-    st = project_homogeneous(J.cam_b, hc, uv, Jc);
-    double JP[6];
-    for (int r = 0; r < 2; ++r)
+    double Jc[6] = {0, 0, 0, 0, 0, 0}, JP[6];
+    st = project_landmark(J.cam_b, J.T, J.hp_W + 4 * i, uv, Jc);
+    for (int r = 0; r < 2; ++r)  // U = J P3 J^T, as project_landmarks_kernel writes it out
       for (int c = 0; c < 3; ++c) JP[3 * r + c] = Jc[3 * r] * J.P3[c] + Jc[3 * r + 1] * J.P3[3 + c] + Jc[3 * r + 2] * J.P3[6 + c];
     for (int r = 0; r < 2; ++r)
       for (int c = 0; c < 2; ++c) U[2 * r + c] = JP[3 * r] * Jc[3 * c] + JP[3 * r + 1] * Jc[3 * c + 1] + JP[3 * r + 2] * Jc[3 * c + 2];
@@ -118,56 +106,11 @@ __global__ __launch_bounds__(VMATCH_PRE_THREADS) void vmatch_prepass_kernel(cons
   for (int k = 0; k < 4; ++k) J.U[4 * i + k] = U[k];
 }
 
-// stereoTriangulate (ProbabilisticStereoTriangulator.cpp:178-236) behind its two back-projections: the lines of
-// stereo_triangulate_kernel between normalize3 and OKVIS_FE_TRI_VALID.  e1 / e2: the rays the pre-pass left.
-__device__ inline bool verify_2d2d(const Camera& cam_a, const Camera& cam_b, const double* T_AB, const double* C_AB, const float* ka,
-                                   const float* kb, const double* e1, const double* e2, double sigma) {
-  double hp[4] = {0, 0, 0, 0};
-  bool valid, parallel;
-  triangulate_fast(e1, T_AB, e2, sigma, hp, &valid, &parallel);
-  if (valid) {
-    double errA, errB;
-    valid = reprojection_error4(cam_a, ka, hp, &errA);
-    if (valid) {
-      const double d[3] = {hp[0] - T_AB[0] * hp[3], hp[1] - T_AB[1] * hp[3], hp[2] - T_AB[2] * hp[3]};
-      double hb[4];
-      mat3_Tvec(C_AB, d, hb);
-      hb[3] = hp[3];
-      valid = reprojection_error4(cam_b, kb, hb, &errB);
-      if (valid) {
-        if (errA > 4.0 || errB > 4.0) valid = false;
-      }
-    }
-  }
-  return valid;
-}
-
-// verifyMatch, Match3D2D (:320-337): the lines of gate_3d2d_kernel.  -> OKVIS_FE_GATE_* bits
-__device__ inline unsigned gate_3d2d(const double* uv, const double* U, const float* kb, double* chi2_out) {
-  const double sd = 0.8 * (double)kb[2] / 12.0, s2 = sd * sd;
-  const double u00 = s2 + U[0], u01 = U[1], u10 = U[2], u11 = s2 + U[3];
-  const double e0 = uv[0] - (double)kb[0], e1 = uv[1] - (double)kb[1];
-  const double idet = 1.0 / (u00 * u11 - u01 * u10);
-  const double chi2 = e0 * ((u11 * idet) * e0 + (-u01 * idet) * e1) + e1 * ((-u10 * idet) * e0 + (u00 * idet) * e1);
-  unsigned f = 0;
-  if (chi2 < 4.0 && chi2 > -1.0) f |= OKVIS_FE_GATE_VERIFIED;
-  if (!(chi2 > 4.0)) f |= OKVIS_FE_GATE_ACCEPTED;
-  if (sqrt(u00 * u00 + u01 * u01 + u10 * u10 + u11 * u11) > 25.0 / (s2 * sqrt(2.0))) f |= OKVIS_FE_GATE_UNCERTAIN;
-  *chi2_out = chi2;
-  return f;
-}
-
 template <int W>
 __global__ __launch_bounds__(MATCH_THREADS) void verified_lists_kernel(VListParams P) {
   __shared__ uint4 lds[W * MATCH_TILE];
   __shared__ uint32_t queue[MATCH_WAVES][MATCH_TILE];  // per row: (index in the tile << 16) | distance of the pairs to verify
-  int lo = 0, hi = P.n_jobs - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (P.jobs[mid].block0 <= (int)blockIdx.x) lo = mid;
-    else hi = mid - 1;
-  }
-  const VJob& J = P.jobs[lo];
+  const VJob& J = P.jobs[find_job(P.jobs, P.n_jobs, &VJob::block0)];
   const int n_a = J.n_a, n_b = J.n_b;
   const bool is2d = J.kind == OKVIS_FE_MATCH_2D2D;
   const int lane = threadIdx.x & 63;
@@ -232,7 +175,9 @@ __global__ __launch_bounds__(MATCH_THREADS) void verified_lists_kernel(VListPara
           if (is2d) {
             const double rb[3] = {J.ray_b[3 * b], J.ray_b[3 * b + 1], J.ray_b[3 * b + 2]};
             const double sig_b = J.sig_b[b];
-            ok = verify_2d2d(J.cam_a, J.cam_b, J.T, C_AB, ka, kb, ra, rb, sig_a > sig_b ? sig_a : sig_b);
+            double hp[4];
+            bool parallel, hp_assigned;
+            ok = verify_2d2d(J.cam_a, J.cam_b, J.T, C_AB, ka, kb, ra, rb, sig_a > sig_b ? sig_a : sig_b, hp, &parallel, &hp_assigned);
           } else {
             fl = gate_3d2d(uv, U, kb, &chi2);
             ok = (fl & OKVIS_FE_GATE_VERIFIED) != 0u;

@@ -1,0 +1,177 @@
+#!/usr/bin/env python3
+"""Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
+
+Every okvis_fe_* entry is called through okvis_amd.frontend; per case the SHA-256 of every output array goes to OUT.json.  Two trees
+whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.
+
+    python tools/fe_digest.py OUT.json [--root TREE]      (TREE: the checkout whose okvis_amd is used, default this one)
+
+The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py, tests/golden/) are
+those of the checkout the tool itself is in; nothing outside it is read.
+  verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
+                      settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
+  stand-alone pieces  the same scenes through project_landmarks (and the two camera models the scenes lack), gate_3d2d,
+                      hamming_candidates (also with a capacity under the total) and stereo_triangulate (with and without sigma_ray,
+                      want_uncertainty 0 and 1, the _gn variant)
+  descriptor matcher  widths 16 / 32 / 48 / 64 through both matchers, alone and as a batch; the recorded cases of dense_matcher.npz
+  RANSAC              the recorded problems of sac_consensus.npz with and without scores, alone and as a batch; bearing_vectors for
+                      the four camera models
+"""
+import argparse
+import ctypes as C
+import functools
+import hashlib
+import json
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("out")
+ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+args = ap.parse_args()
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(HERE, "tests"))
+sys.path.insert(0, os.path.abspath(args.root))
+
+import numpy as np  # noqa: E402
+
+import sac_cases  # noqa: E402
+import test_gpu_descriptor_matcher as DM  # noqa: E402  (its scene generator and the golden cases)
+import vmatch_scene as SC  # noqa: E402
+from okvis_amd import frontend as F  # noqa: E402
+from okvis_amd.window import DIST_EQUIDISTANT, DIST_RADTAN  # noqa: E402
+
+assert os.path.abspath(F.__file__).startswith(os.path.abspath(args.root) + os.sep), F.__file__
+
+SHAPES = [(0, 5), (5, 0), (1, 1), (63, 65), (64, 64), (65, 63), (257, 513), (400, 400)]
+KINDS = [F.MATCH_3D2D, F.MATCH_2D2D]
+MODELS = [DIST_RADTAN, DIST_EQUIDISTANT]
+SETTINGS = [(1, False), (4, False), (8, False), (4, True), (8, True)]
+RATIO = 1.2
+OTHER_INTR = {0: [455.0, 452.0, 370.0, 245.0],                                                    # DIST_NONE
+              3: [420.0, 418.0, 370.0, 243.0, -0.25, 0.06, 0.0002, -0.0001, 0.004, 0.03, -0.01, 0.002]}   # DIST_RADTAN8
+BEARING_INTR = dict(OTHER_INTR)
+BEARING_INTR.update({int(m): SC.INTR[m] for m in MODELS})
+
+out = {}
+
+
+def sha(*arrays):
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def record(name, **arrays):
+    assert name not in out, name
+    out[name] = {k: sha(v) for k, v in arrays.items()}
+
+
+@functools.lru_cache(maxsize=None)
+def scene(model, k, skipped=0.0):
+    return SC.scene(model, 1000 + 10 * k + model, *SHAPES[k], skipped)
+
+
+def vjob(kind, s):
+    cam = F.camera(s["intr"], s["model"])
+    j = {"kind": kind, "desc_a": s["desc_a"], "desc_b": s["desc_b"], "kp_a": s["kp_a"], "kp_b": s["kp_b"], "cam_a": cam, "cam_b": cam,
+         "skip_a": s["skip_a"], "skip_b": s["skip_b"]}
+    if kind == F.MATCH_3D2D:
+        j.update(hp_W=s["hp_W"], T_CbW=s["T_CbW"], P3=s["P3"])
+    else:
+        j.update(T_AB=s["T_AB"], UOplus=s["UOplus"])
+    return j
+
+
+fe = F.Frontend()
+
+# ---------------------------------------------------------------- verified matching
+cases = [(kind, model, k, skipped) for kind in KINDS for model in MODELS for k in range(len(SHAPES)) for skipped in (0.0, 0.15)]
+for num_best, use_ratio in SETTINGS:
+    tag = f"nb{num_best}_ratio{int(use_ratio)}"
+    for kind, model, k, skipped in cases:
+        got, = fe.match_verified([vjob(kind, scene(model, k, skipped))], SC.THRESHOLD, num_best, use_ratio, RATIO)
+        record(f"vmatch/kind{kind}_model{model}_shape{k}_skip{int(skipped > 0)}_{tag}", **got)
+    batch = fe.match_verified([vjob(kind, scene(model, k, skipped)) for kind, model, k, skipped in cases], SC.THRESHOLD, num_best, use_ratio,
+                              RATIO)
+    for j, got in enumerate(batch):
+        record(f"vmatch_batch/{tag}_job{j}", **got)
+
+# ---------------------------------------------------------------- stand-alone pieces
+for model in MODELS:
+    for k in range(len(SHAPES)):
+        s = scene(model, k)
+        name = f"model{model}_shape{k}"
+        cam = F.camera(s["intr"], model)
+        uv, U, st = fe.project_landmarks(cam, s["T_CbW"], s["P3"], s["hp_W"])
+        record(f"project_landmarks/{name}", uv=uv, U=U, status=st)
+        pairs, dist = fe.hamming_candidates(s["desc_a"], s["desc_b"], SC.THRESHOLD)
+        record(f"hamming_candidates/{name}", pairs=pairs, dist=dist)
+        sk = scene(model, k, 0.15)
+        pairs_s, dist_s = fe.hamming_candidates(sk["desc_a"], sk["desc_b"], SC.THRESHOLD, sk["skip_a"], sk["skip_b"])
+        record(f"hamming_candidates/{name}_skip", pairs=pairs_s, dist=dist_s)
+        if len(pairs) > 1:       # a capacity under the total: the prefix comes back, the rest stays as it was
+            cap, n = len(pairs) // 2, C.c_int32(-1)
+            p2, d2 = np.full((cap + 1, 2), -7, np.int32), np.full(cap + 1, -7.0, np.float32)
+            fe._call("hamming_candidates", SC.WIDTH, len(s["desc_a"]), s["desc_a"].ctypes.data, None, len(s["desc_b"]), s["desc_b"].ctypes.data,
+                     None, SC.THRESHOLD, cap, p2.ctypes.data, d2.ctypes.data, C.byref(n))
+            record(f"hamming_candidates/{name}_capacity", pairs=p2, dist=d2, total=np.int32(n.value))
+        chi2, flags = fe.gate_3d2d(uv, U, s["kp_b"], pairs) if len(uv) else (np.zeros(0), np.zeros(0, np.uint8))
+        record(f"gate_3d2d/{name}", chi2=chi2, flags=flags)
+        tri = (cam, cam, s["T_AB"], s["UOplus"], s["kp_a"], s["kp_b"], pairs)
+        sig = SC.pair_sigmas(s, pairs)
+        for sname, sigma in (("sigma", sig), ("nosigma", None)):
+            for want in (0, 1):
+                hp, cov, fl = fe.stereo_triangulate(*tri, sigma, want_uncertainty=bool(want))
+                record(f"stereo_triangulate/{name}_{sname}_unc{want}", hp=hp, cov=cov, flags=fl)
+            hp, cov, fl, gn = fe.stereo_triangulate_gn(*tri, sigma)
+            record(f"stereo_triangulate_gn/{name}_{sname}", hp=hp, cov=cov, flags=fl, gn=gn)
+for model, intr in OTHER_INTR.items():     # the camera models the scenes do not have: the landmarks of the largest scenes
+    for k in (6, 7):
+        s = scene(DIST_RADTAN, k)
+        uv, U, st = fe.project_landmarks(F.camera(intr, model), s["T_CbW"], s["P3"], s["hp_W"])
+        record(f"project_landmarks/model{model}_shape{k}", uv=uv, U=U, status=st)
+
+# ---------------------------------------------------------------- descriptor matcher
+for width in (16, 32, 48, 64):
+    jobs = []
+    for k, (n_a, n_b) in enumerate(DM.SIZES):
+        for skips in (False, True):
+            a, b, sa, sb = DM.scene(100 * width + k, n_a, n_b, width, 0.25 if skips else 0.0)
+            jobs.append((a, b, sa, sb))
+            name = f"w{width}_size{k}_skip{int(skips)}"
+            pairs, dist = fe.hamming_candidates(a, b, width * 8 * 0.12, sa, sb)
+            record(f"hamming_candidates/{name}", pairs=pairs, dist=dist)
+            for num_best, use_ratio in ((1, False), (4, False), (4, True), (8, True)):
+                (pa, pd, acc), = fe.match_descriptors([(a, b, sa, sb)], width * 8 * 0.15, num_best, use_ratio, RATIO)
+                record(f"match_descriptors/{name}_nb{num_best}_ratio{int(use_ratio)}", pair_a=pa, pair_dist=pd, accepted=acc)
+    for num_best, use_ratio in ((4, False), (4, True)):
+        for j, (pa, pd, acc) in enumerate(fe.match_descriptors(jobs, width * 8 * 0.15, num_best, use_ratio, RATIO)):
+            record(f"match_descriptors_batch/w{width}_nb{num_best}_ratio{int(use_ratio)}_job{j}", pair_a=pa, pair_dist=pd, accepted=acc)
+golden = DM.golden_cases()
+assert len(golden) == 6
+for i, c in enumerate(golden):
+    (pa, pd, acc), = fe.match_descriptors([(c["desc_a"], c["desc_b"], c["skip_a"], c["skip_b"])], float(c["threshold"]), int(c["num_best"]),
+                                          bool(c["use_ratio"]), float(c["ratio_threshold"]))
+    record(f"match_descriptors/golden{i}", pair_a=pa, pair_dist=pd, accepted=acc)
+
+# ---------------------------------------------------------------- RANSAC
+sac = sac_cases.golden_jobs()
+for want_scores in (False, True):
+    tag = f"scores{int(want_scores)}"
+    for i, name, job in sac:
+        r, = fe.sac_consensus([job], want_scores)
+        record(f"sac_consensus/case{i}_{name}_{tag}", **{k: np.asarray(v) for k, v in r.items()})
+    for (i, name, _), r in zip(sac, fe.sac_consensus([job for _, _, job in sac], want_scores)):
+        record(f"sac_consensus_batch/case{i}_{name}_{tag}", **{k: np.asarray(v) for k, v in r.items()})
+rng = np.random.default_rng(40)
+for model, intr in sorted(BEARING_INTR.items()):
+    for n in (1, 257, 5000):
+        kp = np.stack([rng.uniform(5, 747, n), rng.uniform(5, 475, n), rng.uniform(4, 30, n)], axis=1).astype(np.float32)
+        b, s, ok = fe.bearing_vectors(F.camera(intr, model), kp)
+        record(f"bearing_vectors/model{model}_n{n}", bearing=b, sigma=s, ok=ok)
+fe.close()
+
+json.dump(out, open(args.out, "w"), indent=1, sort_keys=True)
+print(f"{len(out)} cases -> {args.out}: sha256 {hashlib.sha256(open(args.out, 'rb').read()).hexdigest()}")
