@@ -517,9 +517,18 @@ __global__ __launch_bounds__(LIN_THREADS, OCC) void linearize2_kernel(const WinP
         Wm[0 + c] = -hw * V3[0][c];
         Wm[3 + c] = -hw * V3[1][c];
         Wm[6 + c] = -hw * V3[2][c];
-        Wm[9 + c] = d2 * V3[1][c] - d1 * V3[2][c];
-        Wm[12 + c] = d0 * V3[2][c] - d2 * V3[0][c];
-        Wm[15 + c] = d1 * V3[0][c] - d0 * V3[1][c];
+        if constexpr (std::is_same<REAL, float>::value) {
+          // a b - c d leaves the compiler two ways to contract (which product is rounded), and the instantiations did not all
+          // take the same one: W of the UB = 14 kernel differed from the others' in the last bit of some entries
+          // (tests/test_gpu_fp32_linearize.py).  Spelled out, every float instantiation forms the same bits.
+          Wm[9 + c] = fmaf(d2, V3[1][c], -(d1 * V3[2][c]));
+          Wm[12 + c] = fmaf(d0, V3[2][c], -(d2 * V3[0][c]));
+          Wm[15 + c] = fmaf(d1, V3[0][c], -(d0 * V3[1][c]));
+        } else {
+          Wm[9 + c] = d2 * V3[1][c] - d1 * V3[2][c];
+          Wm[12 + c] = d0 * V3[2][c] - d2 * V3[0][c];
+          Wm[15 + c] = d1 * V3[0][c] - d0 * V3[1][c];
+        }
       }
     }
     if (has_pair) {
@@ -539,7 +548,10 @@ __global__ __launch_bounds__(LIN_THREADS, OCC) void linearize2_kernel(const WinP
           if (k == kk) {
             const REAL w0 = ra < 6 ? Wm[3 * (ra < 6 ? ra : 0)] : bp[0], w1 = ra < 6 ? Wm[3 * (ra < 6 ? ra : 0) + 1] : bp[1],
                        w2 = ra < 6 ? Wm[3 * (ra < 6 ? ra : 0) + 2] : bp[2];
-            v = b == 0 ? -hw * w0 : b == 1 ? -hw * w1 : b == 2 ? -hw * w2 : b == 3 ? w1 * d2 - w2 * d1 : b == 4 ? w2 * d0 - w0 * d2 : w0 * d1 - w1 * d0;
+            if constexpr (std::is_same<REAL, float>::value)   // (spelled out like the rows of W above: the same bits in one round and in two)
+              v = b == 0 ? -hw * w0 : b == 1 ? -hw * w1 : b == 2 ? -hw * w2 : b == 3 ? fmaf(w1, d2, -(w2 * d1)) : b == 4 ? fmaf(w2, d0, -(w0 * d2)) : fmaf(w0, d1, -(w1 * d0));
+            else
+              v = b == 0 ? -hw * w0 : b == 1 ? -hw * w1 : b == 2 ? -hw * w2 : b == 3 ? w1 * d2 - w2 * d1 : b == 4 ? w2 * d0 - w0 * d2 : w0 * d1 - w1 * d0;
           }
       return v;
     };

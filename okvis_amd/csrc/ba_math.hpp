@@ -439,9 +439,10 @@ BA_HD bool reproj_linearize(const double* pose, const double* ext, const double*
 
 // ---- reduced-precision linearisation (BASELINE configs[4]: fp32 Jacobian/Hessian build, fp64 solve) ------
 // Same algebra as distort()/reproj_linearize() above with the arithmetic in T (float).  The only fp64
-// operations are the two translations hp_W - r_WS w and p_S - r_SC w_S: subtracting world-scale coordinates
-// in fp32 would lose the digits the residual lives in; everything after the points are expressed relative to
-// the sensor/camera (rotations, projection, distortion, Jacobians) is T.
+// operations are the translation hp_W - r_WS w and the measurement minus the principal point: subtracting
+// world-scale (or pixel-scale) coordinates in fp32 would lose the digits the residual lives in; everything
+// after the point is expressed relative to the sensor (rotations, the second translation p_S - r_SC w_S with
+// |r_SC| ~ 0.1 m, projection, distortion, Jacobians) is T.
 template <class T>
 BA_HD void qrot_t(const T* q, T* R) {
   const T tx = T(2) * q[0], ty = T(2) * q[1], tz = T(2) * q[2];

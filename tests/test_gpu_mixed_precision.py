@@ -48,15 +48,27 @@ def test_switching_precision_rebuilds_the_graph(oracle):
     w = synthetic.small_window(seed=52, K=4, L=40)
     opt = default_options()
     b = solver.WindowBatch([w], options=opt)
+    fused = [b.launch_route()["fused"]]             # Dp = 24: the upload lays the batch out for fused mode, in ITS precision
     a = b.optimize(5)[0]["final_cost"]
     b.set_state(0, w.pose, w.sb, w.lm)
     opt.fp32_linearize = 1
     b.set_options(opt)
+    fused.append(b.launch_route()["fused"])         # the reduction's stage was sized for fp64: separate Schur launch
     c = b.optimize(5)[0]["final_cost"]
     b.set_state(0, w.pose, w.sb, w.lm)
     opt.fp32_linearize = 0
     b.set_options(opt)
+    fused.append(b.launch_route()["fused"])         # back in the layout's own precision
     d = b.optimize(5)[0]["final_cost"]
     b.close()
+    # ... and the other way round: uploaded for fp32, switched to fp64
+    opt.fp32_linearize = 1
+    b = solver.WindowBatch([w], options=opt)
+    fused.append(b.launch_route()["fused"])
+    opt.fp32_linearize = 0
+    b.set_options(opt)
+    fused.append(b.launch_route()["fused"])
+    b.close()
+    assert fused == [1, 0, 1, 1, 0]
     assert a == d                                   # back on the fp64 kernels: bit-identical rerun
     assert a != c and abs(a - c) <= 1e-5 * a        # the fp32 kernels really ran in between
