@@ -28,13 +28,22 @@ size_t small_smem() { return (size_t)std::max<int>(std::max<int>(ImuLds::TOTAL, 
 
 size_t small_eval_smem() { return (size_t)std::max<int>(EvalLds::TOTAL, 2 * MAX_MARG_DIM) * sizeof(double); }
 
+// landmarks per batch of the serial loop of the matrix-core Schur kernel for tiles of trows rows
+int sch2_serial_nlb(int trows) {
+  const int nlb = sch2_nlb(trows, 5120);             // 40 KB of tiles: three workgroups per CU
+  return nlb < 12 ? sch2_nlb(trows, 9216) : nlb;     // wide tiles: 72 KB, two per CU
+}
+
 // Every instantiation a launch plan can name, with the most dynamic LDS a plan gives it (okvis_ba_create allows it that much).
 // It comes first on purpose: the first reference to a kernel template in this file fixes where its code lands in the code object,
 // and this is the order the launches have always named them in (the same code layout, the same timing).
 std::vector<std::pair<const void*, size_t>> plan_kernels() {
   auto f = [](auto k) { return reinterpret_cast<const void*>(k); };
   const size_t dense = std::max(solve_smem(((MAX_D_LDS + 5) / 6) * 6, false), (size_t)SOLVE_LDS_LIMIT), chain = SOLVE_LDS_LIMIT_CHAIN;
-  const size_t wide = (size_t)sch2_tile_doubles(TILE_DIM, sch2_nlb(TILE_DIM, 9216)) * sizeof(double);
+  // (the serial tiles of every pose part make_plan can meet: 66 - 78 rows stage 16 landmarks a batch, 62.7 KB — more than the 12 of a
+  //  96-row tile, 61.6 KB)
+  size_t wide = 0;
+  for (int t = 1; t <= TILE_DIM; ++t) wide = std::max(wide, (size_t)sch2_tile_doubles(t, sch2_serial_nlb(t)) * sizeof(double));
   const size_t d = std::max(lin2_smem(MAX_D, true, false), small_smem()), s = std::max(lin2_smem(MAX_D, true, true), small_smem());
   const size_t ef = std::max(lin_smem(true, true), small_smem()), ed = std::max(lin_smem(true), small_smem());
   const size_t pf = std::max(lin_smem(false, true), small_smem()), pd = std::max(lin_smem(false), small_smem());
@@ -99,8 +108,7 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
   if (M.schur_blocks > 0 && !p.fused) {
     const bool small_tiles = schur_small_tiles(M.Dp);
     if (!M.any_ext && schur_mfma_allowed(o) && (small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_MFMA_LARGE))) {
-      p.nlb = sch2_nlb(p.trows, 5120);                  // 40 KB of tiles: three workgroups per CU
-      if (p.nlb < 12) p.nlb = sch2_nlb(p.trows, 9216);  // wide tiles: 72 KB, two per CU
+      p.nlb = sch2_serial_nlb(p.trows);
       // the small tiles: stages of four landmarks pipelined over a ring of three tile sets (39 KB at 60 rows: three per CU as well);
       // OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES keeps the batch loop above as the referee
       const bool serial = !small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES);

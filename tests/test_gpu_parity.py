@@ -7,7 +7,31 @@ import pytest
 from okvis_amd import synthetic
 from okvis_amd.window import DIST_EQUIDISTANT, DIST_NONE, DIST_RADTAN, DIST_RADTAN8, default_options
 
+from . import schur_cases
+
 pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def schur_ref(oracle):
+    """e_ref of the Schur referee (tests/schur_cases.py): the yardstick of the entrywise checks of REDUCED_S below"""
+    return schur_cases.Referee(oracle)
+
+
+def _entrywise(schur_ref, oracle, w, S, rhs):
+    """REDUCED_S / REDUCED_RHS against the long-double oracle entry by entry, scale and bounds as in
+    tests/test_gpu_schur_referee.py: the whole array and its pose part."""
+    s = schur_cases.Solved(oracle, w, "dl")
+    for a, x in (("REDUCED_S", S), ("REDUCED_RHS", rhs)):
+        for pose_only in (False, True):
+            e = s.deviation(a, x, pose_only)
+            print(f"SCHURREF parity {a} {'pose_part' if pose_only else 'whole'} e_kernel {e:.3e} bound {schur_ref.bound(a, pose_only):.3e}")
+            assert e <= schur_ref.bound(a, pose_only), (a, pose_only, e, schur_ref.bound(a, pose_only))
+
+
+def _route(b, fused, schur_kernel):
+    r = b.launch_route()
+    assert (r["fused"], r["schur_kernel"]) == (fused, schur_kernel), r
 
 
 def _batch(ws, **kw):
@@ -27,9 +51,12 @@ def _close(a, b, tol=1e-9):
 
 @pytest.mark.parametrize("ext", ["fixed", "shared", "perframe"])
 @pytest.mark.parametrize("model", [DIST_RADTAN, DIST_EQUIDISTANT])
-def test_linearisation_arrays_match_oracle(oracle, ext, model):
+def test_linearisation_arrays_match_oracle(oracle, schur_ref, ext, model):
     w = synthetic.small_window(seed=21, K=4, L=60, estimate_extrinsics=ext, cam_model=model)
     b = _batch([w], debug_arrays=1, use_graph=0)
+    # one small window (Dp = 24, 36 and 72 rows) takes the fused linearise + reduce launch: the REDUCED_S lines below exercise NO
+    # Schur kernel, only the reduction inside the linearise kernels; tests/test_gpu_schur_referee.py referees the Schur kernels
+    _route(b, 1, 0)
     o = oracle.OracleWindow(w)
     c_ref = o.linearize()
     b.begin()
@@ -46,6 +73,7 @@ def test_linearisation_arrays_match_oracle(oracle, ext, model):
     assert o.solve(opt.initial_radius, opt) == 0
     S_g, S_r = b.array("REDUCED_S"), o.array("REDUCED_S")
     _close(S_g, S_r, 1e-12)
+    _entrywise(schur_ref, oracle, w, S_g, b.array("REDUCED_RHS"))
     _close(b.array("REDUCED_RHS"), o.array("REDUCED_RHS"), 1e-9)   # (1e-6 until round 5: the pose prior's residual, ba_math.hpp qmul_strict)
     _close(b.array("STEP"), o.array("STEP"), 1e-8)
     b.close()
@@ -202,7 +230,7 @@ def test_long_imu_factors_are_chunked(oracle):
     b.close()
 
 
-def test_marginalisation_prior_evaluation(oracle):
+def test_marginalisation_prior_evaluation(oracle, schur_ref):
     # a synthetic dense prior e = e0 + J dchi over two poses and one speed/bias block
     # (MarginalizationError::EvaluateWithMinimalJacobians, MarginalizationError.cpp:893-946)
     rng = np.random.default_rng(32)
@@ -227,10 +255,12 @@ def test_marginalisation_prior_evaluation(oracle):
         b.begin()
         s = b.finish()[0]
         assert abs(s["final_cost"] - c) <= 1e-11 * c
+        _route(b, 1, 0)     # fused: these lines exercise no Schur kernel (the reduction inside linearize2_kernel)
         b.begin(); b.iterate(1)
         opt = default_options()
         assert o.solve(opt.initial_radius, opt) == 0
         _close(b.array("REDUCED_S"), o.array("REDUCED_S"), 1e-12)
+        _entrywise(schur_ref, oracle, w, b.array("REDUCED_S"), b.array("REDUCED_RHS"))
         _close(b.array("STEP"), o.array("STEP"), 1e-7)
         sg = b.optimize(10)[0]
         sr = o.optimize(10)
@@ -238,17 +268,19 @@ def test_marginalisation_prior_evaluation(oracle):
         b.close()
 
 
-def test_large_reduced_system_uses_hbm_resident_solve(oracle):
+def test_large_reduced_system_uses_hbm_resident_solve(oracle, schur_ref):
     # D = 300 > 174: the block matrix of the reduced system lives in HBM/L2 (solve_kernel<true>)
     w = synthetic.make_window(20, 200, 1.0, seed=33, frame_dt=0.1)
     assert w.reduced_dim() == 300
     b = _batch([w], debug_arrays=1)
     o = oracle.OracleWindow(w)
     o.linearize()
+    _route(b, 0, 1)     # Dp = 120: two Schur tiles, schur_kernel (fp64 FMA) by default
     b.begin(); b.iterate(1)
     opt = default_options()
     assert o.solve(opt.initial_radius, opt) == 0
     _close(b.array("REDUCED_S"), o.array("REDUCED_S"), 1e-12)
+    _entrywise(schur_ref, oracle, w, b.array("REDUCED_S"), b.array("REDUCED_RHS"))
     _close(b.array("STEP"), o.array("STEP"), 1e-7)
     for n in (3, 12):
         sg = _batch([w]).optimize(n)[0]
