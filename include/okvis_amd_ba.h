@@ -567,6 +567,23 @@ int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* sp
  * failure is reported by _end (OKVIS_BA_ERR_NUMERIC). */
 int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* result);
 int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* result);
+/* The same for windows w0 .. w0 + n - 1 of the uploaded batch in one call, specs[i] / results[i] for window w0 + i: what a caller
+ * that keeps many sequences on one GPU does once per frame (the reference's frame loop marginalises right behind the optimisation,
+ * ThreadedKFVio.cpp:736 / :765).  Per window the semantics are exactly those of okvis_ba_marginalize — the same argument checks, the
+ * same meaning of every field (rank and sweeps included), the same numbers bit for bit — but the batch is linearised once, the
+ * landmark elimination and the export are one launch each over the range, the dense tail runs one workgroup per window, and the
+ * call makes one copy to the device, one back and one synchronisation.  All arguments of all n windows are checked before anything
+ * is enqueued: a bad spec, a result with too little room, a window that carries a marg_* prior or a range outside the batch returns
+ * the error of the single call, no result has been touched and the solver is as usable as before.  Windows off the LDS route (see
+ * above) are served inside the same call by the single call's code, after the others; _batch_begin waits for those.
+ * _batch_begin / _batch_end are the two halves as above: between them the solver refuses the same calls (OKVIS_BA_ERR_STATE), the
+ * single-window entries among them, and while a single-window call is pending the batch entries are refused the same way.
+ * _batch_end looks at every result structure before it ends the call (OKVIS_BA_ERR_ARG: nothing is lost, call it again with more
+ * room).  A numeric failure of a window is reported by _batch_end (OKVIS_BA_ERR_NUMERIC, the first one); the other windows'
+ * results are filled. */
+int okvis_ba_marginalize_batch(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results);
+int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results);
+int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* results);
 
 /* ---- multi-GPU driver --------------------------------------------------------------
  * Windows are independent units: window i of a job runs on rank i mod world, one process per GPU, no data-path

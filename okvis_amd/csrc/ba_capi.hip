@@ -117,6 +117,7 @@ int okvis_ba_create(okvis_ba_solver** out, int device) {
   lds(&chol_tiles_window_kernel, CT_SMEM_DOUBLES * 8);
   lds(&marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
   lds(&marg_dense_kernel<MAX_D, MAX_MARG_DIM>, MARG_LDS_DOUBLES_LARGE * 8);
+  lds(&marg_dense_batch_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
 
   if (e != hipSuccess) {
     int code = OKVIS_BA_HIP_ERROR_BASE + (int)e;
@@ -1205,6 +1206,6 @@ int okvis_ba_synchronize(okvis_ba_solver* s) {
 
 #include "capi_standalone.inc"    // okvis_ba_shard, okvis_ba_batch_run, okvis_ba_dense_solve, okvis_ba_reduced_solve
 
-#include "capi_marginalize.inc"   // okvis_ba_marginalize, _begin, _end
+#include "capi_marginalize.inc"   // okvis_ba_marginalize, _begin, _end; okvis_ba_marginalize_batch, _batch_begin, _batch_end
 
 }  // extern "C"

@@ -608,11 +608,10 @@ __device__ bool marg_chol_inverse(double* M, double* X, int n, int n_true, doubl
   return s_okb != 0;
 }
 
+// The dense tail of one window on one workgroup: the body of marg_dense_kernel and of marg_dense_batch_kernel.
 template <int MAXD, int MAXP>
-__global__ __launch_bounds__(MARG_THREADS) void marg_dense_kernel(const WinPtrs* __restrict__ wins, int w, MargArgs a,
-                                                                   int lds_doubles, int stage) {
+__device__ __forceinline__ void marg_dense_body(const WinPtrs& W, const MargArgs& a, int lds_doubles, int stage) {
   extern __shared__ __attribute__((aligned(16))) double marg_lds[];
-  const WinPtrs& W = wins[w];
   const int tid = threadIdx.x;
   const int D = W.D;
   double* H = W.S;     // [D][D]
@@ -922,6 +921,24 @@ __global__ __launch_bounds__(MARG_THREADS) void marg_dense_kernel(const WinPtrs*
     for (int c = 0; c < na; ++c) s += Q[c * na + r] * (s_ba[c] / s_p[c]);
     a.out_e0[r] = s_lam[r] > 0.0 ? -sqrt(1.0 / s_lam[r]) * s : 0.0;
   }
+#undef MSTAMP
+}
+
+template <int MAXD, int MAXP>
+__global__ __launch_bounds__(MARG_THREADS) void marg_dense_kernel(const WinPtrs* __restrict__ wins, int w, MargArgs a,
+                                                                   int lds_doubles, int stage) {
+  marg_dense_body<MAXD, MAXP>(wins[w], a, lds_doubles, stage);
+}
+
+// A batch of windows (okvis_ba_marginalize_batch): workgroup i takes window record wins[i] with the arguments args[i].  The kernel is
+// LDS-bound to one workgroup per CU, so a batch spreads over as many CUs as it has windows.  The argument record is copied once at
+// the top, before anything is stored: a uniform index into read-only memory, so the copy is a handful of scalar loads and the
+// fields live in scalar registers exactly as the kernel arguments of marg_dense_kernel do.
+template <int MAXD, int MAXP>
+__global__ __launch_bounds__(MARG_THREADS) void marg_dense_batch_kernel(const WinPtrs* __restrict__ wins, const MargArgs* __restrict__ args,
+                                                                         int lds_doubles, int stage) {
+  const MargArgs a = args[blockIdx.x];
+  marg_dense_body<MAXD, MAXP>(wins[blockIdx.x], a, lds_doubles, stage);
 }
 
 }  // namespace ba

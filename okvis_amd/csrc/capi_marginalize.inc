@@ -2,19 +2,35 @@
 // MarginalizationError numerics (see include/okvis_amd_ba.h): linearise at the uploaded values, eliminate
 // the landmarks (schur_kernel in marg_mode), export the dense system (solve_kernel final_only = 2), then the
 // dense elimination + eigen-decomposition (marg_dense_kernel).
-int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
-  if (int rc = okvis_ba_marginalize_begin(s, w, spec, res)) return rc;
-  return okvis_ba_marginalize_end(s, res);
-}
+// okvis_ba_marginalize_batch / _batch_begin / _batch_end: the same for a range of windows in one call — one linearisation, one Schur
+// launch, one export launch, one launch of the dense tail with a workgroup per window (marg_dense_batch_kernel), one copy each way.
+namespace {
 
-int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
-  if (s) s->acc_fresh = false;
-  if (!s || !spec || !res) return OKVIS_BA_ERR_ARG;
-  if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+// One window of a marginalisation call: what the argument check found (the kept blocks, in reduced order: pose-type blocks first),
+// the route its dense tail takes and where its pieces lie in the call's scratch block.
+struct MargJob {
+  int w = 0;
+  const okvis_ba_marg_spec* spec = nullptr;
+  std::vector<int> bt, bi, bo;
+  int na = 0, nm = 0, D = 0, pd = 0, pnb = 0;   // kept / eliminated rows, reduced dimension, previous prior
+  bool large = false;      // reduced system assembled in HBM (D > MAX_D_LDS)
+  bool tiles = false;      // kept blocks beyond the single-workgroup LDS paths: the tail on many workgroups (ba_marg_tiles.hpp)
+  bool lds_route = false;  // the single workgroup whose matrices stay in LDS
+  size_t nn = 1, n1 = 1, out_bytes = 0;
+  size_t o_pm = 0, o_sm = 0, o_pt = 0, o_pi = 0, o_po = 0, o_pH = 0, o_pb = 0;   // written by the host
+  size_t o_work = 0, o_S = 0, o_rhs = 0, o_d2 = 0;                               // workspace, exported system
+  size_t o_out = 0, o_info = 0;                                                  // H | J | b0 | e0 | info
+  int mt_nT = 0, mt_ntiles = 0;
+  size_t o_mtT = 0, o_mtZ = 0, o_mtL = 0, o_mtR = 0, o_mtY = 0, o_mtP = 0, o_mtF = 0, o_mtp = 0, o_mtS = 0, o_mtf = 0;
+  size_t out_span() const { return out_bytes + sizeof(int) * (8 + std::max(1, D)); }
+};
+
+// The argument check of okvis_ba_marginalize for window w; on success J holds the kept blocks and the route.
+int marg_check(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, const okvis_ba_marg_result* res, MargJob& J) {
+  if (!spec || !res) return OKVIS_BA_ERR_ARG;
   if (w < 0 || w >= (int)s->wins.size()) return OKVIS_BA_ERR_ARG;
-  HostWin& H = s->wins[w];
+  const HostWin& H = s->wins[w];
   if (H.marg_dim != 0) return OKVIS_BA_ERR_ARG;                    // the previous prior comes in through spec
-  const bool large_window = H.ptrs.Sg != nullptr;   // reduced system assembled in HBM (D > MAX_D_LDS)
   if ((H.n_pose > 0 && !spec->pose_marg) || (H.n_sb > 0 && !spec->sb_marg)) return OKVIS_BA_ERR_ARG;
   const int pd = spec->prior_dim, pnb = spec->prior_nblocks;
   if (pd < 0 || pnb < 0 || pd > MAX_MARG_DIM) return pd > MAX_MARG_DIM ? OKVIS_BA_ERR_UNSUPPORTED : OKVIS_BA_ERR_ARG;
@@ -35,90 +51,283 @@ int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_sp
     }
     if (k == pnb - 1 && expect != pd) return OKVIS_BA_ERR_ARG;
   }
-  // kept blocks, in reduced order (pose-type blocks first)
-  std::vector<int> bt, bi, bo;
-  int na = 0;
+  // kept blocks, in reduced order (pose-type blocks first); rows of the eliminated block
+  J = MargJob{};
+  int na = 0, nm = 0;
   for (int i = 0; i < H.n_pose; ++i)
     if (H.pose_off[i] >= 0 && !spec->pose_marg[i]) {
-      bt.push_back(OKVIS_BA_BLOCK_POSE); bi.push_back(i); bo.push_back(na);
+      J.bt.push_back(OKVIS_BA_BLOCK_POSE); J.bi.push_back(i); J.bo.push_back(na);
       na += 6;
+    } else if (H.pose_off[i] >= 0) {
+      nm += 6;
     }
   for (int i = 0; i < H.n_sb; ++i)
     if (H.sb_off[i] >= 0 && !spec->sb_marg[i]) {
-      bt.push_back(OKVIS_BA_BLOCK_SPEEDBIAS); bi.push_back(i); bo.push_back(na);
+      J.bt.push_back(OKVIS_BA_BLOCK_SPEEDBIAS); J.bi.push_back(i); J.bo.push_back(na);
       na += 9;
+    } else if (H.sb_off[i] >= 0) {
+      nm += 9;
     }
-  if (na > res->capacity_dim || (int)bt.size() > res->capacity_blocks) return OKVIS_BA_ERR_ARG;
+  if (na > res->capacity_dim || (int)J.bt.size() > res->capacity_blocks) return OKVIS_BA_ERR_ARG;
   if (na > 0 && (!res->H || !res->b0 || !res->J || !res->e0 || !res->block_type || !res->block_idx || !res->block_off))
     return OKVIS_BA_ERR_ARG;
-  HIP_TRY(hipSetDevice(s->device));
-
-  // ---- one scratch allocation ----
-  const int D = H.D;
-  Arena A;
-  const size_t o_pm = A.alloc(std::max(1, H.n_pose)), o_sm = A.alloc(std::max(1, H.n_sb));
-  const size_t o_pt = A.alloc(sizeof(int) * std::max(1, pnb)), o_pi = A.alloc(sizeof(int) * std::max(1, pnb)),
-               o_po = A.alloc(sizeof(int) * std::max(1, pnb));
-  const size_t o_pH = A.alloc(8 * std::max<size_t>(1, (size_t)pd * pd)), o_pb = A.alloc(8 * std::max(1, pd));
-  const size_t o_win = A.alloc(sizeof(WinPtrs)), o_opt = A.alloc(sizeof(OptD));
-  const size_t host_part = A.size;   // everything up to here is written by the host: ONE copy
-  const size_t o_work = A.alloc(8 * marg_work_doubles(std::max(1, D)));
-  const size_t o_S = A.alloc(8 * std::max<size_t>(1, (size_t)D * D)), o_rhs = A.alloc(8 * std::max(1, D)),
-               o_d2 = A.alloc(8 * std::max(1, D));
-  // H | J | b0 | e0 | info: contiguous, ONE copy back
-  const size_t nn = std::max<size_t>(1, (size_t)na * na), n1 = std::max(1, na);
-  const size_t out_bytes = 8 * (2 * nn + 2 * n1);
-  const size_t o_out = A.alloc(out_bytes + sizeof(int) * (8 + std::max(1, D)));
-  const size_t o_info = o_out + out_bytes;
-  // kept blocks beyond the single-workgroup LDS paths: the tail on many workgroups (ba_marg_tiles.hpp)
+  J.w = w, J.spec = spec, J.na = na, J.nm = nm, J.D = H.D, J.pd = pd, J.pnb = pnb;
+  J.large = H.ptrs.Sg != nullptr;
   const bool no_tiles = (s->opt.tuning.flags & OKVIS_BA_TUNE_NO_MARG_TILES) != 0;   // (A/B switch)
-  const bool tiles = na > MARG_PC_NMAX && !no_tiles;
-  const int mt_nT = tiles ? (na + CT_TB - 1) / CT_TB : 0, mt_ntiles = mt_nT * (mt_nT + 1) / 2;
-  const size_t o_mtT = A.alloc(8 * (size_t)std::max(1, mt_ntiles) * CT_TILE), o_mtZ = A.alloc(8 * (size_t)std::max(1, mt_ntiles) * CT_TILE),
-               o_mtL = A.alloc(8 * (size_t)std::max(1, mt_nT) * CT_TILE), o_mtR = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
-               o_mtY = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)), o_mtP = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
-               o_mtF = A.alloc(8 * (size_t)std::max(1, mt_ntiles)), o_mtp = A.alloc(8 * (size_t)std::max(1, D)),
-               o_mtS = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
-               o_mtf = A.alloc(sizeof(int) * (size_t)(mt_ntiles + 1 + 2 * mt_nT + 1 + mt_ntiles));
-  s->stage_marg.resize(host_part);   // page-locked: the one upload of this call is a true asynchronous copy
-  unsigned char* const hb = s->stage_marg.data();
-  if (H.n_pose) std::memcpy(&hb[o_pm], spec->pose_marg, H.n_pose);
-  if (H.n_sb) std::memcpy(&hb[o_sm], spec->sb_marg, H.n_sb);
-  if (pd > 0) {
-    std::memcpy(&hb[o_pt], spec->prior_block_type, sizeof(int) * pnb);
-    std::memcpy(&hb[o_pi], spec->prior_block_idx, sizeof(int) * pnb);
-    std::memcpy(&hb[o_po], spec->prior_block_off, sizeof(int) * pnb);
-    std::memcpy(&hb[o_pH], spec->prior_H, 8 * (size_t)pd * pd);
-    std::memcpy(&hb[o_pb], spec->prior_b0, 8 * (size_t)pd);
+  J.tiles = na > MARG_PC_NMAX && !no_tiles;
+  J.lds_route = !J.large && pd <= MARG_SMALL_PRIOR && na <= MARG_PC_NMAX;
+  J.nn = std::max<size_t>(1, (size_t)na * na), J.n1 = std::max(1, na);
+  J.out_bytes = 8 * (2 * J.nn + 2 * J.n1);
+  return OKVIS_BA_OK;
+}
+
+// ---- the pieces of a window in the scratch block, in the order a call lays them out ----
+void marg_place_host(Arena& A, const HostWin& H, MargJob& J) {
+  J.o_pm = A.alloc(std::max(1, H.n_pose)), J.o_sm = A.alloc(std::max(1, H.n_sb));
+  J.o_pt = A.alloc(sizeof(int) * std::max(1, J.pnb)), J.o_pi = A.alloc(sizeof(int) * std::max(1, J.pnb)),
+  J.o_po = A.alloc(sizeof(int) * std::max(1, J.pnb));
+  J.o_pH = A.alloc(8 * std::max<size_t>(1, (size_t)J.pd * J.pd)), J.o_pb = A.alloc(8 * std::max(1, J.pd));
+}
+void marg_place_work(Arena& A, MargJob& J) {
+  const int D = J.D;
+  J.o_work = A.alloc(8 * marg_work_doubles(std::max(1, D)));
+  J.o_S = A.alloc(8 * std::max<size_t>(1, (size_t)D * D)), J.o_rhs = A.alloc(8 * std::max(1, D)), J.o_d2 = A.alloc(8 * std::max(1, D));
+}
+void marg_place_out(Arena& A, MargJob& J) {   // H | J | b0 | e0 | info: contiguous, ONE copy back
+  J.o_out = A.alloc(J.out_span());
+  J.o_info = J.o_out + J.out_bytes;
+}
+void marg_place_tiles(Arena& A, MargJob& J) {
+  const int D = J.D;
+  J.mt_nT = J.tiles ? (J.na + CT_TB - 1) / CT_TB : 0, J.mt_ntiles = J.mt_nT * (J.mt_nT + 1) / 2;
+  const int mt_nT = J.mt_nT, mt_ntiles = J.mt_ntiles;
+  J.o_mtT = A.alloc(8 * (size_t)std::max(1, mt_ntiles) * CT_TILE), J.o_mtZ = A.alloc(8 * (size_t)std::max(1, mt_ntiles) * CT_TILE),
+  J.o_mtL = A.alloc(8 * (size_t)std::max(1, mt_nT) * CT_TILE), J.o_mtR = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
+  J.o_mtY = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)), J.o_mtP = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
+  J.o_mtF = A.alloc(8 * (size_t)std::max(1, mt_ntiles)), J.o_mtp = A.alloc(8 * (size_t)std::max(1, D)),
+  J.o_mtS = A.alloc(8 * (size_t)std::max(1, CT_TB * mt_nT)),
+  J.o_mtf = A.alloc(sizeof(int) * (size_t)(mt_ntiles + 1 + 2 * mt_nT + 1 + mt_ntiles));
+}
+// the host-written pieces of a window (flags, the previous prior) into the staging block
+void marg_fill_host(unsigned char* hb, const HostWin& H, const MargJob& J) {
+  const okvis_ba_marg_spec* spec = J.spec;
+  if (H.n_pose) std::memcpy(&hb[J.o_pm], spec->pose_marg, H.n_pose);
+  if (H.n_sb) std::memcpy(&hb[J.o_sm], spec->sb_marg, H.n_sb);
+  if (J.pd > 0) {
+    std::memcpy(&hb[J.o_pt], spec->prior_block_type, sizeof(int) * J.pnb);
+    std::memcpy(&hb[J.o_pi], spec->prior_block_idx, sizeof(int) * J.pnb);
+    std::memcpy(&hb[J.o_po], spec->prior_block_off, sizeof(int) * J.pnb);
+    std::memcpy(&hb[J.o_pH], spec->prior_H, 8 * (size_t)J.pd * J.pd);
+    std::memcpy(&hb[J.o_pb], spec->prior_b0, 8 * (size_t)J.pd);
   }
-  if (A.size > s->marg_scratch_bytes) {
+}
+// this window's record with the export buffers attached
+WinPtrs marg_win_copy(unsigned char* d, const HostWin& H, const MargJob& J) {
+  WinPtrs P = H.ptrs;
+  P.S = (decltype(P.S))(d + J.o_S);
+  P.rhs = (decltype(P.rhs))(d + J.o_rhs);
+  P.Dp2 = (decltype(P.Dp2))(d + J.o_d2);
+  P.grad = nullptr;
+  return P;
+}
+void marg_args(unsigned char* d, const MargJob& J, MargArgs& ma) {
+  ma.pose_marg = d + J.o_pm;
+  ma.sb_marg = d + J.o_sm;
+  ma.prior_dim = J.pd;
+  ma.prior_nb = J.pd > 0 ? J.pnb : 0;
+  ma.pb_type = reinterpret_cast<const int*>(d + J.o_pt);
+  ma.pb_idx = reinterpret_cast<const int*>(d + J.o_pi);
+  ma.pb_off = reinterpret_cast<const int*>(d + J.o_po);
+  ma.prior_H = reinterpret_cast<const double*>(d + J.o_pH);
+  ma.prior_b0 = reinterpret_cast<const double*>(d + J.o_pb);
+  ma.work = reinterpret_cast<double*>(d + J.o_work);
+  double* outp = reinterpret_cast<double*>(d + J.o_out);
+  ma.out_H = outp;
+  ma.out_J = outp + J.nn;
+  ma.out_b0 = outp + 2 * J.nn;
+  ma.out_e0 = outp + 2 * J.nn + J.n1;
+  ma.out_info = reinterpret_cast<int*>(d + J.o_info);
+  ma.p_out = reinterpret_cast<double*>(d + J.o_mtp);
+}
+int marg_reserve_scratch(okvis_ba_solver* s, size_t bytes) {
+  if (bytes > s->marg_scratch_bytes) {
     if (s->marg_scratch) HIP_TRY(hipFree(s->marg_scratch));
     s->marg_scratch = nullptr;
     s->marg_scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&s->marg_scratch, A.size));
-    s->marg_scratch_bytes = A.size;
+    HIP_TRY(hipMalloc(&s->marg_scratch, bytes));
+    s->marg_scratch_bytes = bytes;
   }
-  unsigned char* d = s->marg_scratch;
-  WinPtrs P = H.ptrs;   // this window with the export buffers attached
-  P.S = (decltype(P.S))(d + o_S);
-  P.rhs = (decltype(P.rhs))(d + o_rhs);
-  P.Dp2 = (decltype(P.Dp2))(d + o_d2);
-  P.grad = nullptr;
-  std::memcpy(&hb[o_win], &P, sizeof(P));
-  const WinPtrs* d_win = reinterpret_cast<const WinPtrs*>(d + o_win);
-  // the marginalisation pass has its own option record in the scratch block (no trust region: one linearisation, no damping);
-  // the launches below read it through s->d_opt, which points there for the duration of this call.  The solver's own record is
-  // never touched, so nothing has to be restored on the device and captured launch graphs stay valid.
+  return OKVIS_BA_OK;
+}
+// The marginalisation pass has its own option record in the scratch block (no trust region: one linearisation, no damping); the
+// launches read it through s->d_opt, which points there for the duration of the call.  The solver's own record is never touched, so
+// nothing has to be restored on the device and captured launch graphs stay valid.
+OptD marg_optd(const okvis_ba_solver* s) {
   OptD od = make_optd(s->opt, (int)s->wins.size());
   od.marg_mode = 1;
   od.dogleg = 0;
+  return od;
+}
+struct MargSwapOptions {
+  okvis_ba_solver* s;
+  OptD* saved;
+  ~MargSwapOptions() { s->d_opt = saved; }
+};
+// the export of one window whose reduced system is assembled in HBM: assembly of the undamped system, then the kernel that completes
+// it (Schur partials, IMU terms) and, because this copy of the window carries an S pointer, writes it out as one full symmetric
+// D x D matrix
+void marg_export_large(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win) {
+  launch_solve_kernel(s, s->plan.tiled, dim3(1), s->stream, d_win, 2, s->d_ctrl + J.w);
+  const int nT = (((J.D + 5) / 6) * 6 + CT_TB - 1) / CT_TB;
+  hipLaunchKernelGGL(large_export_kernel, dim3(nT * (nT + 1) / 2, 1, CT_TILE / CT_THREADS), dim3(CT_THREADS), 0, s->stream, d_win);
+}
+void marg_dense_launch(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs& args, int stage) {
+  if (J.large || J.pd > MARG_SMALL_PRIOR)
+    hipLaunchKernelGGL((marg_dense_kernel<MAX_D, MAX_MARG_DIM>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES_LARGE * 8, s->stream, d_win, 0,
+                       args, MARG_LDS_DOUBLES_LARGE, stage);
+  else
+    hipLaunchKernelGGL((marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8, s->stream, d_win, 0,
+                       args, MARG_LDS_DOUBLES, stage);
+}
+// The dense tail of one window, on the single workgroup or on the tiled route (mt: where that route leaves its verdict).
+void marg_tail(okvis_ba_solver* s, const MargJob& J, unsigned char* d, const WinPtrs* d_win, const MargArgs& ma, MargTiles& mt) {
+  if (!J.tiles) {
+    marg_dense_launch(s, J, d_win, ma, 0);
+    return;
+  }
+  // the single workgroup stops after M and b0; Schur complement, scaling, tiled factorisation (matrix core), L^-1 for the proof
+  // of full rank, J and e0 on many workgroups
+  const int mt_nT = J.mt_nT, mt_ntiles = J.mt_ntiles, na = J.na, nm = J.nm, pd = J.pd;
+  mt.C.nT = mt_nT;
+  mt.C.T = reinterpret_cast<double*>(d + J.o_mtT);
+  mt.C.Linv = reinterpret_cast<double*>(d + J.o_mtL);
+  mt.C.rhs = reinterpret_cast<double*>(d + J.o_mtR);
+  mt.C.y = reinterpret_cast<double*>(d + J.o_mtY);
+  mt.C.flag = reinterpret_cast<int*>(d + J.o_mtf);
+  mt.C.pflag = mt.C.flag + mt_ntiles + 1;
+  mt.Z = reinterpret_cast<double*>(d + J.o_mtZ);
+  mt.fro = reinterpret_cast<double*>(d + J.o_mtF);
+  mt.p2 = reinterpret_cast<double*>(d + J.o_mtP);
+  mt.rowsum = reinterpret_cast<double*>(d + J.o_mtS);
+  mt.ok = mt.C.flag + mt_ntiles + 1 + 2 * mt_nT;
+  mt.zflag = mt.ok + 1;
+  static const bool attrs = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CT_SMEM_DOUBLES * 8);
+    return true;
+  }();
+  (void)attrs;
+  if (pd > 0)
+    hipLaunchKernelGGL(marg_prior_add_kernel, dim3((unsigned)(((size_t)pd * pd + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)),
+                       dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
+  if (nm > 0) {
+    marg_dense_launch(s, J, d_win, ma, 1 | 2 | 4);
+    hipLaunchKernelGGL(marg_M_kernel, dim3((unsigned)(((size_t)na * nm + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0,
+                       s->stream, d_win, ma);
+    hipLaunchKernelGGL(marg_b0_kernel, dim3((unsigned)((na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0, s->stream,
+                       d_win, ma);
+  } else {
+    marg_dense_launch(s, J, d_win, ma, 1 | 2);   // (nothing to eliminate densely: b0 is a gather)
+  }
+  const unsigned nb2 = (unsigned)(((size_t)na * na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS);
+  hipLaunchKernelGGL(marg_schur_kernel, dim3(nb2), dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
+  hipLaunchKernelGGL(marg_tiles_scale_kernel, dim3((CT_TB * mt_nT + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS), dim3(MARG_TILES_THREADS), 0,
+                     s->stream, ma, mt);
+  hipLaunchKernelGGL(marg_tiles_fill_kernel, dim3(mt_ntiles), dim3(MARG_TILES_THREADS), 0, s->stream, ma, mt);
+  hipLaunchKernelGGL(chol_tile_kernel, dim3(mt_ntiles), dim3(CT_THREADS), CT_SMEM_DOUBLES * 8, s->stream, mt.C);
+  hipLaunchKernelGGL(marg_tiles_inverse_kernel, dim3(mt_ntiles), dim3(CT_THREADS), 2 * CT_TB * CT_LD * 8, s->stream, ma, mt);
+  hipLaunchKernelGGL(marg_tiles_out_kernel, dim3(mt_ntiles), dim3(MARG_TILES_THREADS), 0, s->stream, ma, mt);
+  hipLaunchKernelGGL(marg_tiles_rowsum_kernel, dim3((na + MARG_TILES_THREADS / 64 - 1) / (MARG_TILES_THREADS / 64)), dim3(MARG_TILES_THREADS), 0,
+                     s->stream, ma, mt);
+  hipLaunchKernelGGL(marg_tiles_decide_kernel, dim3(1), dim3(MARG_THREADS), 0, s->stream, ma, mt);
+}
+// No proof of full rank on the tiled route (a rank-deficient kept block, a pivot that is not positive): the single workgroup takes
+// over — the previous prior is part of H already, everything else is done again — and goes on to the eigen-decomposition
+void marg_tiles_fallback(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs& ma) {
+  MargArgs again = ma;
+  again.prior_dim = 0;
+  again.prior_nb = 0;
+  marg_dense_launch(s, J, d_win, again, 0);
+  s->marg_tiles_fallbacks++;
+}
+// what is known without the numbers: the blocks the new prior connects
+void marg_report_blocks(const okvis_ba_solver::MargPending::Item& it, okvis_ba_marg_result* res) {
+  res->dim = it.na;
+  res->nblocks = (int)it.bt.size();
+  for (size_t k = 0; k < it.bt.size(); ++k) {
+    res->block_type[k] = it.bt[k];
+    res->block_idx[k] = it.bi[k];
+    res->block_off[k] = it.bo[k];
+  }
+}
+bool marg_result_has_room(const okvis_ba_solver::MargPending::Item& it, const okvis_ba_marg_result* res) {
+  if (it.na > res->capacity_dim || (int)it.bt.size() > res->capacity_blocks) return false;
+  return !(it.na > 0 && (!res->H || !res->b0 || !res->J || !res->e0 || !res->block_type || !res->block_idx || !res->block_off));
+}
+void marg_pending_item(MargJob& J, size_t at, okvis_ba_solver::MargPending::Item& it) {
+  it.w = J.w, it.na = J.na, it.nn = J.nn, it.n1 = J.n1, it.out_bytes = J.out_bytes, it.at = at;
+  it.bt.swap(J.bt), it.bi.swap(J.bi), it.bo.swap(J.bo);
+}
+// The numbers of one window out of the download staging into its result; the accepted-buffer index back to the host's window.
+int marg_hand_over(okvis_ba_solver* s, const okvis_ba_solver::MargPending::Item& it, okvis_ba_marg_result* res) {
+  const int na = it.na;
+  const unsigned char* base = s->stage_dl.data() + it.at;
+  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  std::memcpy(info, base + it.out_bytes, sizeof(info));
+  if (na > 0) {
+    const double* h = reinterpret_cast<const double*>(base);
+    std::memcpy(res->H, h, 8 * (size_t)na * na);
+    std::memcpy(res->J, h + it.nn, 8 * (size_t)na * na);
+    std::memcpy(res->b0, h + 2 * it.nn, 8 * (size_t)na);
+    std::memcpy(res->e0, h + 2 * it.nn + it.n1, 8 * (size_t)na);
+  }
+  if (info[0] != na) return OKVIS_BA_ERR_NUMERIC;
+  res->rank = info[2];
+  res->sweeps[0] = info[3];
+  res->sweeps[1] = info[4];
+  if (debug_word().marg)
+    std::fprintf(stderr, "marginalize: kept dim %d rank %d sweeps %d %d  pivoted-Cholesky bounds: dropped %.3f tau_hi, kept %d tau_hi\n", info[0],
+                 info[2], info[3], info[4], info[6] * 1e-3, info[7]);
+  marg_report_blocks(it, res);
+  s->wins[it.w].acc = info[5] & 1;   // read by marg_dense_kernel after the export: no separate copy + synchronisation
+  return OKVIS_BA_OK;
+}
+
+}  // namespace
+
+int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
+  if (int rc = okvis_ba_marginalize_begin(s, w, spec, res)) return rc;
+  return okvis_ba_marginalize_end(s, res);
+}
+
+int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
+  if (s) s->acc_fresh = false;
+  if (!s || !spec || !res) return OKVIS_BA_ERR_ARG;
+  if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+  MargJob J;
+  if (int rc = marg_check(s, w, spec, res, J)) return rc;
+  const HostWin& H = s->wins[w];
+  HIP_TRY(hipSetDevice(s->device));
+
+  // ---- one scratch allocation ----
+  Arena A;
+  marg_place_host(A, H, J);
+  const size_t o_win = A.alloc(sizeof(WinPtrs)), o_opt = A.alloc(sizeof(OptD));
+  const size_t host_part = A.size;   // everything up to here is written by the host: ONE copy
+  marg_place_work(A, J);
+  marg_place_out(A, J);
+  marg_place_tiles(A, J);
+  s->stage_marg.resize(host_part);   // page-locked: the one upload of this call is a true asynchronous copy
+  unsigned char* const hb = s->stage_marg.data();
+  marg_fill_host(hb, H, J);
+  if (int rc = marg_reserve_scratch(s, A.size)) return rc;
+  unsigned char* d = s->marg_scratch;
+  const WinPtrs P = marg_win_copy(d, H, J);
+  std::memcpy(&hb[o_win], &P, sizeof(P));
+  const WinPtrs* d_win = reinterpret_cast<const WinPtrs*>(d + o_win);
+  const OptD od = marg_optd(s);
   std::memcpy(&hb[o_opt], &od, sizeof(od));
   HIP_TRY(hipMemcpyAsync(d, hb, host_part, hipMemcpyHostToDevice, s->stream));
-  struct SwapOptions {
-    okvis_ba_solver* s;
-    OptD* saved;
-    ~SwapOptions() { s->d_opt = saved; }
-  } swap_options{s, s->d_opt};
+  MargSwapOptions swap_options{s, s->d_opt};
   s->d_opt = reinterpret_cast<OptD*>(d + o_opt);
 
   // ---- linearise + landmark elimination + export ----
@@ -126,101 +335,25 @@ int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_sp
   if (rc != OKVIS_BA_OK) return rc;
   s->begun = false;
   HIP_TRY(launch_schur(s, sub(s->stream, Extent{w, 1, s->plan.one_helpers})));
-  if (large_window) {
-    // assembly of the undamped system, then the kernel that completes it (Schur partials, IMU terms) and, because this copy of
-    // the window carries an S pointer, writes it out as one full symmetric D x D matrix
-    launch_solve_kernel(s, s->plan.tiled, dim3(1), s->stream, d_win, 2, s->d_ctrl + w);
-    const int nT = (((D + 5) / 6) * 6 + CT_TB - 1) / CT_TB;
-    hipLaunchKernelGGL(large_export_kernel, dim3(nT * (nT + 1) / 2, 1, CT_TILE / CT_THREADS), dim3(CT_THREADS), 0, s->stream, d_win);
-  } else
+  if (J.large)
+    marg_export_large(s, J, d_win);
+  else
     launch_solve_kernel(s, s->plan.solve, dim3(1, 1 + s->plan.one_helpers), s->stream, d_win, 2, s->d_ctrl + w);
   HIP_TRY(hipGetLastError());
   MargArgs ma;
-  ma.pose_marg = d + o_pm;
-  ma.sb_marg = d + o_sm;
-  ma.prior_dim = pd;
-  ma.prior_nb = pd > 0 ? pnb : 0;
-  ma.pb_type = reinterpret_cast<const int*>(d + o_pt);
-  ma.pb_idx = reinterpret_cast<const int*>(d + o_pi);
-  ma.pb_off = reinterpret_cast<const int*>(d + o_po);
-  ma.prior_H = reinterpret_cast<const double*>(d + o_pH);
-  ma.prior_b0 = reinterpret_cast<const double*>(d + o_pb);
-  ma.work = reinterpret_cast<double*>(d + o_work);
-  double* outp = reinterpret_cast<double*>(d + o_out);
-  ma.out_H = outp;
-  ma.out_J = outp + nn;
-  ma.out_b0 = outp + 2 * nn;
-  ma.out_e0 = outp + 2 * nn + n1;
-  ma.out_info = reinterpret_cast<int*>(d + o_info);
-  ma.p_out = reinterpret_cast<double*>(d + o_mtp);
-  auto dense = [&](const MargArgs& args, int stage) {
-    if (large_window || pd > MARG_SMALL_PRIOR)
-      hipLaunchKernelGGL((marg_dense_kernel<MAX_D, MAX_MARG_DIM>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES_LARGE * 8, s->stream, d_win, 0,
-                         args, MARG_LDS_DOUBLES_LARGE, stage);
-    else
-      hipLaunchKernelGGL((marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8, s->stream, d_win, 0,
-                         args, MARG_LDS_DOUBLES, stage);
-  };
+  marg_args(d, J, ma);
   MargTiles mt{};
-  if (tiles) {
-    // the single workgroup stops after M and b0; Schur complement, scaling, tiled factorisation (matrix core), L^-1 for the proof
-    // of full rank, J and e0 on many workgroups
-    mt.C.nT = mt_nT;
-    mt.C.T = reinterpret_cast<double*>(d + o_mtT);
-    mt.C.Linv = reinterpret_cast<double*>(d + o_mtL);
-    mt.C.rhs = reinterpret_cast<double*>(d + o_mtR);
-    mt.C.y = reinterpret_cast<double*>(d + o_mtY);
-    mt.C.flag = reinterpret_cast<int*>(d + o_mtf);
-    mt.C.pflag = mt.C.flag + mt_ntiles + 1;
-    mt.Z = reinterpret_cast<double*>(d + o_mtZ);
-    mt.fro = reinterpret_cast<double*>(d + o_mtF);
-    mt.p2 = reinterpret_cast<double*>(d + o_mtP);
-    mt.rowsum = reinterpret_cast<double*>(d + o_mtS);
-    mt.ok = mt.C.flag + mt_ntiles + 1 + 2 * mt_nT;
-    mt.zflag = mt.ok + 1;
-    static const bool attrs = [] {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(chol_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, CT_SMEM_DOUBLES * 8);
-      return true;
-    }();
-    (void)attrs;
-    if (pd > 0)
-      hipLaunchKernelGGL(marg_prior_add_kernel, dim3((unsigned)(((size_t)pd * pd + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)),
-                         dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
-    int nm = 0;   // rows of the eliminated block
-    for (int i = 0; i < H.n_pose; ++i) nm += (H.pose_off[i] >= 0 && spec->pose_marg[i]) ? 6 : 0;
-    for (int i = 0; i < H.n_sb; ++i) nm += (H.sb_off[i] >= 0 && spec->sb_marg[i]) ? 9 : 0;
-    if (nm > 0) {
-      dense(ma, 1 | 2 | 4);
-      hipLaunchKernelGGL(marg_M_kernel, dim3((unsigned)(((size_t)na * nm + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0,
-                         s->stream, d_win, ma);
-      hipLaunchKernelGGL(marg_b0_kernel, dim3((unsigned)((na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0, s->stream,
-                         d_win, ma);
-    } else {
-      dense(ma, 1 | 2);   // (nothing to eliminate densely: b0 is a gather)
-    }
-    const unsigned nb2 = (unsigned)(((size_t)na * na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS);
-    hipLaunchKernelGGL(marg_schur_kernel, dim3(nb2), dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
-    hipLaunchKernelGGL(marg_tiles_scale_kernel, dim3((CT_TB * mt_nT + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS), dim3(MARG_TILES_THREADS), 0,
-                       s->stream, ma, mt);
-    hipLaunchKernelGGL(marg_tiles_fill_kernel, dim3(mt_ntiles), dim3(MARG_TILES_THREADS), 0, s->stream, ma, mt);
-    hipLaunchKernelGGL(chol_tile_kernel, dim3(mt_ntiles), dim3(CT_THREADS), CT_SMEM_DOUBLES * 8, s->stream, mt.C);
-    hipLaunchKernelGGL(marg_tiles_inverse_kernel, dim3(mt_ntiles), dim3(CT_THREADS), 2 * CT_TB * CT_LD * 8, s->stream, ma, mt);
-    hipLaunchKernelGGL(marg_tiles_out_kernel, dim3(mt_ntiles), dim3(MARG_TILES_THREADS), 0, s->stream, ma, mt);
-    hipLaunchKernelGGL(marg_tiles_rowsum_kernel, dim3((na + MARG_TILES_THREADS / 64 - 1) / (MARG_TILES_THREADS / 64)), dim3(MARG_TILES_THREADS), 0,
-                       s->stream, ma, mt);
-    hipLaunchKernelGGL(marg_tiles_decide_kernel, dim3(1), dim3(MARG_THREADS), 0, s->stream, ma, mt);
-  } else {
-    dense(ma, 0);
-  }
+  marg_tail(s, J, d, d_win, ma, mt);
   HIP_TRY(hipGetLastError());
   // H | J | b0 | e0 | info are contiguous on the device: one copy into page-locked staging, one synchronisation
-  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  s->stage_dl.resize(out_bytes + sizeof(info) + sizeof(int));
-  int* const tiles_ok = reinterpret_cast<int*>(s->stage_dl.data() + out_bytes + sizeof(info));
+  const bool tiles = J.tiles;
+  const size_t out_bytes = J.out_bytes, info_bytes = 8 * sizeof(int);
+  s->stage_dl.resize(out_bytes + info_bytes + sizeof(int));
+  int* const tiles_ok = reinterpret_cast<int*>(s->stage_dl.data() + out_bytes + info_bytes);
   // (the tiled route may have to fall back on the single workgroup, which needs this call's arguments: it is waited for here;
   //  the route of the pipeline's sizes only enqueues the copy and leaves the wait to okvis_ba_marginalize_end)
   auto fetch = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), outp, out_bytes + sizeof(info), hipMemcpyDeviceToHost, s->stream);
+    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), ma.out_H, out_bytes + info_bytes, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess && tiles) e = hipMemcpyAsync(tiles_ok, mt.ok, sizeof(int), hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess && tiles) e = hipStreamSynchronize(s->stream);
     return e;
@@ -228,75 +361,166 @@ int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_sp
   *tiles_ok = 1;
   HIP_TRY(fetch());
   if (tiles && !*tiles_ok) {
-    // no proof of full rank (a rank-deficient kept block, a pivot that is not positive): the single workgroup takes over — the
-    // previous prior is part of H already, everything else is done again — and goes on to the eigen-decomposition
-    MargArgs again = ma;
-    again.prior_dim = 0;
-    again.prior_nb = 0;
-    dense(again, 0);
+    marg_tiles_fallback(s, J, d_win, ma);
     HIP_TRY(hipGetLastError());
     *tiles_ok = 1;
-    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), outp, out_bytes + sizeof(info), hipMemcpyDeviceToHost, s->stream);
+    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), ma.out_H, out_bytes + info_bytes, hipMemcpyDeviceToHost, s->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
     HIP_TRY(e);
-    s->marg_tiles_fallbacks++;
-  }
-  // what is known without the numbers: the blocks the new prior connects
-  res->dim = na;
-  res->nblocks = (int)bt.size();
-  for (size_t k = 0; k < bt.size(); ++k) {
-    res->block_type[k] = bt[k];
-    res->block_idx[k] = bi[k];
-    res->block_off[k] = bo[k];
   }
   okvis_ba_solver::MargPending& mp = s->marg_pending;
+  mp.items.assign(1, okvis_ba_solver::MargPending::Item{});
+  marg_pending_item(J, 0, mp.items[0]);
+  marg_report_blocks(mp.items[0], res);
   mp.active = true;
+  mp.batch = false;
   mp.synced = tiles;
-  mp.w = w, mp.na = na, mp.nn = nn, mp.n1 = n1, mp.out_bytes = out_bytes;
-  mp.bt.swap(bt), mp.bi.swap(bi), mp.bo.swap(bo);
   return OKVIS_BA_OK;
 }
 
 int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* res) {
   if (!s || !res) return OKVIS_BA_ERR_ARG;
   okvis_ba_solver::MargPending& mp = s->marg_pending;
-  if (!mp.active) return OKVIS_BA_ERR_STATE;
+  if (!mp.active || mp.batch) return OKVIS_BA_ERR_STATE;   // (a pending batch is ended by okvis_ba_marginalize_batch_end)
   // the result structure is looked at first: a call with too little room changes nothing and can be repeated with more
-  if (mp.na > res->capacity_dim || (int)mp.bt.size() > res->capacity_blocks) return OKVIS_BA_ERR_ARG;
-  if (mp.na > 0 && (!res->H || !res->b0 || !res->J || !res->e0 || !res->block_type || !res->block_idx || !res->block_off)) return OKVIS_BA_ERR_ARG;
+  if (!marg_result_has_room(mp.items[0], res)) return OKVIS_BA_ERR_ARG;
   mp.active = false;   // (whatever happens below, the call is over)
   HIP_TRY(hipSetDevice(s->device));
   if (!mp.synced) HIP_TRY(hipStreamSynchronize(s->stream));
-  const int na = mp.na;
-  const size_t nn = mp.nn, n1 = mp.n1, out_bytes = mp.out_bytes;
-  const std::vector<int>&bt = mp.bt, &bi = mp.bi, &bo = mp.bo;
-  HostWin& H = s->wins[mp.w];
-  if (na > res->capacity_dim || (int)bt.size() > res->capacity_blocks) return OKVIS_BA_ERR_ARG;
-  if (na > 0 && (!res->H || !res->b0 || !res->J || !res->e0 || !res->block_type || !res->block_idx || !res->block_off)) return OKVIS_BA_ERR_ARG;
-  int info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  std::memcpy(info, s->stage_dl.data() + out_bytes, sizeof(info));
-  if (na > 0) {
-    const double* h = reinterpret_cast<const double*>(s->stage_dl.data());
-    std::memcpy(res->H, h, 8 * (size_t)na * na);
-    std::memcpy(res->J, h + nn, 8 * (size_t)na * na);
-    std::memcpy(res->b0, h + 2 * nn, 8 * (size_t)na);
-    std::memcpy(res->e0, h + 2 * nn + n1, 8 * (size_t)na);
+  if (int rc = marg_hand_over(s, mp.items[0], res)) return rc;
+  s->acc_fresh = true;
+  return OKVIS_BA_OK;
+}
+
+// ---- a range of windows in one call ----
+int okvis_ba_marginalize_batch(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
+  if (int rc = okvis_ba_marginalize_batch_begin(s, w0, n, specs, results)) return rc;
+  return okvis_ba_marginalize_batch_end(s, results);
+}
+
+int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
+  if (s) s->acc_fresh = false;
+  if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
+  if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+  if (n <= 0 || w0 < 0 || (int64_t)w0 + n > (int64_t)s->wins.size()) return OKVIS_BA_ERR_ARG;
+  // every window's arguments before anything is enqueued
+  std::vector<MargJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i)
+    if (int rc = marg_check(s, w0 + i, &specs[i], &results[i], jobs[i])) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+
+  // ---- one scratch allocation for the call: what the host writes | workspaces, exported systems | every window's outputs ----
+  Arena A;
+  for (int i = 0; i < n; ++i) marg_place_host(A, s->wins[w0 + i], jobs[i]);
+  const size_t o_wins = A.alloc(sizeof(WinPtrs) * (size_t)n), o_args = A.alloc(sizeof(MargArgs) * (size_t)n), o_opt = A.alloc(sizeof(OptD));
+  const size_t host_part = A.size;   // ONE copy up
+  for (int i = 0; i < n; ++i) {
+    marg_place_work(A, jobs[i]);
+    marg_place_tiles(A, jobs[i]);
   }
-  if (info[0] != na) return OKVIS_BA_ERR_NUMERIC;
-  res->dim = na;
-  res->nblocks = (int)bt.size();
-  res->rank = info[2];
-  res->sweeps[0] = info[3];
-  res->sweeps[1] = info[4];
-  if (debug_word().marg)
-    std::fprintf(stderr, "marginalize: kept dim %d rank %d sweeps %d %d  pivoted-Cholesky bounds: dropped %.3f tau_hi, kept %d tau_hi\n", info[0],
-                 info[2], info[3], info[4], info[6] * 1e-3, info[7]);
-  for (size_t k = 0; k < bt.size(); ++k) {
-    res->block_type[k] = bt[k];
-    res->block_idx[k] = bi[k];
-    res->block_off[k] = bo[k];
+  for (int i = 0; i < n; ++i) marg_place_out(A, jobs[i]);
+  const size_t out_base = jobs[0].o_out, out_total = A.size - out_base;   // ONE copy back
+  s->stage_marg.resize(host_part);
+  unsigned char* const hb = s->stage_marg.data();
+  if (int rc = marg_reserve_scratch(s, A.size)) return rc;
+  unsigned char* d = s->marg_scratch;
+  std::vector<MargArgs> args((size_t)n);
+  bool all_lds = true, any_small = false;
+  for (int i = 0; i < n; ++i) {
+    const HostWin& H = s->wins[w0 + i];
+    marg_fill_host(hb, H, jobs[i]);
+    const WinPtrs P = marg_win_copy(d, H, jobs[i]);
+    std::memcpy(&hb[o_wins + sizeof(WinPtrs) * (size_t)i], &P, sizeof(P));
+    marg_args(d, jobs[i], args[i]);
+    all_lds = all_lds && jobs[i].lds_route;
+    any_small = any_small || !jobs[i].large;
   }
-  H.acc = info[5] & 1;   // read by marg_dense_kernel after the export: no separate copy + synchronisation
+  std::memcpy(&hb[o_args], args.data(), sizeof(MargArgs) * (size_t)n);
+  const WinPtrs* d_wins = reinterpret_cast<const WinPtrs*>(d + o_wins);
+  const MargArgs* d_args = reinterpret_cast<const MargArgs*>(d + o_args);
+  const OptD od = marg_optd(s);
+  std::memcpy(&hb[o_opt], &od, sizeof(od));
+  HIP_TRY(hipMemcpyAsync(d, hb, host_part, hipMemcpyHostToDevice, s->stream));
+  MargSwapOptions swap_options{s, s->d_opt};
+  s->d_opt = reinterpret_cast<OptD*>(d + o_opt);
+
+  // ---- linearise + landmark elimination + export: one launch each for the range ----
+  // Helper workgroups as the plan's own extents have them: up to SOLVE_HELPED_MAX_WINDOWS windows they sum the Schur chunk partials,
+  // longer ranges sum inside the solving workgroup.  Both add a chunk's partials in chunk order starting from zero (ba_solve.hpp),
+  // so a window's exported system has the bits of the single call's either way.
+  int rc = okvis_ba_begin(s);
+  if (rc != OKVIS_BA_OK) return rc;
+  s->begun = false;
+  const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
+  HIP_TRY(launch_schur(s, sub(s->stream, Extent{w0, n, helpers})));
+  // (windows assembled in HBM leave this launch at once: their export follows, window by window)
+  if (any_small && s->plan.solve.k) launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
+  HIP_TRY(hipGetLastError());
+  // ---- the dense tail: a workgroup per window, one launch per run of consecutive windows on the LDS route (a range of the
+  //      pipeline's sizes is one run) ----
+  for (int i = 0; i < n;) {
+    if (!jobs[i].lds_route) {
+      ++i;
+      continue;
+    }
+    int j = i;
+    while (j < n && jobs[j].lds_route) ++j;
+    hipLaunchKernelGGL((marg_dense_batch_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3((unsigned)(j - i)), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8,
+                       s->stream, d_wins + i, d_args + i, MARG_LDS_DOUBLES, 0);
+    i = j;
+  }
+  HIP_TRY(hipGetLastError());
+  s->stage_dl.resize(out_total + sizeof(int));
+  int* const tiles_ok = reinterpret_cast<int*>(s->stage_dl.data() + out_total);
+  // ---- windows off the LDS route, one after the other as okvis_ba_marginalize serves them (HBM workspace, tiled tail and its
+  //      fall-back, which needs the call's arguments: waited for here) ----
+  for (int i = 0; i < n && !all_lds; ++i) {
+    const MargJob& J = jobs[i];
+    if (J.lds_route) continue;
+    if (J.large) marg_export_large(s, J, d_wins + i);
+    MargTiles mt{};
+    marg_tail(s, J, d, d_wins + i, args[i], mt);
+    HIP_TRY(hipGetLastError());
+    if (J.tiles) {
+      *tiles_ok = 1;
+      HIP_TRY(hipMemcpyAsync(tiles_ok, mt.ok, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipStreamSynchronize(s->stream));
+      if (!*tiles_ok) {
+        marg_tiles_fallback(s, J, d_wins + i, args[i]);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+  }
+  // every window's H | J | b0 | e0 | info in one copy; the wait is okvis_ba_marginalize_batch_end's
+  HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
+  okvis_ba_solver::MargPending& mp = s->marg_pending;
+  mp.items.assign((size_t)n, okvis_ba_solver::MargPending::Item{});
+  for (int i = 0; i < n; ++i) {
+    marg_pending_item(jobs[i], jobs[i].o_out - out_base, mp.items[i]);
+    marg_report_blocks(mp.items[i], &results[i]);
+  }
+  mp.active = true;
+  mp.batch = true;
+  mp.synced = false;
+  return OKVIS_BA_OK;
+}
+
+int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* results) {
+  if (!s || !results) return OKVIS_BA_ERR_ARG;
+  okvis_ba_solver::MargPending& mp = s->marg_pending;
+  if (!mp.active || !mp.batch) return OKVIS_BA_ERR_STATE;   // (a pending single call is ended by okvis_ba_marginalize_end)
+  // every result structure is looked at first: a call with too little room anywhere changes nothing and can be repeated with more
+  for (size_t i = 0; i < mp.items.size(); ++i)
+    if (!marg_result_has_room(mp.items[i], &results[i])) return OKVIS_BA_ERR_ARG;
+  mp.active = false;   // (whatever happens below, the call is over)
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  int rc = OKVIS_BA_OK;   // (a numeric failure of one window does not keep the others' numbers back: the first one is reported)
+  for (size_t i = 0; i < mp.items.size(); ++i) {
+    const int r = marg_hand_over(s, mp.items[i], &results[i]);
+    if (rc == OKVIS_BA_OK) rc = r;
+  }
+  if (rc != OKVIS_BA_OK) return rc;
   s->acc_fresh = true;
   return OKVIS_BA_OK;
 }

@@ -166,12 +166,18 @@ struct okvis_ba_solver {
   StageVec stage_marg;           // host-written part of okvis_ba_marginalize's scratch block
   StageVec stage_marg_vals;      // okvis_ba_set_marg_prior_values: the staged J | H0 | e0 span ...
   hipEvent_t ev_marg_vals = nullptr;   // ... and the event behind its copy
-  // okvis_ba_marginalize_begin without its _end yet: what _end needs to hand the numbers over (the kept blocks are known at begin)
+  // okvis_ba_marginalize_begin / okvis_ba_marginalize_batch_begin without its _end yet: what _end needs to hand the numbers over,
+  // one item per window of the call (the kept blocks are known at begin)
   struct MargPending {
     bool active = false, synced = false;
-    int w = 0, na = 0;
-    size_t nn = 0, n1 = 0, out_bytes = 0;
-    std::vector<int> bt, bi, bo;
+    bool batch = false;   // begun by okvis_ba_marginalize_batch_begin: ended by okvis_ba_marginalize_batch_end only, and vice versa
+    struct Item {
+      int w = 0, na = 0;
+      size_t nn = 0, n1 = 0, out_bytes = 0;
+      size_t at = 0;   // where the window's H | J | b0 | e0 | info start in stage_dl
+      std::vector<int> bt, bi, bo;
+    };
+    std::vector<Item> items;
   } marg_pending;
   StageVec stage_pre;            // first preintegrations started at upload (imu_pre_kernel): the staged block and its device copy
   unsigned char* d_pre = nullptr;   // (PRE_MAX_TERMS records)

@@ -201,6 +201,37 @@ class WindowBatch:
         _lib.check(st, "marginalize")
         return out
 
+    def marginalize_batch(self, w0: int, jobs) -> list:
+        """okvis_ba_marginalize_batch on windows w0 .. w0 + len(jobs) - 1: jobs[i] = (pose_marg, sb_marg, prior_or_None) for window
+        w0 + i.  One linearisation, one copy each way and one synchronisation for the whole range; per window the dict (and the
+        bits) ``marginalize`` returns."""
+        self.marginalize_batch_begin(w0, jobs)
+        return self.marginalize_batch_end()
+
+    def marginalize_batch_begin(self, w0: int, jobs):
+        """First half of :meth:`marginalize_batch`: checks every window's arguments and enqueues the work.  Until
+        :meth:`marginalize_batch_end` the solver takes no edits and hands out no results."""
+        from .window import marg_marshal_batch
+        jobs = list(jobs)
+        w0 = int(w0)
+        if w0 < 0 or w0 + len(jobs) > len(self.windows):
+            raise IndexError(f"windows {w0} .. {w0 + len(jobs) - 1} of a batch of {len(self.windows)}")
+        shapes = [(self.windows[w0 + i].n_pose, self.windows[w0 + i].n_sb) for i in range(len(jobs))]
+        specs, results, outs, keep = marg_marshal_batch(shapes, jobs)
+        _lib.check(self._L.okvis_ba_marginalize_batch_begin(self._h, w0, len(jobs), specs, results), "marginalize_batch_begin")
+        self._marg_batch = (results, outs, keep)
+
+    def marginalize_batch_end(self) -> list:
+        """Second half of :meth:`marginalize_batch`: waits and returns the list of results."""
+        if getattr(self, "_marg_batch", None) is None:
+            _lib.check(-2, "marginalize_batch_end")   # OKVIS_BA_ERR_STATE: no batch has been begun
+        results, outs, keep = self._marg_batch
+        self._marg_batch = None
+        _lib.check(self._L.okvis_ba_marginalize_batch_end(self._h, results), "marginalize_batch_end")
+        from .window import marg_unpack
+        del keep
+        return [marg_unpack(results[i], outs[i]) for i in range(len(outs))]
+
     def synchronize(self):
         _lib.check(self._L.okvis_ba_synchronize(self._h), "synchronize")
 

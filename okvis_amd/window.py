@@ -108,9 +108,9 @@ class MargResultC(C.Structure):
                 ("block_off", _ip), ("H", _dp), ("b0", _dp), ("J", _dp), ("e0", _dp), ("sweeps", C.c_int32 * 2)]
 
 
-def marg_call(fn, n_pose, n_sb, pose_marg, sb_marg, prior=None):
-    """Marshal one okvis_ba_marginalize-shaped call ``fn(spec*, result*) -> status``.
-    prior = dict(block_type, block_idx, H, b0) over blocks of the uploaded window, or None."""
+def marg_marshal(n_pose, n_sb, pose_marg, sb_marg, prior, spec, res):
+    """Fill one ``MargSpecC`` / ``MargResultC`` pair (elements of arrays, or single structures) for a window of n_pose / n_sb blocks.
+    Returns (out, keep): the result arrays ``res`` points to, and the arrays ``spec`` points to (alive as long as the call)."""
     pm = np.ascontiguousarray(pose_marg, np.uint8).reshape(-1)
     sm = np.ascontiguousarray(sb_marg, np.uint8).reshape(-1)
     assert pm.size == n_pose and sm.size == n_sb
@@ -118,7 +118,6 @@ def marg_call(fn, n_pose, n_sb, pose_marg, sb_marg, prior=None):
         pm = np.zeros(1, np.uint8)
     if sm.size == 0:
         sm = np.zeros(1, np.uint8)
-    spec = MargSpecC()
     spec.pose_marg = pm.ctypes.data_as(_bp)
     spec.sb_marg = sm.ctypes.data_as(_bp)
     keep = [pm, sm]
@@ -138,20 +137,46 @@ def marg_call(fn, n_pose, n_sb, pose_marg, sb_marg, prior=None):
     capb = max(1, n_pose + n_sb)
     out = dict(block_type=np.zeros(capb, np.int32), block_idx=np.zeros(capb, np.int32), block_off=np.zeros(capb, np.int32),
                H=np.zeros(max(1, cap * cap)), b0=np.zeros(max(1, cap)), J=np.zeros(max(1, cap * cap)), e0=np.zeros(max(1, cap)))
-    res = MargResultC()
     res.capacity_dim, res.capacity_blocks = cap, capb
     for k in ("block_type", "block_idx", "block_off"):
         setattr(res, k, out[k].ctypes.data_as(_ip))
     for k in ("H", "b0", "J", "e0"):
         setattr(res, k, out[k].ctypes.data_as(_dp))
+    return out, keep
+
+
+def marg_unpack(res, out) -> dict:
+    """The dict ``marginalize`` returns, from a filled ``MargResultC`` and the arrays it points to."""
+    n, nb = int(res.dim), int(res.nblocks)
+    return dict(dim=n, rank=int(res.rank), sweeps=(int(res.sweeps[0]), int(res.sweeps[1])), block_type=out["block_type"][:nb].copy(), block_idx=out["block_idx"][:nb].copy(),
+                block_off=out["block_off"][:nb].copy(), H=out["H"][:n * n].reshape(n, n).copy(), b0=out["b0"][:n].copy(),
+                J=out["J"][:n * n].reshape(n, n).copy(), e0=out["e0"][:n].copy())
+
+
+def marg_marshal_batch(shapes, jobs):
+    """Arrays of ``MargSpecC`` / ``MargResultC`` for okvis_ba_marginalize_batch: shapes[i] = (n_pose, n_sb) of the i-th window of the
+    range, jobs[i] = (pose_marg, sb_marg, prior_or_None).  Returns (specs, results, outs, keep)."""
+    assert len(shapes) == len(jobs)
+    n = len(jobs)
+    specs, results = (MargSpecC * max(1, n))(), (MargResultC * max(1, n))()
+    outs, keep = [], []
+    for i, ((n_pose, n_sb), (pm, sm, prior)) in enumerate(zip(shapes, jobs)):
+        out, k = marg_marshal(n_pose, n_sb, pm, sm, prior, specs[i], results[i])
+        outs.append(out)
+        keep.append(k)
+    return specs, results, outs, keep
+
+
+def marg_call(fn, n_pose, n_sb, pose_marg, sb_marg, prior=None):
+    """Marshal one okvis_ba_marginalize-shaped call ``fn(spec*, result*) -> status``.
+    prior = dict(block_type, block_idx, H, b0) over blocks of the uploaded window, or None."""
+    spec, res = MargSpecC(), MargResultC()
+    out, keep = marg_marshal(n_pose, n_sb, pose_marg, sb_marg, prior, spec, res)
     status = fn(C.byref(spec), C.byref(res))
     del keep
     if status != 0:
         return status, None
-    n, nb = int(res.dim), int(res.nblocks)
-    return 0, dict(dim=n, rank=int(res.rank), sweeps=(int(res.sweeps[0]), int(res.sweeps[1])), block_type=out["block_type"][:nb].copy(), block_idx=out["block_idx"][:nb].copy(),
-                   block_off=out["block_off"][:nb].copy(), H=out["H"][:n * n].reshape(n, n).copy(), b0=out["b0"][:n].copy(),
-                   J=out["J"][:n * n].reshape(n, n).copy(), e0=out["e0"][:n].copy())
+    return 0, marg_unpack(res, out)
 
 
 STRATEGY_DOGLEG, STRATEGY_LM = 0, 1

@@ -51,12 +51,50 @@ def run(name, w, poses, sbs, reps=20, with_oracle=True):
             "H_rel_diff": float(err)}
 
 
+def run_batch(n, reps=20):
+    """n pipeline-like sub-windows (seeds 9 .. 9 + n - 1) in one solver: okvis_ba_marginalize_batch over all of them against the loop of
+    n okvis_ba_marginalize calls, `reps` repetitions each.  (A library without the batched entry: the loop alone.)"""
+    ws = [synthetic.small_window(seed=9 + i, K=6, L=150, visibility=0.8) for i in range(n)]
+    jobs = []
+    for w in ws:
+        pm = np.zeros(w.n_pose, np.uint8); sm = np.zeros(w.n_sb, np.uint8)
+        pm[0] = 1; sm[[0, 1]] = 1
+        jobs.append((pm, sm, None))
+    b = solver.WindowBatch(ws, options=default_options())
+    batched = hasattr(b, "marginalize_batch")
+
+    def loop():
+        return [b.marginalize(i, *jobs[i][:2]) for i in range(n)]
+
+    def stats(f):
+        f()                                   # warm-up (module load, allocations)
+        b.synchronize()
+        t = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            f()
+            t.append((time.perf_counter() - t0) * 1e3)
+        return {"median_ms": float(np.median(t)), "min_ms": min(t), "max_ms": max(t)}
+    out = {"case": "batch of pipeline-like sub-windows", "windows": n, "repetitions": reps, "route": b.launch_route(),
+           "loop_of_single_calls": stats(loop)}
+    if batched:
+        out["batched_call"] = stats(lambda: b.marginalize_batch(0, jobs))
+        out["loop_over_batched"] = out["loop_of_single_calls"]["median_ms"] / out["batched_call"]["median_ms"]
+        one, many = loop(), b.marginalize_batch(0, jobs)
+        out["same_bits"] = bool(all(np.array_equal(np.asarray(u[k]), np.asarray(v[k])) for u, v in zip(one, many) for k in u))
+    b.close()
+    return out
+
+
 def main():
     out = [run("pipeline-like", synthetic.small_window(seed=9, K=6, L=150, visibility=0.8), [0], [0, 1]),
            run("configs[1]-sized", synthetic.config_A(), [0, 1], [0, 1, 2, 3, 4], reps=10),
            run("20 frames, D = 300 (HBM workspace)", synthetic.make_window(20, 200, 1.0, seed=33, frame_dt=0.1), [0, 1], [0, 1], reps=5)]
     if "--config-c" in sys.argv:
         out.append(run("configs[2]-sized, D = 750 (HBM workspace)", synthetic.config_C(), [0, 1], [0, 1], reps=3, with_oracle=False))
+    if "--batch" in sys.argv:   # --batch [N]: N windows in one solver, the batched call against the loop of single calls
+        k = sys.argv.index("--batch") + 1
+        out.append(run_batch(int(sys.argv[k]) if k < len(sys.argv) and sys.argv[k].isdigit() else 64))
     print(json.dumps({"marginalize": out, "note": "gpu = whole okvis_ba_marginalize call (linearise + landmark Schur + "
                       "dense elimination + the two decompositions (Cholesky / pivoted Cholesky / Jacobi, see jacobi_sweeps) + download), window already uploaded; "
                       "cpu = oracle restatement on the full dense matrix, 1 thread, not Eigen"}))
