@@ -35,6 +35,14 @@
  * The minimal solvers (GP3P, five-point, two-point rotation), the sampler and the RANSAC loop are OpenGV's and are not here:
  * hypotheses come in from the caller.
  *
+ * and the state propagation that every layer around the backend calls:
+ *
+ *   okvis_fe_imu_propagate       ImuError::propagation with covariance and Jacobian (okvis_ceres/src/ImuError.cpp:287-504), for the
+ *                                chains of calls of many sequences per call: the per-frame call of Estimator::addStates
+ *                                (okvis_ceres/src/Estimator.cpp:145-147) and ThreadedKFVio::frameConsumerLoop
+ *                                (okvis_multisensor_processing/src/ThreadedKFVio.cpp:416-418), and the IMU-rate chain of
+ *                                ThreadedKFVio::imuConsumerLoop through Frontend::propagation (:559-598, Frontend.cpp:274-292)
+ *
  * What stays with the caller is what needs the estimator's book-keeping or image data: which keypoints carry a landmark,
  * addLandmark / addObservation.  G = PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
@@ -253,6 +261,49 @@ typedef struct okvis_fe_sac_job { /* one sample-consensus problem with its hypot
  * correspondences); best and inliers are read off them on the host.  A cam_index entry outside 0..n_cams-1 is OKVIS_BA_ERR_ARG.
  * What is not here: the minimal solvers, the sampler, the loop (see INTEGRATION.md for the recipe). */
 int okvis_fe_sac_consensus(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_job* jobs);
+
+#define OKVIS_FE_IMU_COV 1 /* the 15x15 covariance of the propagated state is wanted */
+#define OKVIS_FE_IMU_JAC 2 /* the 15x15 Jacobian of the propagated state is wanted   */
+
+typedef struct okvis_fe_imu_job { /* one sequence's chain of ImuError::propagation calls */
+  int32_t s_begin, s_count; /* its measurement deque: samples s_begin .. s_begin + s_count - 1 of the pool, stamps strictly ascending */
+  int32_t e_begin, e_count; /* its end times: ends[e_begin .. e_begin + e_count - 1], ascending, e_count >= 1                    */
+  int32_t prm;              /* index into params[]                                                                            */
+  int32_t flags;            /* OKVIS_FE_IMU_COV | OKVIS_FE_IMU_JAC, for every end of the job                                  */
+  int64_t t_start;          /* ns                                                                                             */
+  double T_WS[7];           /* r, q (x, y, z, w) at t_start                                                                   */
+  double sb[9];             /* v, b_g, b_a at t_start                                                                         */
+} okvis_fe_imu_job;
+
+/* ImuError::propagation (okvis_ceres/src/ImuError.cpp:287-504) for many jobs in one launch.  For k = 0 .. e_count - 1 a job makes
+ * the call propagation(deque, params[prm], T, sb, start_k, ends[e_begin + k], cov?, jac?) with start_0 = t_start,
+ * start_k = ends[e_begin + k - 1], and T, sb = the job's for k = 0, the outputs of call k - 1 afterwards: what
+ * ThreadedKFVio::imuConsumerLoop does with T_WS_propagated_ / speedAndBiases_propagated_ through Frontend::propagation
+ * (ThreadedKFVio.cpp:559-598, Frontend.cpp:274-292), once per IMU sample and with the WHOLE deque.  A job with e_count = 1 is the call
+ * of Estimator::addStates (Estimator.cpp:145-147) and of ThreadedKFVio::frameConsumerLoop (:416-418).  Every call is a fresh one
+ * (Delta_q, the integrals and P_delta start from nothing, :306-325); only the state is carried.
+ * The statement is the reference's, operation for operation in IEEE double without fused multiply-adds: the end interpolation before
+ * the start interpolation, which reads the already interpolated second sample (:347-366); leading samples skipped while dt <= 0;
+ * a saturated sample multiplies the step's sigma by 100 (:369-389), and sigma2_v = dt * sigma_a_c(step) * sigma_a_c(parameters)
+ * (:438), so that a saturated accelerometer weighs 100 times where a saturated gyroscope weighs 10^4 times; dalpha_db_g without the
+ * right Jacobian (:412); F_delta from the integrals before the memory shift (:421-431); the loop ends at nexttime == t_end;
+ * g_W = g (0, 0, 6371009).normalized(); cov = T P_delta T^T and the blocks of jac as at :480-502.
+ * Out, at the end's index in the pool: T_WS [n_ends][7] (q normalised as Transformation's constructor does), sb [n_ends][9],
+ * count [n_ends] = the call's return value (the number of integration steps), and for the jobs that ask, cov / jac [n_ends][225]
+ * row-major over (r, alpha, v, b_g, b_a).  Rows of cov / jac that no call wrote are left as they were: those of jobs without the
+ * flag and those of calls that returned early (count = -1, or s_count < 2).
+ *   count = -1  the deque ends before the end time (:301-302): the call's outputs are its inputs, the chain goes on from them
+ *   count =  0  s_count < 2, for every end of the job: Frontend::propagation's early return (Frontend.cpp:281-286); also a call
+ *               with end == start, which goes through the statement with nothing to integrate (q comes back normalised,
+ *               cov = 0, jac = I)
+ * OKVIS_BA_ERR_ARG, before anything is enqueued and with nothing written: NULL context or required pointer (cov / jac are required
+ * once a job sets the flag), negative counts, a sample or end range outside its pool, e_count < 1, prm outside params, unknown flag
+ * bits, stamps of a deque not strictly ascending, ends not ascending or before t_start, and for s_count >= 2 a deque that starts
+ * after t_start (the reference asserts against it, :300).  n_jobs = 0 is valid. */
+int okvis_fe_imu_propagate(okvis_fe_context* ctx, int32_t n_params, const okvis_ba_imu_params* params, int32_t n_samples,
+                           const int64_t* s_t, const double* s_gyr, const double* s_acc, int32_t n_ends, const int64_t* ends,
+                           int32_t n_jobs, const okvis_fe_imu_job* jobs, double* T_WS, double* sb, double* cov, double* jac,
+                           int32_t* count);
 
 #ifdef __cplusplus
 }

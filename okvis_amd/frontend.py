@@ -1,7 +1,7 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
 with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
-best-match search) and whole verified matching steps (the matcher under "Hamming distance and verifyMatch") on the MI355X.  No CPU
-path."""
+best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch") and the IMU state
+propagation with covariance and Jacobian on the MI355X.  No CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -9,15 +9,17 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from .window import ImuParamsC
 
 TRI_VALID, TRI_NOT_PARALLEL, TRI_CAN_INIT, TRI_RANK_DEFICIENT = 1, 2, 4, 8
 PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = range(5)
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
-           "okvis_fe_sac_consensus", "okvis_fe_match_verified"]
+           "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
+IMU_COV, IMU_JAC = 1, 2
 
 
 class CameraC(C.Structure):
@@ -49,6 +51,12 @@ class SacJobC(C.Structure):
                 ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("bearing1", C.c_void_p), ("bearing2", C.c_void_p),
                 ("sigma1", C.c_void_p), ("sigma2", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p),
                 ("inliers", C.c_void_p), ("scores", C.c_void_p)]
+
+
+class ImuJobC(C.Structure):
+    """okvis_fe_imu_job"""
+    _fields_ = [("s_begin", C.c_int32), ("s_count", C.c_int32), ("e_begin", C.c_int32), ("e_count", C.c_int32), ("prm", C.c_int32),
+                ("flags", C.c_int32), ("t_start", C.c_int64), ("T_WS", C.c_double * 7), ("sb", C.c_double * 9)]
 
 
 def camera(intr, model, width=752, height=480) -> CameraC:
@@ -108,6 +116,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_bearing_vectors.argtypes = [vp, cam, i32, vp, vp, vp, vp]
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
+        L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
 
 
 class Frontend:
@@ -273,6 +282,45 @@ class Frontend:
                 r["scores"] = sc
             res.append(r)
         return res
+
+    def imu_propagate(self, params, s_t, s_gyr, s_acc, jobs, ends, fill=np.nan):
+        """ImuError::propagation for the chains of calls of many sequences, in one call.  params: a list of ImuParams (or
+        ImuParamsC); s_t [n] int64 ns, s_gyr / s_acc [n][3]: the pool of samples; ends [m] int64 ns: the pool of end times; jobs:
+        dicts with s_begin, s_count (the job's deque in the sample pool), e_begin, e_count (its ascending end times), t_start,
+        T_WS [7], sb [9], and optionally prm (index into params, default 0) and flags (IMU_COV | IMU_JAC, default 0).
+        -> T_WS [m][7], sb [m][9], count [m] int32 (the steps of each call; -1: deque too short in time, 0: fewer than two
+        samples), cov [m][15][15], jac [m][15][15].  Call k of a job starts at its end k - 1 from the state call k - 1 returned.
+        Rows that no call wrote (ends of no job; cov / jac not asked for or of a call that returned early) hold `fill`."""
+        table = imu_job_table(jobs)
+        prm, s_t, s_gyr, s_acc, ends = imu_pools(params, s_t, s_gyr, s_acc, ends)
+        m = len(ends)
+        T, sb, count = np.full((m, 7), fill), np.full((m, 9), fill), np.full(m, -2, np.int32)
+        cov, jac = np.full((m, 15, 15), fill), np.full((m, 15, 15), fill)
+        self._call("imu_propagate", len(prm), prm, len(s_t), s_t.ctypes.data, s_gyr.ctypes.data, s_acc.ctypes.data, m, ends.ctypes.data,
+                   len(jobs), table, T.ctypes.data, sb.ctypes.data, cov.ctypes.data, jac.ctypes.data, count.ctypes.data)
+        return T, sb, count, cov, jac
+
+
+def imu_pools(params, s_t, s_gyr, s_acc, ends):
+    """the pools of okvis_fe_imu_propagate in the C layout: (ImuParamsC array, s_t, s_gyr, s_acc, ends)"""
+    prm = (ImuParamsC * max(1, len(params)))(*[p if isinstance(p, ImuParamsC) else p.as_c() for p in params])
+    s_t, ends = np.ascontiguousarray(s_t, np.int64).reshape(-1), np.ascontiguousarray(ends, np.int64).reshape(-1)
+    s_gyr, s_acc = _f64(s_gyr).reshape(-1, 3), _f64(s_acc).reshape(-1, 3)
+    if not len(s_t) == len(s_gyr) == len(s_acc):
+        raise ValueError("arrays of different lengths")
+    return prm, s_t, s_gyr, s_acc, ends
+
+
+def imu_job_table(jobs):
+    """-> the okvis_fe_imu_job array (a job holds no pointers: nothing else has to outlive the call)"""
+    table = (ImuJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        t = table[j]
+        t.s_begin, t.s_count, t.e_begin, t.e_count = int(job["s_begin"]), int(job["s_count"]), int(job["e_begin"]), int(job["e_count"])
+        t.prm, t.flags, t.t_start = int(job.get("prm", 0)), int(job.get("flags", 0)), int(job["t_start"])
+        t.T_WS[:] = list(_f64(job["T_WS"], 7))
+        t.sb[:] = list(_f64(job["sb"], 9))
+    return table
 
 
 def sac_job_table(jobs, want_scores=False):
