@@ -176,8 +176,13 @@ typedef struct okvis_ba_window {
  * linked-in backend must not change its behaviour with its host process's environment, so they are fields now, set per solver
  * with okvis_ba_set_options BEFORE the upload they are meant for (okvis_ba_check_window[_lists] take them through their options
  * argument).  All zero = the defaults.  None of them changes what is computed; a different grouping of a sum moves its rounding.
- * The fields are driven against the oracle by tests/test_gpu_switches.py, test_gpu_separate_launch.py, test_gpu_chain_solve.py,
- * test_gpu_structure_paths.py and test_index_build.py.  The library reads ONE environment variable, OKVIS_BA_DEBUG
+ * Which test drives which field against the oracle: NO_EARLY_PREINTEGRATION tests/test_gpu_switches.py and test_gpu_imu_referee.py;
+ * SCHUR_DECIDES test_gpu_separate_launch.py; split_small_min and NO_SMALL_RIDE test_gpu_separate_launch.py and
+ * test_gpu_imu_referee.py (the IMU factor's record on each of their routes); SCHUR_VALU, SCHUR_MFMA_LARGE test_gpu_schur_referee.py;
+ * SCHUR_SERIAL_BATCHES test_gpu_schur_referee.py and test_gpu_schur_pipeline.py; group_lm test_gpu_structure_paths.py and
+ * test_gpu_schur_referee.py; solve_mode test_gpu_chain_solve.py and test_gpu_variants.py; NO_LDL_COMP / LDL_COMP_ALL
+ * test_oracle_referee.py and test_index_build.py; H0_ON_HOST, NO_MARG_TILES test_gpu_marginalization.py; lin2_occupancy
+ * test_gpu_fp32_linearize.py; solve_helpers test_gpu_batch64.py.  stagger_us is driven by no test.  The library reads ONE environment variable, OKVIS_BA_DEBUG
  * (a comma-separated list of print-only diagnostics: "build", "upload", "marg", "arena=<file>"); it never changes a result.
  */
 #define OKVIS_BA_TUNE_SCHUR_DECIDES 0x1u      /* the separate Schur launch takes the trust-region decision itself (rounds 1-4) instead of
@@ -283,8 +288,13 @@ enum okvis_ba_array {
   OKVIS_BA_ARR_IMU_RESIDUAL = 13,/* [n_imu][15] weighted IMU residual at the accepted state             */
   OKVIS_BA_ARR_HPP = 14,        /* [D][D]       un-reduced, un-damped pose/speed-bias Hessian block U (oracle only) */
   OKVIS_BA_ARR_DAMPING = 15,    /* [D]          clamp(diag U) used for the LM damping of the last solve   */
-  OKVIS_BA_ARR_IMU_SB_REF = 16  /* [n_imu][9]   reference speed/bias of each ImuError's preintegration cache */
+  OKVIS_BA_ARR_IMU_SB_REF = 16, /* [n_imu][9]   reference speed/bias of each ImuError's preintegration cache */
+  OKVIS_BA_ARR_IMU_LIN = 17     /* [n_imu][511] each ImuError's linearisation at the accepted state, over the factor's OWN 30 columns
+                                   pose0(6) | sb0(9) | pose1(6) | sb1(9) (fixed states included): H = J^T J, lower triangle packed
+                                   at a(a+1)/2+b, b <= a (465) | g = J^T r (30) | weighted residual r (15) | cost r.r / 2 (1).
+                                   The order in which the device keeps H | g is undone on the host.             */
 };
+#define OKVIS_BA_IMU_LIN_DOUBLES 511
 
 /* ---- lifecycle ----------------------------------------------------------------------------------- */
 int okvis_ba_abi_version(void);

@@ -1075,6 +1075,7 @@ static int locate(okvis_ba_solver* s, int w, int which, const double** ptr, int6
     case 96: *ptr = nullptr; *n = 1; return 0;        // diagnostics: launch slots since okvis_ba_begin
     case OKVIS_BA_ARR_IMU_SB_REF: *ptr = nullptr; *n = 9 * (int64_t)H.n_imu; return 0;
     case OKVIS_BA_ARR_IMU_RESIDUAL: *ptr = nullptr; *n = 15 * (int64_t)H.n_imu; return 0;
+    case OKVIS_BA_ARR_IMU_LIN: *ptr = nullptr; *n = OKVIS_BA_IMU_LIN_DOUBLES * (int64_t)H.n_imu; return 0;
   }
   return OKVIS_BA_ERR_ARG;
 }
@@ -1132,6 +1133,29 @@ int okvis_ba_download(okvis_ba_solver* s, int w, int which, double* out, int64_t
     const HostWin& H = s->wins[w];
     for (int f = 0; f < H.n_imu; ++f)
       HIP_TRY(hipMemcpy(out + 15 * f, H.ptrs.imu_lin[H.acc] + (size_t)f * IMU_LIN_STRIDE + IMU_R, 15 * 8, hipMemcpyDeviceToHost));
+    return OKVIS_BA_OK;
+  }
+  if (which == OKVIS_BA_ARR_IMU_LIN) {
+    // the factors' records of the accepted buffer, H | g brought back from the order the factor workgroup wrote them in
+    // (W.imu_pos, read back from the device: the list the kernel itself used) to the packed triangle over the factor's own columns
+    const HostWin& H = s->wins[w];
+    if (H.n_imu == 0) return OKVIS_BA_OK;
+    static_assert(OKVIS_BA_IMU_LIN_DOUBLES == IMU_COST + 1 && IMU_G == 465 && IMU_R == 495, "H | g | r | cost");
+    std::vector<double> rec((size_t)IMU_LIN_STRIDE * H.n_imu);
+    std::vector<int> pos((size_t)IMU_LIN_STRIDE * H.n_imu);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(rec.data(), H.ptrs.imu_lin[H.acc], rec.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pos.data(), H.ptrs.imu_pos, pos.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int f = 0; f < H.n_imu; ++f) {
+      const double* r = rec.data() + (size_t)IMU_LIN_STRIDE * f;
+      const int* ps = pos.data() + (size_t)IMU_LIN_STRIDE * f;
+      double* o = out + (size_t)OKVIS_BA_IMU_LIN_DOUBLES * f;
+      for (int e = 0; e < IMU_R; ++e) {
+        if (ps[e] < 0 || ps[e] >= IMU_R) return OKVIS_BA_ERR_STATE;
+        o[e] = r[ps[e]];
+      }
+      for (int e = IMU_R; e < OKVIS_BA_IMU_LIN_DOUBLES; ++e) o[e] = r[e];
+    }
     return OKVIS_BA_OK;
   }
   if (n > 0) HIP_TRY(hipMemcpy(out, p, (size_t)n * 8, hipMemcpyDeviceToHost));

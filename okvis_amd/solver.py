@@ -15,8 +15,11 @@ import numpy as np
 from . import _lib
 from .window import LimitsC, OptionsC, SummaryC, Window, WindowC, default_options
 
+# okvis_ba_download's arrays (include/okvis_amd_ba.h, enum okvis_ba_array).  IMU_LIN: [n_imu][511], per IMU factor of the accepted
+# buffer H = J^T J as the packed lower triangle (index a (a + 1) / 2 + b) over the factor's own columns pose0(6) | sb0(9) |
+# pose1(6) | sb1(9) (465), g = J^T r (30), the weighted residual r (15), the cost (1) — reshape(-1, 511).
 ARR = dict(POSE=0, SB=1, LM=2, OBS_RESIDUAL=3, LM_V=4, LM_B=5, LM_HQ=6, PAIR_W=7, REDUCED_S=8,
-           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, DAMPING=15, IMU_SB_REF=16, PROF=99, IMU_REDO_COUNT=98, CTRL=97, SLOTS=96)
+           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, DAMPING=15, IMU_SB_REF=16, IMU_LIN=17, PROF=99, IMU_REDO_COUNT=98, CTRL=97, SLOTS=96)
 _dp = C.POINTER(C.c_double)
 
 
@@ -268,6 +271,7 @@ class WindowBatch:
             None if sb is None else sb.ctypes.data_as(_dp), None if lm is None else lm.ctypes.data_as(_dp)), "set_state")
 
     def array(self, name: str, w: int = 0) -> np.ndarray:
+        """okvis_ba_download of the array ARR[name] of window w, flat (ARR's comment has the layout of IMU_LIN)"""
         n = C.c_int64()
         _lib.check(self._L.okvis_ba_array_size(self._h, w, ARR[name], C.byref(n)), f"array_size {name}")
         out = np.zeros(max(n.value, 0))

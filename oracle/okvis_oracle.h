@@ -51,6 +51,16 @@ int orc_imu_evaluate_at_ref(int n, const int64_t* t, const double* gyr, const do
                             const double pose0[7], const double sb0[9], const double pose1[7],
                             const double sb1[9], double r[15], double* J0, double* J1, double* J2,
                             double* J3);
+/* orc_imu_evaluate_fresh (sb_ref NULL) or the evaluation of a factor whose record was built at sb_ref, with the reference's own
+ * threshold deciding whether it is rebuilt at sb0 (ImuError.cpp:549) — and the preintegration record the evaluation used, in the
+ * order of the product's ImuCacheD: Delta_q (x y z w) | C_integral | C_doubleintegral | acc_integral | acc_doubleintegral |
+ * dalpha_db_g | dv_db_g | dp_db_g | sqrtInfo 15x15 | sb_ref: 289 doubles.  n_steps: integration steps of that record.
+ * Returns the evaluation's count of re-preintegrations. */
+int orc_imu_evaluate_record(int n, const int64_t* t, const double* gyr, const double* acc,
+                            const okvis_ba_imu_params* p, int64_t t0, int64_t t1, const double* sb_ref,
+                            const double pose0[7], const double sb0[9], const double pose1[7],
+                            const double sb1[9], double r[15], double* J0, double* J1, double* J2,
+                            double* J3, double record[289], int* n_steps);
 int orc_imu_propagation(int n, const int64_t* t, const double* gyr, const double* acc,
                         const okvis_ba_imu_params* p, double T_WS[7], double sb[9], int64_t t_start,
                         int64_t t_end, double* cov_15x15, double* jac_15x15);

@@ -1053,6 +1053,44 @@ int orc_imu_evaluate_at_ref(int n, const int64_t* t, const double* gyr, const do
   return c.redoCounter;
 }
 
+int orc_imu_evaluate_record(int n, const int64_t* t, const double* gyr, const double* acc,
+                            const okvis_ba_imu_params* p, int64_t t0, int64_t t1, const double* sb_ref,
+                            const double pose0[7], const double sb0[9], const double pose1[7],
+                            const double sb1[9], double r[15], double* J0, double* J1, double* J2,
+                            double* J3, double record[289], int* n_steps) {
+  In g(gyr, 3 * (size_t)n), a(acc, 3 * (size_t)n);
+  ImuSamples s{n, t, g, a};
+  ImuCache c;
+  ImuParams prm = make_params(p);
+  int steps = -1;
+  if (sb_ref) {  // the object lived through an earlier optimize(): its record was built at sb_ref
+    steps = imu_redo_preintegration(s, prm, t0, t1, In(sb_ref, 9), &c);
+    c.redo = false;
+  }
+  imu_evaluate(s, prm, t0, t1, &c, In(pose0, 7), In(sb0, 9), In(pose1, 7), In(sb1, 9), Out(r, 15), Out(J0, 90), Out(J1, 135),
+               Out(J2, 90), Out(J3, 135));
+  if (c.redoCounter > 0) {  // (the count of the preintegration the record now holds: the same loop at the record's own reference)
+    ImuCache again;
+    steps = imu_redo_preintegration(s, prm, t0, t1, c.sb_ref, &again);
+  }
+  if (n_steps) *n_steps = steps;
+  if (record) {
+    double* o = record;
+    *o++ = (double)c.Delta_q.x, *o++ = (double)c.Delta_q.y, *o++ = (double)c.Delta_q.z, *o++ = (double)c.Delta_q.w;
+    const M3* m3[2] = {&c.C_integral, &c.C_doubleintegral};
+    for (const M3* m : m3)
+      for (int i = 0; i < 9; ++i) *o++ = (double)m->a[i];
+    for (int i = 0; i < 3; ++i) *o++ = (double)c.acc_integral[i];
+    for (int i = 0; i < 3; ++i) *o++ = (double)c.acc_doubleintegral[i];
+    const M3* j3[3] = {&c.dalpha_db_g, &c.dv_db_g, &c.dp_db_g};
+    for (const M3* m : j3)
+      for (int i = 0; i < 9; ++i) *o++ = (double)m->a[i];
+    for (int i = 0; i < 225; ++i) *o++ = (double)c.sqrtInfo.a[i];
+    for (int i = 0; i < 9; ++i) *o++ = (double)c.sb_ref[i];
+  }
+  return c.redoCounter;
+}
+
 int orc_imu_propagation(int n, const int64_t* t, const double* gyr, const double* acc,
                         const okvis_ba_imu_params* p, double T_WS[7], double sb[9], int64_t t_start,
                         int64_t t_end, double* cov, double* jac) {

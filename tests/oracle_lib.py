@@ -21,7 +21,8 @@ _ip = C.POINTER(C.c_int32)
 
 # array ids (include/okvis_amd_ba.h enum okvis_ba_array)
 ARR = dict(POSE=0, SB=1, LM=2, OBS_RESIDUAL=3, LM_V=4, LM_B=5, LM_HQ=6, PAIR_W=7, REDUCED_S=8,
-           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, IMU_SB_REF=16)
+           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, IMU_SB_REF=16,
+           IMU_LIN=17)   # IMU_LIN: GPU only ([n_imu][511]: H 465 packed lower | g 30 | r 15 | cost; tests/imu_cases.py unpacks it)
 
 
 def locked_make(args, lock_dir):
@@ -183,6 +184,23 @@ def imu_evaluate_at_ref(t, gyr, acc, prm, t0, t1, sb_ref, pose0, sb0, pose1, sb1
                                       C.c_int64(int(t0)), C.c_int64(int(t1)), _p(_arr(sb_ref)), _p(_arr(pose0)),
                                       _p(_arr(sb0)), _p(_arr(pose1)), _p(_arr(sb1)), _p(r), *[_p(j) for j in Js])
     return r, Js, n
+
+
+IMU_RECORD_DOUBLES = 289   # orc_imu_evaluate_record: ImuCacheD without its last double (the two flag words)
+
+
+def imu_evaluate_record(t, gyr, acc, prm, t0, t1, pose0, sb0, pose1, sb1, sb_ref=None, extended=False):
+    """orc_imu_evaluate_record of the fp64 build or (extended) the long-double one: r, (J0..J3), the record [289], the record's
+    integration steps, the evaluation's count of re-preintegrations"""
+    L = lib_ld() if extended else lib()
+    t, gyr, acc, pc = _imu_args(t, gyr, acc, prm)
+    r, rec, steps = np.zeros(15), np.zeros(IMU_RECORD_DOUBLES), C.c_int(0)
+    Js = (np.zeros((15, 6)), np.zeros((15, 9)), np.zeros((15, 6)), np.zeros((15, 9)))
+    L.orc_imu_evaluate_record.restype = C.c_int
+    n = L.orc_imu_evaluate_record(int(t.size), t.ctypes.data_as(_lp), _p(gyr), _p(acc), C.byref(pc), C.c_int64(int(t0)),
+                                  C.c_int64(int(t1)), None if sb_ref is None else _p(_arr(sb_ref)), _p(_arr(pose0)), _p(_arr(sb0)),
+                                  _p(_arr(pose1)), _p(_arr(sb1)), _p(r), *[_p(j) for j in Js], _p(rec), C.byref(steps))
+    return r, Js, rec, steps.value, n
 
 
 def imu_propagation(t, gyr, acc, prm, T_WS, sb, t_start, t_end, want_cov=False, want_jac=False):
