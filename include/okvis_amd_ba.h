@@ -595,6 +595,68 @@ int okvis_ba_marginalize_batch(okvis_ba_solver* s, int w0, int n, const okvis_ba
 int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results);
 int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* results);
 
+/* ---- marginal state covariance ------------------------------------------------------------------------
+ * How certain the estimate of a window is.  For window w at the state the solver holds (the uploaded values, or the accepted state
+ * after okvis_ba_optimize), S0 is the reduced system the optimisation's Schur step forms, with lambda = 0:
+ *     S0 = U - sum_l W_l V_l^-1 W_l^T
+ * U is the undamped Hessian over all free pose-type and speed/bias blocks (OKVIS_BA_ARR_HPP: the robustified reprojection terms,
+ * the IMU terms as the solver evaluates them at that state, the pose, speed/bias and relative-pose priors and the window's
+ * marginalisation prior J^T J), V_l and W_l are OKVIS_BA_ARR_LM_V and OKVIS_BA_ARR_PAIR_W, V_l^-1 is the plain 3 x 3 inverse: no
+ * damping, no Jacobi term on V, no pseudo-inverse (this is not the marginalisation pass's landmark rule).  For the caller's list K
+ * of free blocks the result Sigma_K is the rows and columns of K in S0^-1, in the order of the list and in the solver's tangent
+ * coordinates: a pose-type block (r, alpha), a speed/bias block (v, b_g, b_a) — the coordinates of the 15-vector of
+ * ImuError::propagation, so that with `jac` and `cov` of okvis_fe_imu_propagate the covariance of a propagated state is
+ * jac Sigma jac^T + cov for K = (pose, speed/bias) of the state the chain starts from.
+ * The reference computes nothing of the kind (ThreadedKFVio.cpp:579-584 drops the propagation's covariance and Jacobian,
+ * okvis::Estimator has no covariance getter).
+ *
+ * okvis_ba_state_covariance serves windows w0 .. w0 + n - 1 in one call, specs[i] / results[i] for window w0 + i: the batch is
+ * linearised once, the landmark elimination, the export of S0 and the selected inverse (cov_kernel, one workgroup per window: Jacobi
+ * scaling d_i = 1 / sqrt(S0_ii) rounded to a power of two — exact —, Cholesky in LDS, the selected columns refined twice with a
+ * residual in twice the working precision; fp64) are one launch each over the range; one copy up, one copy back, one
+ * synchronisation per call.  A window's numbers have the same bits alone or in any range, and a column's do not depend on what
+ * else the list names or in which order.
+ *  - result->S0 (NULL, or room for [D][D] doubles, D = okvis_ba_reduced_dim) is the referee's tap: the very matrix the kernel
+ *    inverted, as a full symmetric matrix in the reduced ordering.
+ *  - result->min_pivot is the smallest pivot (squared diagonal entry of the Cholesky factor) of the Jacobi-scaled factorisation,
+ *    a conditioning diagnostic: between 0.5 and 2 for a diagonal matrix, towards 0 as the scaled matrix approaches singularity.  (After a failure:
+ *    the pivot that was not positive, or 0 when a diagonal entry of S0 was not.)
+ *  - result->info = 1 when a diagonal entry of S0 is not positive, or a pivot is not positive, or a result is not finite: that
+ *    window's cov is then filled with NaN, the other windows of the call are filled as usual, and the call returns
+ *    OKVIS_BA_ERR_NUMERIC.  info = 0 otherwise.
+ *  - OKVIS_BA_ERR_ARG, with nothing enqueued and no result touched: NULL arguments (result->cov among them), a range outside the
+ *    batch, n_blocks < 1, an unknown block type or an index out of range, a fixed block, a block named twice, a total dimension
+ *    above OKVIS_BA_COV_MAX_DIM, a capacity below dim^2.
+ *  - OKVIS_BA_ERR_UNSUPPORTED, checked the same way: a window whose reduced dimension exceeds OKVIS_BA_COV_MAX_WINDOW_DIM.  Only
+ *    windows the LDS solver handles are served; the HBM-resident and tiled routes of larger windows are out of scope.
+ *  - OKVIS_BA_ERR_STATE: before okvis_ba_upload, between okvis_ba_begin and okvis_ba_finish, and while a marginalisation is pending
+ *    (okvis_ba_marginalize_begin / _batch_begin without its _end).
+ *  - The call leaves the solver unchanged: pose, speed/bias and landmark values, okvis_ba_fetch_results,
+ *    okvis_ba_fetch_imu_caches and every later okvis_ba_optimize are bit for bit what they are without the call (the control
+ *    records and the IMU terms' preintegration records are kept in front of the launches and put back behind them; the call runs
+ *    under an option record of its own, so the solver's options and its captured launch graphs stay valid). */
+#define OKVIS_BA_COV_MAX_WINDOW_DIM 174  /* the LDS solver's limit (MAX_D_LDS) */
+#define OKVIS_BA_COV_MAX_DIM 30          /* rows of one result: two full states */
+
+typedef struct okvis_ba_cov_spec {
+  int32_t n_blocks;
+  const int32_t *block_type, *block_idx;  /* OKVIS_BA_BLOCK_*; index in the window */
+} okvis_ba_cov_spec;
+
+typedef struct okvis_ba_cov_result {
+  int32_t capacity;   /* in: doubles available in cov */
+  int32_t dim, info;  /* out */
+  double min_pivot;   /* out */
+  double* cov;        /* [dim][dim] row-major */
+  double* S0;         /* NULL or [D][D] */
+} okvis_ba_cov_result;
+
+int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n,
+                              const okvis_ba_cov_spec* specs, okvis_ba_cov_result* results);
+/* Measurement hook (HIP events of the last successful okvis_ba_state_covariance): the time of its assembly launches (keep, linearise,
+ * landmark elimination, export) and of cov_kernel.  OKVIS_BA_ERR_STATE before the first call. */
+int okvis_ba_last_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* kernel_ms);
+
 /* ---- multi-GPU driver --------------------------------------------------------------
  * Windows are independent units: window i of a job runs on rank i mod world, one process per GPU, no data-path
  * collective.  The only exchange is ONE all-gather of these fixed-size records after all windows finished (RCCL over

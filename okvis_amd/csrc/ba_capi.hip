@@ -17,6 +17,7 @@
 #include "../../include/okvis_amd_ba.h"
 #include "ba_imu.hpp"
 #include "ba_chol_tiles.hpp"
+#include "ba_cov.hpp"
 #include "ba_linearize.hpp"
 #include "ba_linearize2.hpp"
 #include "ba_schur2.hpp"
@@ -33,7 +34,7 @@ using namespace ba;
 #include "capi_index_build.inc"   // batch_layout, build_batch, build_window and its helpers (the index build)
 #include "capi_launch.inc"        // LDS sizes, the launch plan (make_plan) and the launches, sub-batch fork / join
 // below: life cycle, options, upload / patch, state, begin / iterate / finish, queries and downloads, measurement hooks; then
-// capi_standalone.inc and capi_marginalize.inc
+// capi_standalone.inc, capi_marginalize.inc and capi_covariance.inc
 
 // =====================================================================================================
 extern "C" {
@@ -118,6 +119,7 @@ int okvis_ba_create(okvis_ba_solver** out, int device) {
   lds(&marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
   lds(&marg_dense_kernel<MAX_D, MAX_MARG_DIM>, MARG_LDS_DOUBLES_LARGE * 8);
   lds(&marg_dense_batch_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
+  lds(&cov_kernel, cov_lds_bytes(MAX_D_LDS));
 
   if (e != hipSuccess) {
     int code = OKVIS_BA_HIP_ERROR_BASE + (int)e;
@@ -139,6 +141,8 @@ int okvis_ba_destroy(okvis_ba_solver* s) {
   if (s->h_ctrl_stage) (void)hipHostFree(s->h_ctrl_stage);
   if (s->d_ctrl_stage) (void)hipFree(s->d_ctrl_stage);
   if (s->marg_scratch) (void)hipFree(s->marg_scratch);
+  for (auto ev : s->ev_cov)
+    if (ev) (void)hipEventDestroy(ev);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
@@ -1231,5 +1235,7 @@ int okvis_ba_synchronize(okvis_ba_solver* s) {
 #include "capi_standalone.inc"    // okvis_ba_shard, okvis_ba_batch_run, okvis_ba_dense_solve, okvis_ba_reduced_solve
 
 #include "capi_marginalize.inc"   // okvis_ba_marginalize, _begin, _end; okvis_ba_marginalize_batch, _batch_begin, _batch_end
+
+#include "capi_covariance.inc"    // okvis_ba_state_covariance
 
 }  // extern "C"

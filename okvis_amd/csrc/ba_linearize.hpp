@@ -85,7 +85,8 @@ __device__ __forceinline__ void fused_reduce_fast(const WinPtrs& W, const OptD& 
     const double* r = s_lmres + 16 * lt;
     double v[6] = {r[0], r[1], r[2], r[3], r[4], r[5]}, vi[6];
     if (opt.marg_mode) {
-      pinv3sym_precond(v, vi);
+      if (opt.marg_mode == 2) inv3sym(v, vi);   // (state covariance: the plain inverse)
+      else pinv3sym_precond(v, vi);
     } else {
       double sc[3] = {1.0, 1.0, 1.0};
       if (opt.dogleg) {

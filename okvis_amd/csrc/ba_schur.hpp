@@ -103,7 +103,8 @@ __device__ __forceinline__ void schur_reduce_chunk(const WinPtrs& W, const OptD&
     const double b0 = bb[3 * (size_t)l], b1 = bb[3 * (size_t)l + 1], b2 = bb[3 * (size_t)l + 2];
     double vi[6];
     if (opt.marg_mode) {
-      pinv3sym_precond(v, vi);   // MarginalizationError::marginalizeOut landmark path (no damping)
+      if (opt.marg_mode == 2) inv3sym(v, vi);   // (state covariance: the plain inverse)
+      else pinv3sym_precond(v, vi);   // MarginalizationError::marginalizeOut landmark path (no damping)
     } else {
       double sc[3] = {1.0, 1.0, 1.0};
       if (opt.dogleg) {

@@ -367,7 +367,8 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     const double b0 = lb3[0], b1 = lb3[1], b2 = lb3[2];
     double vi[6];
     if (opt.marg_mode) {
-      pinv3sym_precond(v, vi);   // MarginalizationError::marginalizeOut landmark path (no damping)
+      if (opt.marg_mode == 2) inv3sym(v, vi);   // (state covariance: the plain inverse)
+      else pinv3sym_precond(v, vi);   // MarginalizationError::marginalizeOut landmark path (no damping)
     } else {
       double sc[3] = {1.0, 1.0, 1.0};
       if (opt.dogleg) {

@@ -103,7 +103,8 @@ struct OptD {
   double initial_radius, max_radius, min_radius, min_lm_diag2, max_lm_diag2;  // diag2 bounds: Ceres clamps the SQUARED column norm
   double min_relative_decrease, function_tolerance, gradient_tolerance, parameter_tolerance;
   int gauss_newton;  // 1 = accept every step, keep the radius fixed
-  int marg_mode;     // 1 = marginalisation pass: no damping, landmark blocks eliminated with the preconditioned pseudo-inverse
+  int marg_mode;     // 1 = marginalisation pass: no damping, landmark blocks eliminated with the preconditioned pseudo-inverse;
+                     // 2 = state covariance (okvis_ba_state_covariance): no damping, landmark blocks eliminated with the plain inverse
   int dogleg;        // 1 = Ceres' DOGLEG strategy (the reference's configuration), 0 = Levenberg-Marquardt
   int jacobi_scaling;
   int max_invalid;   // max_num_consecutive_invalid_steps

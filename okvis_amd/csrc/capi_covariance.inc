@@ -1,0 +1,188 @@
+// Part of ba_capi.hip, inside its extern "C" block, behind capi_marginalize.inc (whose scratch block, window-record copy and
+// option-record swap it uses).  okvis_ba_state_covariance (DESIGN.md "State covariance"): for a range of windows, linearise at the
+// state the solver holds, eliminate the landmarks with the plain inverse and no damping (OptD::marg_mode = 2), export the reduced
+// system S0 (solve_kernel final_only = 2) — one launch each, as okvis_ba_marginalize_batch does — then cov_kernel (ba_cov.hpp), one
+// workgroup per window.  One copy up, one copy back, one synchronisation.  The control records and the IMU terms' preintegration
+// records are kept in front of the launches and put back behind them (cov_keep_kernel): the solver is left as it was.
+namespace {
+
+struct CovJob {
+  int D = 0, k = 0;
+  int rows[COV_MAX_DIM];   // the selected reduced rows, ascending (what the kernel works on)
+  int at[COV_MAX_DIM];     // row p of the result (list order) = row at[p] of the kernel's
+  size_t o_S = 0, o_rhs = 0, o_d2 = 0, o_out = 0;
+};
+
+int cov_check(const okvis_ba_solver* s, int w, const okvis_ba_cov_spec* spec, const okvis_ba_cov_result* res, CovJob& J) {
+  const HostWin& H = s->wins[w];
+  if (spec->n_blocks < 1 || !spec->block_type || !spec->block_idx || !res->cov) return OKVIS_BA_ERR_ARG;
+  int k = 0, list[COV_MAX_DIM];
+  for (int b = 0; b < spec->n_blocks; ++b) {
+    const int t = spec->block_type[b], idx = spec->block_idx[b];
+    if (t != OKVIS_BA_BLOCK_POSE && t != OKVIS_BA_BLOCK_SPEEDBIAS) return OKVIS_BA_ERR_ARG;
+    const bool pose = t == OKVIS_BA_BLOCK_POSE;
+    if (idx < 0 || idx >= (pose ? H.n_pose : H.n_sb)) return OKVIS_BA_ERR_ARG;
+    const int off = pose ? H.pose_off[idx] : H.sb_off[idx], rows = pose ? 6 : 9;
+    if (off < 0) return OKVIS_BA_ERR_ARG;   // a fixed block
+    for (int q = 0; q < k; ++q)
+      if (list[q] == off) return OKVIS_BA_ERR_ARG;   // named twice
+    if (k + rows > COV_MAX_DIM) return OKVIS_BA_ERR_ARG;
+    for (int r = 0; r < rows; ++r) list[k++] = off + r;
+  }
+  if ((int64_t)res->capacity < (int64_t)k * k) return OKVIS_BA_ERR_ARG;
+  if (H.D > OKVIS_BA_COV_MAX_WINDOW_DIM || H.ptrs.Sg != nullptr) return OKVIS_BA_ERR_UNSUPPORTED;
+  J = CovJob{};
+  J.D = H.D, J.k = k;
+  std::copy(list, list + k, J.rows);
+  std::sort(J.rows, J.rows + k);
+  for (int p = 0; p < k; ++p) J.at[p] = (int)(std::lower_bound(J.rows, J.rows + k, list[p]) - J.rows);
+  return OKVIS_BA_OK;
+}
+
+}  // namespace
+
+int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_cov_spec* specs, okvis_ba_cov_result* results) {
+  if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
+  if (!s->uploaded || s->begun || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+  if (n <= 0 || w0 < 0 || (int64_t)w0 + n > (int64_t)s->wins.size()) return OKVIS_BA_ERR_ARG;
+  // every window's arguments before anything is enqueued
+  std::vector<CovJob> jobs((size_t)n);
+  for (int i = 0; i < n; ++i)
+    if (int rc = cov_check(s, w0 + i, &specs[i], &results[i], jobs[i])) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const int nw = (int)s->wins.size();
+  if (!s->acc_fresh) {   // (okvis_ba_begin starts from the accepted buffers as the host knows them)
+    std::vector<Ctrl> cs;
+    if (int rc = fetch_ctrl(s, cs)) return rc;
+    for (int i = 0; i < nw; ++i) s->wins[i].acc = cs[i].acc & 1;
+    s->acc_fresh = true;
+  }
+
+  // ---- one scratch allocation: what the host writes | what is kept of the solver | workspaces | every window's outputs ----
+  Arena A;
+  const size_t o_wins = A.alloc(sizeof(WinPtrs) * (size_t)n), o_args = A.alloc(sizeof(CovArgs) * (size_t)n), o_opt = A.alloc(sizeof(OptD));
+  const size_t host_part = A.size;   // ONE copy up
+  const int max_imu = std::max(0, s->max.imu);
+  const size_t keep_stride = COV_KEEP_CTRL + 2 * (size_t)max_imu * (sizeof(ImuCacheD) / 8);
+  const size_t o_keep = A.alloc(8 * keep_stride * (size_t)nw);
+  int Dmax = 1;
+  for (int i = 0; i < n; ++i) {
+    CovJob& J = jobs[i];
+    J.o_rhs = A.alloc(8 * (size_t)J.D), J.o_d2 = A.alloc(8 * (size_t)J.D);
+    if (!results[i].S0) J.o_S = A.alloc(8 * (size_t)J.D * J.D);
+    Dmax = std::max(Dmax, J.D);
+  }
+  size_t out_base = 0;
+  for (int i = 0; i < n; ++i) {   // cov | min_pivot | info | the tap, if asked for: contiguous over the range, ONE copy back
+    CovJob& J = jobs[i];
+    J.o_out = A.alloc(8 * cov_out_doubles(J.k));
+    if (i == 0) out_base = J.o_out;
+    if (results[i].S0) J.o_S = A.alloc(8 * (size_t)J.D * J.D);
+  }
+  const size_t out_total = A.size - out_base;
+  s->stage_marg.resize(host_part);
+  unsigned char* const hb = s->stage_marg.data();
+  if (int rc = marg_reserve_scratch(s, A.size)) return rc;
+  unsigned char* d = s->marg_scratch;
+  for (int i = 0; i < n; ++i) {
+    const CovJob& J = jobs[i];
+    WinPtrs P = s->wins[w0 + i].ptrs;   // this window's record with the export buffers attached
+    P.S = (decltype(P.S))(d + J.o_S);
+    P.rhs = (decltype(P.rhs))(d + J.o_rhs);
+    P.Dp2 = (decltype(P.Dp2))(d + J.o_d2);
+    P.grad = nullptr;
+    std::memcpy(&hb[o_wins + sizeof(WinPtrs) * (size_t)i], &P, sizeof(P));
+    CovArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.S = reinterpret_cast<const double*>(d + J.o_S);
+    a.out = reinterpret_cast<double*>(d + J.o_out);
+    a.D = J.D, a.k = J.k;
+    std::copy(J.rows, J.rows + J.k, a.rows);
+    std::memcpy(&hb[o_args + sizeof(CovArgs) * (size_t)i], &a, sizeof(a));
+  }
+  OptD od = marg_optd(s);
+  od.marg_mode = 2;
+  std::memcpy(&hb[o_opt], &od, sizeof(od));
+  const WinPtrs* d_wins = reinterpret_cast<const WinPtrs*>(d + o_wins);
+  double* d_keep = reinterpret_cast<double*>(d + o_keep);
+  for (auto& ev : s->ev_cov)
+    if (!ev) HIP_TRY(hipEventCreate(&ev));
+  HIP_TRY(hipMemcpyAsync(d, hb, host_part, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipEventRecord(s->ev_cov[0], s->stream));
+  hipLaunchKernelGGL(cov_keep_kernel, dim3((unsigned)nw), dim3(256), 0, s->stream, s->d_wins, d_keep, keep_stride, max_imu, 0);
+  HIP_TRY(hipGetLastError());
+
+  // ---- linearise + landmark elimination + export: one launch each for the range (helper workgroups as the plan's own extents
+  //      have them; either way a chunk's partials are added in chunk order, so a window's system has the same bits) ----
+  struct HostFlags {
+    okvis_ba_solver* s;
+    bool evaluated, res_staged, acc_fresh, mirror_fresh;
+    long long slots;
+    ~HostFlags() {
+      s->begun = false;
+      s->evaluated = evaluated, s->res_staged = res_staged, s->acc_fresh = acc_fresh, s->mirror_fresh = mirror_fresh, s->slots = slots;
+    }
+  } host_flags{s, s->evaluated, s->res_staged, s->acc_fresh, s->mirror_fresh, s->slots};
+  int rc;
+  {
+    MargSwapOptions swap_options{s, s->d_opt};
+    s->d_opt = reinterpret_cast<OptD*>(d + o_opt);
+    rc = okvis_ba_begin(s);
+    if (rc == OKVIS_BA_OK) {
+      const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
+      hipError_t e = launch_schur(s, sub(s->stream, Extent{w0, n, helpers}));
+      if (e == hipSuccess) {
+        launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
+        e = hipGetLastError();
+      }
+      if (e != hipSuccess) {
+        s->last_hip_error = (int)e;
+        rc = OKVIS_BA_HIP_ERROR_BASE + (int)e;
+      }
+    }
+  }
+  if (rc == OKVIS_BA_OK) {
+    (void)hipEventRecord(s->ev_cov[1], s->stream);
+    hipLaunchKernelGGL(cov_kernel, dim3((unsigned)n), dim3(COV_THREADS), cov_lds_bytes(Dmax), s->stream, reinterpret_cast<const CovArgs*>(d + o_args));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(s->ev_cov[2], s->stream);
+    if (e != hipSuccess) {
+      s->last_hip_error = (int)e;
+      rc = OKVIS_BA_HIP_ERROR_BASE + (int)e;
+    }
+  }
+  // (whatever happened above: what was kept goes back)
+  hipLaunchKernelGGL(cov_keep_kernel, dim3((unsigned)nw), dim3(256), 0, s->stream, s->d_wins, d_keep, keep_stride, max_imu, 1);
+  HIP_TRY(hipGetLastError());
+  if (rc != OKVIS_BA_OK) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return rc;
+  }
+  s->stage_dl.resize(out_total);
+  HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  for (int i = 0; i < n; ++i) {
+    const CovJob& J = jobs[i];
+    okvis_ba_cov_result& R = results[i];
+    const int k = J.k;
+    const double* o = reinterpret_cast<const double*>(s->stage_dl.data() + (J.o_out - out_base));
+    for (int a = 0; a < k; ++a)
+      for (int b = 0; b < k; ++b) R.cov[a * k + b] = o[J.at[a] * k + J.at[b]];
+    R.dim = k;
+    R.min_pivot = o[k * k];
+    std::memcpy(&R.info, o + k * k + 1, sizeof(int32_t));
+    if (R.S0) std::memcpy(R.S0, s->stage_dl.data() + (J.o_S - out_base), 8 * (size_t)J.D * J.D);
+    if (R.info != 0) rc = OKVIS_BA_ERR_NUMERIC;
+  }
+  return rc;
+}
+
+int okvis_ba_last_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* kernel_ms) {
+  if (!s || !assembly_ms || !kernel_ms) return OKVIS_BA_ERR_ARG;
+  if (!s->ev_cov[2]) return OKVIS_BA_ERR_STATE;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipEventSynchronize(s->ev_cov[2]));
+  HIP_TRY(hipEventElapsedTime(assembly_ms, s->ev_cov[0], s->ev_cov[1]));
+  HIP_TRY(hipEventElapsedTime(kernel_ms, s->ev_cov[1], s->ev_cov[2]));
+  return OKVIS_BA_OK;
+}

@@ -301,6 +301,19 @@ class Frontend:
         return T, sb, count, cov, jac
 
 
+def propagated_covariance(P0, jac, cov):
+    """Covariance of a propagated state: ``jac @ P0 @ jac.T + cov``.  jac, cov [..., 15, 15]: what ``Frontend.imu_propagate``
+    returns for a call (flags IMU_COV | IMU_JAC); P0 [15, 15]: the covariance of the state the chain starts from, e.g.
+    ``WindowBatch.state_covariance()`` of the (pose, speed/bias) blocks of that state.  All three are over the 15-vector of
+    ImuError::propagation, which is the solver's tangent space of (pose, speed/bias): rows 0-2 position r, 3-5 orientation alpha,
+    6-8 velocity v, 9-11 gyroscope bias b_g, 12-14 accelerometer bias b_a.  For call k > 0 of a job, jac is with respect to the
+    state call k - 1 returned: chain the calls (P_k = propagated_covariance(P_{k-1}, jac_k, cov_k))."""
+    P0, jac, cov = np.asarray(P0, np.float64), np.asarray(jac, np.float64), np.asarray(cov, np.float64)
+    if P0.shape[-2:] != (15, 15) or jac.shape[-2:] != (15, 15) or cov.shape[-2:] != (15, 15):
+        raise ValueError("P0, jac and cov are [..., 15, 15]")
+    return jac @ P0 @ np.swapaxes(jac, -1, -2) + cov
+
+
 def imu_pools(params, s_t, s_gyr, s_acc, ends):
     """the pools of okvis_fe_imu_propagate in the C layout: (ImuParamsC array, s_t, s_gyr, s_acc, ends)"""
     prm = (ImuParamsC * max(1, len(params)))(*[p if isinstance(p, ImuParamsC) else p.as_c() for p in params])

@@ -235,6 +235,62 @@ class WindowBatch:
         del keep
         return [marg_unpack(results[i], outs[i]) for i in range(len(outs))]
 
+    def newest_state_blocks(self, w: int) -> list:
+        """[(BLOCK_POSE, i), (BLOCK_SPEEDBIAS, j)]: the pose and speed/bias blocks window w's last IMU term ends at."""
+        from .window import BLOCK_POSE, BLOCK_SPEEDBIAS
+        W = self.windows[w]
+        if W.n_imu < 1:
+            raise ValueError(f"window {w} has no IMU term: name the blocks")
+        return [(BLOCK_POSE, int(np.asarray(W.imu_pose1).reshape(-1)[-1])), (BLOCK_SPEEDBIAS, int(np.asarray(W.imu_sb1).reshape(-1)[-1]))]
+
+    def state_covariance(self, blocks=None, w0: int = 0, n: int | None = None, want_S0: bool = False) -> list:
+        """okvis_ba_state_covariance on windows w0 .. w0 + n - 1 (default: to the end of the batch): the marginal covariance of the
+        listed free blocks at the state the solver holds, rows and columns of the inverse of the undamped reduced system, in the
+        order of the list and in the solver's tangent coordinates (pose-type block: r, alpha; speed/bias block: v, b_g, b_a).
+        blocks: one list of (block type, index) pairs (``window.BLOCK_POSE`` / ``BLOCK_SPEEDBIAS``) for every window, a list of
+        such lists (one per window), or None = the newest state: the pose and speed/bias blocks the window's last IMU term ends
+        at (ValueError for a window without IMU terms).  One linearisation, one copy each way and one synchronisation for the
+        range; the solver is left as it was.  Per window a dict cov [dim][dim], dim, info, min_pivot and, with want_S0, S0 [D][D]
+        (the matrix the kernel inverted).  A window with info = 1 has cov filled with NaN; the call then raises BackendError
+        (OKVIS_BA_ERR_NUMERIC) whose ``results`` attribute holds the list."""
+        from .window import cov_marshal_batch
+        w0 = int(w0)
+        n = len(self.windows) - w0 if n is None else int(n)
+        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
+            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        if blocks is None:
+            sels = [self.newest_state_blocks(w0 + i) for i in range(n)]
+        elif len(blocks) > 0 and isinstance(blocks[0], (list, tuple)) and len(blocks[0]) > 0 and isinstance(blocks[0][0], (list, tuple)):
+            sels = [list(b) for b in blocks]
+            if len(sels) != n:
+                raise ValueError(f"{len(sels)} selections for {n} windows")
+        else:
+            sels = [list(blocks)] * n
+        dims = [self.reduced_dim(w0 + i) for i in range(n)] if want_S0 else [0] * n
+        specs, results, outs, keep = cov_marshal_batch(sels, dims, want_S0)
+        st = self._L.okvis_ba_state_covariance(self._h, w0, n, specs, results)
+        del keep
+        if st not in (0, -5):
+            _lib.check(st, "state_covariance")
+        res = []
+        for i in range(n):
+            k = int(results[i].dim)
+            r = dict(cov=outs[i]["cov"][:k * k].reshape(k, k).copy(), dim=k, info=int(results[i].info), min_pivot=float(results[i].min_pivot))
+            if want_S0:
+                r["S0"] = outs[i]["S0"].reshape(dims[i], dims[i]).copy()
+            res.append(r)
+        if st != 0:
+            err = _lib.BackendError(st, "state_covariance")
+            err.results = res
+            raise err
+        return res
+
+    def last_covariance_ms(self) -> dict:
+        """okvis_ba_last_covariance_ms: HIP-event times of the last state_covariance call's assembly launches and of cov_kernel"""
+        a, k = C.c_float(), C.c_float()
+        _lib.check(self._L.okvis_ba_last_covariance_ms(self._h, C.byref(a), C.byref(k)), "last_covariance_ms")
+        return dict(assembly=a.value, kernel=k.value)
+
     def synchronize(self):
         _lib.check(self._L.okvis_ba_synchronize(self._h), "synchronize")
 

@@ -108,6 +108,43 @@ class MargResultC(C.Structure):
                 ("block_off", _ip), ("H", _dp), ("b0", _dp), ("J", _dp), ("e0", _dp), ("sweeps", C.c_int32 * 2)]
 
 
+class CovSpecC(C.Structure):
+    """ctypes image of ``okvis_ba_cov_spec``."""
+    _fields_ = [("n_blocks", C.c_int32), ("block_type", _ip), ("block_idx", _ip)]
+
+
+class CovResultC(C.Structure):
+    """ctypes image of ``okvis_ba_cov_result``."""
+    _fields_ = [("capacity", C.c_int32), ("dim", C.c_int32), ("info", C.c_int32), ("min_pivot", C.c_double),
+                ("cov", _dp), ("S0", _dp)]
+
+
+BLOCK_POSE, BLOCK_SPEEDBIAS = 0, 1   # OKVIS_BA_BLOCK_*
+COV_MAX_WINDOW_DIM, COV_MAX_DIM = 174, 30   # OKVIS_BA_COV_MAX_WINDOW_DIM, OKVIS_BA_COV_MAX_DIM
+
+
+def cov_marshal_batch(selections, dims, want_S0):
+    """Arrays of ``CovSpecC`` / ``CovResultC`` for okvis_ba_state_covariance: selections[i] = [(block type, index), ...] of the
+    i-th window of the range, dims[i] its reduced dimension (the size of the tap).  Returns (specs, results, outs, keep)."""
+    n = len(selections)
+    specs, results = (CovSpecC * max(1, n))(), (CovResultC * max(1, n))()
+    outs, keep = [], []
+    for i, sel in enumerate(selections):
+        bt = np.ascontiguousarray([b[0] for b in sel], np.int32).reshape(-1)
+        bi = np.ascontiguousarray([b[1] for b in sel], np.int32).reshape(-1)
+        specs[i].n_blocks = len(sel)
+        specs[i].block_type, specs[i].block_idx = bt.ctypes.data_as(_ip), bi.ctypes.data_as(_ip)
+        cap = int(np.where(bt == BLOCK_POSE, 6, 9).sum()) if len(sel) else 1
+        out = dict(cov=np.zeros(max(1, cap * cap)), S0=np.zeros(max(1, dims[i] * dims[i])) if want_S0 else None)
+        results[i].capacity = cap * cap
+        results[i].cov = out["cov"].ctypes.data_as(_dp)
+        if want_S0:
+            results[i].S0 = out["S0"].ctypes.data_as(_dp)
+        outs.append(out)
+        keep.append((bt, bi))
+    return specs, results, outs, keep
+
+
 def marg_marshal(n_pose, n_sb, pose_marg, sb_marg, prior, spec, res):
     """Fill one ``MargSpecC`` / ``MargResultC`` pair (elements of arrays, or single structures) for a window of n_pose / n_sb blocks.
     Returns (out, keep): the result arrays ``res`` points to, and the arrays ``spec`` points to (alive as long as the call)."""
