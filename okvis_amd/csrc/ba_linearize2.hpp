@@ -50,6 +50,16 @@ struct Lin2Cfg {
 };
 static_assert(LIN2_PIECES * 3 * 2 <= LIN2_PIECES * 16, "phase A's pair sums alias the record area");
 static_assert(LIN2_PIECES <= LIN_THREADS, "one pair per work-item");
+// a * b + c in one rounding, in the precision of the arguments (where the contraction must not be left to the compiler)
+__device__ __forceinline__ float fma_real(float a, float b, float c) { return fmaf(a, b, c); }
+__device__ __forceinline__ double fma_real(double a, double b, double c) { return fma(a, b, c); }
+// a * b - c * d with both products rounded before the subtraction (no contraction)
+template <class T>
+__device__ __forceinline__ T sub_of_rounded_products(T a, T b, T c, T d) {
+#pragma clang fp contract(off)
+  const T p = a * b, q = c * d;
+  return p - q;
+}
 
 // value of lane + 1 of the same DPP row (0 for the last lane of a row): row_shl:1
 template <class T>
@@ -517,18 +527,19 @@ __global__ __launch_bounds__(LIN_THREADS, OCC) void linearize2_kernel(const WinP
         Wm[0 + c] = -hw * V3[0][c];
         Wm[3 + c] = -hw * V3[1][c];
         Wm[6 + c] = -hw * V3[2][c];
-        if constexpr (std::is_same<REAL, float>::value) {
-          // a b - c d leaves the compiler two ways to contract (which product is rounded), and the instantiations did not all
-          // take the same one: W of the UB = 14 kernel differed from the others' in the last bit of some entries
-          // (tests/test_gpu_fp32_linearize.py).  Spelled out, every float instantiation forms the same bits.
-          Wm[9 + c] = fmaf(d2, V3[1][c], -(d1 * V3[2][c]));
-          Wm[12 + c] = fmaf(d0, V3[2][c], -(d2 * V3[0][c]));
-          Wm[15 + c] = fmaf(d1, V3[0][c], -(d0 * V3[1][c]));
-        } else {
-          Wm[9 + c] = d2 * V3[1][c] - d1 * V3[2][c];
-          Wm[12 + c] = d0 * V3[2][c] - d2 * V3[0][c];
-          Wm[15 + c] = d1 * V3[0][c] - d0 * V3[1][c];
-        }
+        // a b - c d leaves the compiler ways to contract (which product is rounded, or both), and the instantiations did not all
+        // take the same one.  In float W of the UB = 14 kernel differed from the others' in the last bit of some entries
+        // (tests/test_gpu_fp32_linearize.py); in double W[3][0] and W[5][2] of the fused kernels differed from the unfused
+        // ones' (tests/test_gpu_fp64_linearize.py).  Spelled out, every instantiation of one precision forms the same bits.
+        // In double: c d rounded first, as both families had it in seven of the nine entries; W[3][0] as the fused kernels
+        // formed it (a b rounded first), W[5][2] as the unfused ones did (both products rounded), so that each family's
+        // results move in one entry only (profiles/fp64_referee_notes.md, "Route pairs").
+        constexpr bool dbl = std::is_same<REAL, double>::value;
+        if (dbl && c == 0) Wm[9 + c] = fma_real(-d1, V3[2][c], d2 * V3[1][c]);
+        else Wm[9 + c] = fma_real(d2, V3[1][c], -(d1 * V3[2][c]));
+        Wm[12 + c] = fma_real(d0, V3[2][c], -(d2 * V3[0][c]));
+        if (dbl && c == 2) Wm[15 + c] = sub_of_rounded_products(d1, V3[0][c], d0, V3[1][c]);
+        else Wm[15 + c] = fma_real(d1, V3[0][c], -(d0 * V3[1][c]));
       }
     }
     if (has_pair) {

@@ -25,6 +25,22 @@ observations — is float32.  All constants are wrapped in the dtype, so no oper
     "equi_dpoly"   the 9 k4 theta^8 term of the equidistant d(theta_d)/d(theta) dropped
     "je_sign"      one sign in the rotation columns of J_ext
     "jp_trans"     the translation columns of J_pose (= -w J_lm) taken with +
+
+and, in the sums of window_arrays (what a kernel's reduction or robustifier could get wrong; tests/test_fp64_statement_host.py):
+
+    "drop_last_obs"  the last observation of one landmark (drop_landmark(w)) left out of V, b, H_l and W
+    "rho_prime"      the Jacobians scaled by rho' instead of sqrt(rho')
+    "hq_robust"      LM_HQ summed from the robustified Jacobians
+
+dtype = numpy.longdouble (x87 extended) evaluates everything, the two differences included, in long double; keep_dtype = True then
+returns the arrays unrounded.  scales = True adds, per refereed array, what every entry is a sum OF in absolute values (as
+tests/schur_statement.py does for S): sum over the observations of a_A^T a_B for LM_V, LM_HQ, LM_B, PAIR_W, and
+s (|z - c| + f a_d) for OBS_RESIDUAL.  The plain |J| and |f d| do not serve as a_J and a_d: the Jacobian entries and the projected
+point are themselves cancelling sums (products of rotations with differences), and with the plain scale the deviation of two
+correct fp64 evaluations reaches 1.7e-13 = 1500 x 2^-53 (OBS_RESIDUAL of a point that projects next to the principal point,
+PAIR_W).  So the scale is built from the operands' magnitudes, the way the Schur statement does: a_Jl = |Jh| |C_CS| |C_SW|, a_Jp =
+|Jh| |C_CS| [ |C_SW| |w| , |C_SW| |[dW]x| ], a_Je = |Jh| [ |C_CS| |w| , |C_CS| |[eS]x| ] with |Jh| = s f |Jd| |du|, and a_d = |d| +
+|Jd| (a_pC_xy + |u| a_pC_z) / |z| with a_pC = |C_CS| (|C_SW| |dW| + |r_SC w|).  An entry whose scale is zero had nothing added.
 """
 from __future__ import annotations
 
@@ -32,6 +48,7 @@ import numpy as np
 
 DIST_NONE, DIST_RADTAN, DIST_EQUIDISTANT, DIST_RADTAN8 = 0, 1, 2, 3
 MUTATIONS = ("radtan_j00", "equi_dpoly", "je_sign", "jp_trans")
+SUM_MUTATIONS = ("drop_last_obs", "rho_prime", "hq_robust")
 ARRAYS = ("OBS_RESIDUAL", "LM_V", "LM_B", "LM_HQ", "PAIR_W")
 MIN_DEPTH = 0.2      # ReprojectionError.hpp:147
 
@@ -112,15 +129,17 @@ def observation(pose, ext, lm, intr, model, uv, sqrt_w, dtype=np.float64, mutate
     residual; an undefined projection gives zeros throughout, an invalid one (depth below 0.2 m) keeps r and zeroes the
     Jacobians.  depth = p_C.z / w (inf when |w| <= 1e-8: the reference then makes no validity check)."""
     T = dtype
+    D = np.result_type(T, np.float64).type                            # the two differences: float64, or long double under it
     pose, ext, lm, intr = (np.asarray(a, np.float64) for a in (pose, ext, lm, intr))
     out = dict(r=np.zeros(2, T), Jp=np.zeros((2, 6), T), Jl=np.zeros((2, 3), T), Je=np.zeros((2, 6), T), depth=np.inf,
-               defined=False, valid=False)
+               defined=False, valid=False, r_scale=np.zeros(2, T), aJp=np.zeros((2, 6), T), aJl=np.zeros((2, 3), T),
+               aJe=np.zeros((2, 6), T))
     with np.errstate(all="ignore"):
         C_WS, C_SC = _rotation(pose[3:7], T), _rotation(ext[3:7], T)
         C_SW, C_CS = C_WS.T, C_SC.T
         w64 = lm[3]
         w = T(w64)
-        dW = (lm[:3] - pose[:3] * w64).astype(T)                      # float64 difference, then rounded
+        dW = (lm[:3].astype(D) - pose[:3].astype(D) * D(w64)).astype(T)   # float64 difference, then rounded
         pS = C_SW @ dW
         eS = pS - ext[:3].astype(T) * w                               # sensor-scale coordinates: dtype arithmetic
         pC = C_CS @ eS
@@ -137,7 +156,14 @@ def observation(pose, ext, lm, intr, model, uv, sqrt_w, dtype=np.float64, mutate
         out["defined"] = True
         d0, d1, Jd = dist
         fu, fv, s = T(intr[0]), T(intr[1]), T(sqrt_w)
-        out["r"] = np.array([s * (T(uv[0] - intr[2]) - fu * d0), s * (T(uv[1] - intr[3]) - fv * d1)], dtype=T)
+        z0, z1 = T(D(uv[0]) - D(intr[2])), T(D(uv[1]) - D(intr[3]))
+        out["r"] = np.array([s * (z0 - fu * d0), s * (z1 - fv * d1)], dtype=T)
+        # the operands' magnitudes: p_C is a sum of rotated differences, a_pC = |C_CS| (|C_SW| |dW| + |r_SC w|) what it is a sum of;
+        # u = p / z and the distortion hand that on to first order: a_d = |d| + |Jd| (a_pC_xy + |u| a_pC_z) / |z|
+        a_pC = np.abs(C_CS) @ (np.abs(C_SW) @ np.abs(dW) + np.abs(ext[:3].astype(T) * w))
+        a_u = np.array([a_pC[0] + abs(u0) * a_pC[2], a_pC[1] + abs(u1) * a_pC[2]], dtype=T) / abs(z)
+        a_d = np.array([abs(d0), abs(d1)], dtype=T) + np.abs(Jd) @ a_u
+        out["r_scale"] = np.array([s * (abs(z0) + fu * a_d[0]), s * (abs(z1) + fv * a_d[1])], dtype=T)
         if abs(w64) > 1.0e-8 and pC[2] / w < T(MIN_DEPTH):
             return out
         out["valid"] = True
@@ -148,6 +174,11 @@ def observation(pose, ext, lm, intr, model, uv, sqrt_w, dtype=np.float64, mutate
         out["Jl"] = -(Jh_CS @ C_SW)
         out["Jp"] = Jh_CS @ np.concatenate([C_SW * w, -(C_SW @ _cross(dW, T))], axis=1)
         out["Je"] = Jh @ np.concatenate([C_CS * w, -(C_CS @ _cross(eS, T))], axis=1)
+        aJh = np.abs(np.array([[s * fu], [s * fv]], dtype=T)) * (np.abs(Jd) @ np.abs(du))
+        aJh_CS = aJh @ np.abs(C_CS)
+        out["aJl"] = aJh_CS @ np.abs(C_SW)
+        out["aJp"] = aJh_CS @ np.concatenate([np.abs(C_SW) * abs(w), np.abs(C_SW) @ np.abs(_cross(dW, T))], axis=1)
+        out["aJe"] = aJh @ np.concatenate([np.abs(C_CS) * abs(w), np.abs(C_CS) @ np.abs(_cross(eS, T))], axis=1)
         if mutate == "jp_trans":
             out["Jp"][:, :3] = -out["Jp"][:, :3]
         if mutate == "je_sign":
@@ -170,11 +201,18 @@ def pairs(w):
 _UT = ((0, 0), (0, 1), (0, 2), (1, 1), (1, 2), (2, 2))
 
 
-def window_arrays(w, dtype=np.float64, mutate=None):
+def drop_landmark(w):
+    """the landmark whose last observation the mutation "drop_last_obs" leaves out: the last one with two observations or more"""
+    counts = np.bincount(np.asarray(w.obs_lm), minlength=w.n_lm)
+    return int(np.flatnonzero(counts >= 2)[-1])
+
+
+def window_arrays(w, dtype=np.float64, mutate=None, keep_dtype=False, scales=False, reverse=False):
     """The landmark-side linearisation of a whole Window at its state, laid out as WindowBatch.array / OracleWindow.array return
     them (flat float64): OBS_RESIDUAL [n_obs, 2], LM_V [n_lm, 6] and LM_HQ [n_lm, 6] (upper triangles; LM_HQ without the robust
     weight: Map::getLhs), LM_B [n_lm, 3], PAIR_W [n_pair, 6, 3]; plus `pairs`, and per observation `depth`, `defined`, `valid`.
-    Sums run in observation order in `dtype`; the Cauchy corrector scales r and J by sqrt(rho') (Ceres Corrector, rho'' <= 0)."""
+    Sums run in observation order (reverse: last observation first) in `dtype`; the Cauchy corrector scales r and J by sqrt(rho')
+    (Ceres Corrector, rho'' <= 0).  keep_dtype: the arrays stay in `dtype`; scales: a dict `scale` of float64 arrays, see above."""
     T = dtype
     pose = np.asarray(w.pose, np.float64).reshape(-1, 7)
     lm = np.asarray(w.lm, np.float64).reshape(-1, 4)
@@ -187,32 +225,61 @@ def window_arrays(w, dtype=np.float64, mutate=None):
     R = np.zeros((n_obs, 2), T)
     V, Hq, B = np.zeros((n_lm, 6), T), np.zeros((n_lm, 6), T), np.zeros((n_lm, 3), T)
     W = np.zeros((len(pair_lm), 6, 3), T)
+    aR, aV, aHq, aB, aW = (np.zeros(a.shape, T) for a in (R, V, Hq, B, W))
+    dropped = -1
+    if mutate == "drop_last_obs":
+        dropped = int(np.flatnonzero(np.asarray(w.obs_lm) == drop_landmark(w))[-1])
+    ut = lambda m: np.array([m[i, j] for i, j in _UT], dtype=T)      # noqa: E731
     depth, defined, valid = np.full(n_obs, np.inf), np.zeros(n_obs, bool), np.zeros(n_obs, bool)
     bb = T(float(w.cauchy_b) * float(w.cauchy_b))
-    for o in range(n_obs):
+    for o in (range(n_obs - 1, -1, -1) if reverse else range(n_obs)):
         l, ip, ie, c = int(w.obs_lm[o]), int(w.obs_pose[o]), int(w.obs_ext[o]), int(w.obs_cam[o])
         ob = observation(pose[ip], pose[ie], lm[l], intr[c], int(model[c]), uv[o], float(w.obs_sqrtw[o]), T, mutate)
         depth[o], defined[o], valid[o] = ob["depth"], ob["defined"], ob["valid"]
         r, Jp, Jl, Je = ob["r"], ob["Jp"], ob["Jl"], ob["Je"]
         R[o] = r
+        aR[o] = ob["r_scale"]
+        if o == dropped:
+            continue
         sr = T(1)
         if w.cauchy_b > 0:
             sr = np.sqrt(T(1) / (T(1) + (r[0] * r[0] + r[1] * r[1]) / bb))
-        H = Jl.T @ Jl
-        Hq[l] += np.array([H[i, j] for i, j in _UT], dtype=T)
-        rs, Jps, Jls, Jes = sr * r, sr * Jp, sr * Jl, sr * Je
-        Vl = Jls.T @ Jls
-        V[l] += np.array([Vl[i, j] for i, j in _UT], dtype=T)
+        sj = sr * sr if mutate == "rho_prime" else sr
+        rs, Jps, Jls, Jes = sr * r, sj * Jp, sj * Jl, sj * Je
+        Hq[l] += ut(Jls.T @ Jls if mutate == "hq_robust" else Jl.T @ Jl)
+        V[l] += ut(Jls.T @ Jls)
         B[l] += Jls.T @ rs
         if (l, ip) in pair_of:
             W[pair_of[(l, ip)]] += Jps.T @ Jls
         if (l, ie) in pair_of:
             W[pair_of[(l, ie)]] += Jes.T @ Jls
+        if scales:
+            mJp, mJl, mJe = ob["aJp"], ob["aJl"], ob["aJe"]
+            aHq[l] += ut(mJl.T @ mJl)
+            aV[l] += ut((sj * mJl).T @ (sj * mJl))
+            aB[l] += (sj * mJl).T @ (sr * ob["r_scale"])
+            if (l, ip) in pair_of:
+                aW[pair_of[(l, ip)]] += (sj * mJp).T @ (sj * mJl)
+            if (l, ie) in pair_of:
+                aW[pair_of[(l, ie)]] += (sj * mJe).T @ (sj * mJl)
     for a in (R, V, Hq, B, W):
         assert a.dtype == T
-    f = lambda a: np.asarray(a, np.float64).reshape(-1)      # noqa: E731
-    return dict(OBS_RESIDUAL=f(R), LM_V=f(V), LM_B=f(B), LM_HQ=f(Hq), PAIR_W=f(W), pairs=(pair_lm, pair_block), depth=depth,
-                defined=defined, valid=valid)
+    f = lambda a: np.asarray(a, T if keep_dtype else np.float64).reshape(-1)      # noqa: E731
+    out = dict(OBS_RESIDUAL=f(R), LM_V=f(V), LM_B=f(B), LM_HQ=f(Hq), PAIR_W=f(W), pairs=(pair_lm, pair_block), depth=depth,
+               defined=defined, valid=valid)
+    if scales:
+        g = lambda a: np.asarray(a, np.float64).reshape(-1)      # noqa: E731
+        out["scale"] = dict(OBS_RESIDUAL=g(aR), LM_V=g(aV), LM_B=g(aB), LM_HQ=g(aHq), PAIR_W=g(aW))
+    return out
+
+
+def deviation_entrywise(a, ref, scale):
+    """max |a - ref| / scale over scale > 0 (float); where the scale is zero nothing was added and `a` must equal `ref` (asserted)"""
+    a, ref, scale = (np.asarray(v, np.float64) for v in (a, ref, scale))
+    assert a.shape == ref.shape == scale.shape, (a.shape, ref.shape, scale.shape)
+    assert np.array_equal(a[scale == 0.0], ref[scale == 0.0]), "an entry nothing sums into differs"
+    on = scale > 0.0
+    return float((np.abs(a - ref)[on] / scale[on]).max()) if on.any() else 0.0
 
 
 def deviation(a, ref):

@@ -7,6 +7,7 @@ import pytest
 from okvis_amd import synthetic
 from okvis_amd.window import DIST_EQUIDISTANT, DIST_NONE, DIST_RADTAN, DIST_RADTAN8, default_options
 
+from . import lin64_cases
 from . import schur_cases
 
 pytestmark = pytest.mark.gpu
@@ -16,6 +17,12 @@ pytestmark = pytest.mark.gpu
 def schur_ref(oracle):
     """e_ref of the Schur referee (tests/schur_cases.py): the yardstick of the entrywise checks of REDUCED_S below"""
     return schur_cases.Referee(oracle)
+
+
+@pytest.fixture(scope="module")
+def lin_ref(oracle):
+    """e_ref of the fp64 linearisation referee (tests/lin64_cases.py): the yardstick of the five landmark-side arrays below"""
+    return lin64_cases.Referee(oracle)
 
 
 def _entrywise(schur_ref, oracle, w, S, rhs):
@@ -51,7 +58,7 @@ def _close(a, b, tol=1e-9):
 
 @pytest.mark.parametrize("ext", ["fixed", "shared", "perframe"])
 @pytest.mark.parametrize("model", [DIST_RADTAN, DIST_EQUIDISTANT])
-def test_linearisation_arrays_match_oracle(oracle, schur_ref, ext, model):
+def test_linearisation_arrays_match_oracle(oracle, schur_ref, lin_ref, ext, model):
     w = synthetic.small_window(seed=21, K=4, L=60, estimate_extrinsics=ext, cam_model=model)
     b = _batch([w], debug_arrays=1, use_graph=0)
     # one small window (Dp = 24, 36 and 72 rows) takes the fused linearise + reduce launch: the REDUCED_S lines below exercise NO
@@ -64,6 +71,13 @@ def test_linearisation_arrays_match_oracle(oracle, schur_ref, ext, model):
     assert abs(s["final_cost"] - c_ref) <= 1e-12 * c_ref
     for name in ("OBS_RESIDUAL", "LM_V", "LM_B", "LM_HQ", "PAIR_W", "IMU_RESIDUAL"):
         _close(b.array(name), o.array(name))
+    # the five landmark-side arrays against the long-double oracle, entrywise and max-scaled, within the referee's bound
+    # (tests/test_gpu_fp64_linearize.py)
+    e = lin64_cases.window_deviations(oracle, w, {a: b.array(a) for a in lin64_cases.stmt.ARRAYS})
+    for a in lin64_cases.stmt.ARRAYS:
+        for k in lin64_cases.SCALES:
+            print(f"FP64REF parity {a} {k} e_kernel {e[a][k]:.3e} bound {lin_ref.bound(a, k):.3e}")
+            assert e[a][k] <= lin_ref.bound(a, k), (a, k, e[a][k], lin_ref.bound(a, k))
     _close(b.array("LM_QUALITY"), o.array("LM_QUALITY"), 1e-7)
     assert np.array_equal(b.pairs()[0], o.pairs()[0]) and np.array_equal(b.pairs()[1], o.pairs()[1])
     # reduced system and step of the first iteration
