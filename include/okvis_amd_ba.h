@@ -657,6 +657,55 @@ int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n,
  * landmark elimination, export) and of cov_kernel.  OKVIS_BA_ERR_STATE before the first call. */
 int okvis_ba_last_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* kernel_ms);
 
+/* ---- landmark covariance ------------------------------------------------------------------------------
+ * How certain the map is.  With S0, U, V_l, W_l exactly as above (no damping; V_l^-1 the plain 3 x 3 inverse by cofactors, the one
+ * the elimination used), P = (S0^-1)[0:Dp, 0:Dp] the pose-type part (Dp = 6 x the number of free pose-type blocks) and, for landmark
+ * l, W_l its pairs' 6 x 3 blocks stacked and rows_l their reduced rows:
+ *     G_l = W_l V_l^-1,      Sigma_l = V_l^-1 + G_l^T P[rows_l, rows_l] G_l            (3 x 3)
+ * the landmark's diagonal block of the inverse of the full undamped normal matrix.  It is expressed in the tangent coordinates of
+ * HomogeneousPointLocalParameterization: a step on the first three stored homogeneous coordinates of hp_W, w untouched.  For w = 1
+ * that is metres^2 in the world frame; otherwise divide by w^2.  Both terms are positive semi-definite.
+ * The reference has nothing of the kind: VioKeyframeWindowMatchingAlgorithm::doSetup gates its 3D-2D matches with a velocity-scaled
+ * pose uncertainty as a stand-in (INTEGRATION.md has the recipe that adds R Sigma_l R^T there).
+ *
+ * okvis_ba_landmark_covariance serves windows w0 .. w0 + n - 1 in one call, specs[i] / results[i] for window w0 + i, with the
+ * assembly of okvis_ba_state_covariance (one linearisation for the range), then P for every window (the state covariance's kernel
+ * body, all Dp columns: an entry of P has the bits okvis_ba_state_covariance returns for it) and one launch over every selected
+ * landmark of every window; one copy up, one copy back, one synchronisation.  A landmark's nine numbers have the same bits alone,
+ * in any selection and in any range of windows.  The solver is left bit for bit as it was, as by okvis_ba_state_covariance.
+ *  - spec->lm_idx NULL: every landmark in window order (n_lm is ignored); otherwise n_lm >= 0 indices in 0 .. the window's
+ *    n_lm - 1, repeats allowed (identical rows).
+ *  - result->flags[i] = 1, and row i NaN, when the landmark has no pair (no observation from a free block), or V_l is not positive
+ *    definite as far as the terms of the cofactor inverse show (v00, the leading 2 x 2 minor, the determinant), or the result is
+ *    not finite.  Such a landmark affects no other, does not raise info and does not change the return code.
+ *  - result->info = 1 when S0 cannot be inverted (the rule of okvis_ba_state_covariance): every row of that window is NaN, every
+ *    flag 1, the other windows are filled as usual and the call returns OKVIS_BA_ERR_NUMERIC.  min_pivot as above.
+ *  - result->S0 / Spp / V / W (each NULL or room for [D][D], [Dp][Dp], [n_lm of the window][6], [n_pair][18] doubles) are the
+ *    referee's taps: the very arrays the kernels read.
+ *  - OKVIS_BA_ERR_ARG, with nothing enqueued and no result touched: NULL arguments (cov and flags among them), a range outside the
+ *    batch, n_lm < 0, an index out of range, a capacity below the number of landmarks asked for.
+ *  - OKVIS_BA_ERR_UNSUPPORTED (a window above OKVIS_BA_COV_MAX_WINDOW_DIM: the HBM and tiled routes) and OKVIS_BA_ERR_STATE as for
+ *    okvis_ba_state_covariance. */
+typedef struct okvis_ba_lmcov_spec {
+  int32_t n_lm;
+  const int32_t* lm_idx;     /* NULL: all landmarks, window order */
+} okvis_ba_lmcov_spec;
+
+typedef struct okvis_ba_lmcov_result {
+  int32_t capacity;          /* in: landmarks cov / flags have room for */
+  int32_t n, info;           /* out */
+  double min_pivot;          /* out, as okvis_ba_cov_result */
+  double* cov;               /* [n][9] row-major, bitwise symmetric */
+  uint8_t* flags;            /* [n] 0 ok, 1 this landmark has no covariance (row = NaN) */
+  double *S0, *Spp, *V, *W;  /* referee's taps, each NULL or [D][D], [Dp][Dp], [n_lm of the window][6], [n_pair][18] */
+} okvis_ba_lmcov_result;
+
+int okvis_ba_landmark_covariance(okvis_ba_solver* s, int w0, int n,
+                                 const okvis_ba_lmcov_spec* specs, okvis_ba_lmcov_result* results);
+/* Measurement hook (HIP events of the last successful okvis_ba_landmark_covariance): its assembly launches, the inverse stage
+ * (cov_pose_kernel) and the landmark stage (lmcov_kernel and, with V / W taps, their copy).  OKVIS_BA_ERR_STATE before the first call. */
+int okvis_ba_last_landmark_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* inverse_ms, float* landmark_ms);
+
 /* ---- multi-GPU driver --------------------------------------------------------------
  * Windows are independent units: window i of a job runs on rank i mod world, one process per GPU, no data-path
  * collective.  The only exchange is ONE all-gather of these fixed-size records after all windows finished (RCCL over

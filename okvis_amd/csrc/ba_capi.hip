@@ -18,6 +18,7 @@
 #include "ba_imu.hpp"
 #include "ba_chol_tiles.hpp"
 #include "ba_cov.hpp"
+#include "ba_lmcov.hpp"
 #include "ba_linearize.hpp"
 #include "ba_linearize2.hpp"
 #include "ba_schur2.hpp"
@@ -34,7 +35,7 @@ using namespace ba;
 #include "capi_index_build.inc"   // batch_layout, build_batch, build_window and its helpers (the index build)
 #include "capi_launch.inc"        // LDS sizes, the launch plan (make_plan) and the launches, sub-batch fork / join
 // below: life cycle, options, upload / patch, state, begin / iterate / finish, queries and downloads, measurement hooks; then
-// capi_standalone.inc, capi_marginalize.inc and capi_covariance.inc
+// capi_standalone.inc, capi_marginalize.inc, capi_covariance.inc and capi_landmark_covariance.inc
 
 // =====================================================================================================
 extern "C" {
@@ -142,6 +143,8 @@ int okvis_ba_destroy(okvis_ba_solver* s) {
   if (s->d_ctrl_stage) (void)hipFree(s->d_ctrl_stage);
   if (s->marg_scratch) (void)hipFree(s->marg_scratch);
   for (auto ev : s->ev_cov)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : s->ev_lmcov)
     if (ev) (void)hipEventDestroy(ev);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1237,5 +1240,6 @@ int okvis_ba_synchronize(okvis_ba_solver* s) {
 #include "capi_marginalize.inc"   // okvis_ba_marginalize, _begin, _end; okvis_ba_marginalize_batch, _batch_begin, _batch_end
 
 #include "capi_covariance.inc"    // okvis_ba_state_covariance
+#include "capi_landmark_covariance.inc"   // okvis_ba_landmark_covariance
 
 }  // extern "C"

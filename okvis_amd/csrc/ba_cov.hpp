@@ -10,6 +10,8 @@
 //      leaves cond x eps = 1e-8 ... 1e-5 in the result, as any fp64 host inverse does; the refinement takes that to the rounding
 //      of the result itself;
 //   4. Sigma_K = diag(d_K) X_K diag(d_K): the entry of the lower triangle (in ascending row order) is computed, the upper mirrored.
+// The body is the device function cov_solve, shared by cov_kernel (a list of rows: okvis_ba_state_covariance) and cov_pose_kernel
+// (all pose-type rows, written to HBM: stage one of okvis_ba_landmark_covariance, ba_lmcov.hpp).
 // Route chosen among the two of the issue: unit vectors, not "K last and the trailing Schur complement".  The trailing block needs
 // no second array but cannot be refined (its error is in the complement, not in the small inverse); the unit vectors need D x 15
 // doubles next to the packed triangle (119 + 20 KB at D = 174) and give every column the same arithmetic whatever else is
@@ -38,16 +40,27 @@ struct CovArgs {
 __host__ __device__ constexpr size_t cov_lds_bytes(int D) { return 8 * ((size_t)D * (D + 1) / 2 + (size_t)D * COV_KC + D); }
 __host__ __device__ constexpr size_t cov_out_doubles(int k) { return (size_t)k * k + 2; }
 
-__global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restrict__ args) {
+// Which reduced rows are selected: a list (cov_kernel) or the leading k (cov_pose_kernel).  Ascending either way.
+struct CovRowList {
+  const int* r;
+  __device__ __forceinline__ int operator()(int q) const { return r[q]; }
+};
+struct CovRowLeading {
+  __device__ __forceinline__ int operator()(int q) const { return q; }
+};
+
+// The whole of a window's work, shared by the two kernels below: columns rows(0 .. k-1) of S^-1, the k x k result to `out`
+// (row-major, bitwise symmetric), min_pivot and info to tail[0], tail[1].  A column's arithmetic does not depend on what else is
+// selected: entry (a, b) has the same bits in either kernel.
+template <class Rows>
+__device__ __forceinline__ void cov_solve(const double* S, double* out, double* tail, int D, int k, const Rows rows) {
   extern __shared__ __attribute__((aligned(16))) double cov_smem[];
   __shared__ int s_bad;
-  const CovArgs& A = args[blockIdx.x];
-  const int D = A.D, k = A.k, tid = threadIdx.x;
+  const int tid = threadIdx.x;
   const int nL = D * (D + 1) / 2;
   double* L = cov_smem;            // packed lower triangle, row i at i (i + 1) / 2: S^, then its factor, then the factor's inverse
   double* Wm = L + nL;             // [D][COV_KC]: right-hand sides and intermediate vectors
   double* sd = Wm + D * COV_KC;    // the scaling d
-  const double* S = A.S;
   const double nan = __builtin_nan("");
   const bool row = tid < D;        // this work-item has a row
   const int ri = row ? tid : 0;
@@ -130,7 +143,6 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
       __syncthreads();
     }
   }
-  double* out = A.out;
   for (int c0 = 0; c0 < k && !bad; c0 += COV_KC) {
     const int kc = min(COV_KC, k - c0);
     // y = M^T (M w) for the COV_KC columns w in Wm, into registers (Wm is overwritten with M w on the way)
@@ -165,7 +177,7 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
     double x[COV_KC];
     if (row) {
 #pragma unroll
-      for (int c = 0; c < COV_KC; ++c) Wm[tid * COV_KC + c] = (c < kc && A.rows[c0 + c] == tid) ? 1.0 : 0.0;
+      for (int c = 0; c < COV_KC; ++c) Wm[tid * COV_KC + c] = (c < kc && rows(c0 + c) == tid) ? 1.0 : 0.0;
     }
     __syncthreads();
     apply(x);
@@ -179,7 +191,7 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
       double hi[COV_KC], lo[COV_KC];
 #pragma unroll
       for (int c = 0; c < COV_KC; ++c) {
-        hi[c] = (c < kc && A.rows[c0 + c] == tid) ? 1.0 : 0.0;
+        hi[c] = (c < kc && rows(c0 + c) == tid) ? 1.0 : 0.0;
         lo[c] = 0.0;
       }
       if (row) {
@@ -217,7 +229,7 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
     // ---- 4. the lower triangle of Sigma_K in ascending row order, mirrored
     int a = -1;
     for (int q = 0; q < k; ++q)
-      if (row && A.rows[q] == tid) a = q;
+      if (row && rows(q) == tid) a = q;
     bool nf = false;
     if (a >= 0) {
       const double da = sd[tid];
@@ -225,7 +237,7 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
       for (int c = 0; c < COV_KC; ++c) {
         const int b = c0 + c;
         if (c < kc && a >= b) {
-          const double v = (x[c] * da) * sd[A.rows[b]];
+          const double v = (x[c] * da) * sd[rows(b)];
           if (!(fabs(v) < __builtin_inf())) nf = true;
           out[a * k + b] = v;
           out[b * k + a] = v;
@@ -241,9 +253,27 @@ __global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restr
     for (int e = tid; e < k * k; e += COV_THREADS) out[e] = nan;
   }
   if (tid == 0) {
-    out[k * k] = min_pivot;
-    *reinterpret_cast<int*>(out + k * k + 1) = bad ? 1 : 0;
+    tail[0] = min_pivot;
+    *reinterpret_cast<int*>(tail + 1) = bad ? 1 : 0;
   }
+}
+
+__global__ __launch_bounds__(COV_THREADS) void cov_kernel(const CovArgs* __restrict__ args) {
+  const CovArgs& A = args[blockIdx.x];
+  cov_solve(A.S, A.out, A.out + A.k * A.k, A.D, A.k, CovRowList{A.rows});
+}
+
+// Stage one of okvis_ba_landmark_covariance: P = (S0^-1)[0:Dp, 0:Dp], every pose-type column, ceil(Dp / COV_KC) passes over the
+// same factor.  One workgroup per window, the LDS of cov_kernel.
+struct CovPoseArgs {
+  const double* S;   // [D][D] the exported system, full symmetric
+  double* P;         // [Dp][Dp]
+  double* tail;      // min_pivot | info (int)
+  int D, Dp;
+};
+__global__ __launch_bounds__(COV_THREADS) void cov_pose_kernel(const CovPoseArgs* __restrict__ args) {
+  const CovPoseArgs& A = args[blockIdx.x];
+  cov_solve(A.S, A.P, A.tail, A.D, A.Dp, CovRowLeading{});
 }
 
 // What the assembly launches of okvis_ba_state_covariance write besides linearisation buffers that every okvis_ba_begin rewrites:

@@ -301,6 +301,19 @@ class Frontend:
         return T, sb, count, cov, jac
 
 
+def landmark_covariance_in_camera(Sigma, T_CW):
+    """A landmark's covariance rotated into a camera frame: ``R Sigma R^T``, R the rotation of T_CW (world to camera).  Sigma
+    [..., 3, 3]: what ``WindowBatch.landmark_covariance()`` returns for a landmark (divided by w^2 when the stored homogeneous
+    point has w != 1); T_CW [4, 4] or [3, 3], or a stack matching Sigma.  This is the matrix to add to P_C, the 3 x 3 point
+    uncertainty the reference's 3D-2D matching gate propagates through the projection Jacobian
+    (VioKeyframeWindowMatchingAlgorithm::doSetup).  numpy only."""
+    Sigma, T = np.asarray(Sigma, np.float64), np.asarray(T_CW, np.float64)
+    if Sigma.shape[-2:] != (3, 3) or T.shape[-2:] not in ((4, 4), (3, 3)):
+        raise ValueError("Sigma is [..., 3, 3], T_CW [..., 4, 4] or [..., 3, 3]")
+    R = T[..., :3, :3]
+    return R @ Sigma @ np.swapaxes(R, -1, -2)
+
+
 def propagated_covariance(P0, jac, cov):
     """Covariance of a propagated state: ``jac @ P0 @ jac.T + cov``.  jac, cov [..., 15, 15]: what ``Frontend.imu_propagate``
     returns for a call (flags IMU_COV | IMU_JAC); P0 [15, 15]: the covariance of the state the chain starts from, e.g.

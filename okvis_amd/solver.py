@@ -291,6 +291,66 @@ class WindowBatch:
         _lib.check(self._L.okvis_ba_last_covariance_ms(self._h, C.byref(a), C.byref(k)), "last_covariance_ms")
         return dict(assembly=a.value, kernel=k.value)
 
+    def landmark_covariance(self, landmarks=None, w0: int = 0, n: int | None = None, want_taps: bool = False) -> list:
+        """okvis_ba_landmark_covariance on windows w0 .. w0 + n - 1 (default: to the end of the batch): for every selected landmark
+        the 3 x 3 diagonal block of the inverse of the full undamped normal matrix at the state the solver holds,
+        ``V^-1 + G^T P[rows, rows] G`` with ``G = W V^-1`` and P the pose-type part of the inverse of the reduced system, in the
+        tangent coordinates of the homogeneous point (a step on its first three coordinates; metres^2 in the world frame for
+        w = 1, otherwise divide by w^2).  landmarks: None = every landmark of every window in window order, one list of indices
+        for every window, or a list of lists (an entry may be None).  One linearisation, one copy each way and one synchronisation
+        for the range; the solver is left as it was.  Per window a dict cov [m][3][3], flags [m] (bool: True = no covariance, the
+        row is NaN: a landmark without observations from a free block, or a V that is not positive definite), info, min_pivot and,
+        with want_taps, S0 [D][D], Spp [Dp][Dp], V [n_lm][6], W [n_pair][18]: the arrays the kernels read.  A window with
+        info = 1 has every row NaN and every flag set; the call then raises BackendError (OKVIS_BA_ERR_NUMERIC) whose ``results``
+        attribute holds the list."""
+        from .window import lmcov_marshal_batch
+        w0 = int(w0)
+        n = len(self.windows) - w0 if n is None else int(n)
+        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
+            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        if landmarks is None:
+            sels = [None] * n
+        elif len(landmarks) > 0 and (landmarks[0] is None or isinstance(landmarks[0], (list, tuple, np.ndarray))):
+            sels = list(landmarks)
+            if len(sels) != n:
+                raise ValueError(f"{len(sels)} selections for {n} windows")
+        else:
+            sels = [landmarks] * n
+        counts = [int(self.windows[w0 + i].n_lm) for i in range(n)]
+        taps = None
+        if want_taps:
+            taps = []
+            for i in range(n):
+                W = self.windows[w0 + i]
+                np_ = C.c_int32()
+                _lib.check(self._L.okvis_ba_pair_count(self._h, w0 + i, C.byref(np_)))
+                taps.append((self.reduced_dim(w0 + i), 6 * int((np.asarray(W.pose_fixed).reshape(-1) == 0).sum()), counts[i], np_.value))
+        specs, results, outs, keep = lmcov_marshal_batch(sels, counts, taps)
+        st = self._L.okvis_ba_landmark_covariance(self._h, w0, n, specs, results)
+        del keep
+        if st not in (0, -5):
+            _lib.check(st, "landmark_covariance")
+        res = []
+        for i in range(n):
+            m = int(results[i].n)
+            r = dict(cov=outs[i]["cov"][:m].reshape(m, 3, 3).copy(), flags=outs[i]["flags"][:m].astype(bool), info=int(results[i].info),
+                     min_pivot=float(results[i].min_pivot))
+            if want_taps:
+                r.update({k: outs[i][k].copy() for k in ("S0", "Spp", "V", "W")})
+            res.append(r)
+        if st != 0:
+            err = _lib.BackendError(st, "landmark_covariance")
+            err.results = res
+            raise err
+        return res
+
+    def last_landmark_covariance_ms(self) -> dict:
+        """okvis_ba_last_landmark_covariance_ms: HIP-event times of the last landmark_covariance call's assembly launches, of the
+        inverse stage (all pose-type columns of the reduced system's inverse) and of the landmark stage"""
+        a, k, l = C.c_float(), C.c_float(), C.c_float()
+        _lib.check(self._L.okvis_ba_last_landmark_covariance_ms(self._h, C.byref(a), C.byref(k), C.byref(l)), "last_landmark_covariance_ms")
+        return dict(assembly=a.value, inverse=k.value, landmark=l.value)
+
     def synchronize(self):
         _lib.check(self._L.okvis_ba_synchronize(self._h), "synchronize")
 

@@ -119,6 +119,17 @@ class CovResultC(C.Structure):
                 ("cov", _dp), ("S0", _dp)]
 
 
+class LmcovSpecC(C.Structure):
+    """ctypes image of ``okvis_ba_lmcov_spec``."""
+    _fields_ = [("n_lm", C.c_int32), ("lm_idx", _ip)]
+
+
+class LmcovResultC(C.Structure):
+    """ctypes image of ``okvis_ba_lmcov_result``."""
+    _fields_ = [("capacity", C.c_int32), ("n", C.c_int32), ("info", C.c_int32), ("min_pivot", C.c_double),
+                ("cov", _dp), ("flags", _bp), ("S0", _dp), ("Spp", _dp), ("V", _dp), ("W", _dp)]
+
+
 BLOCK_POSE, BLOCK_SPEEDBIAS = 0, 1   # OKVIS_BA_BLOCK_*
 COV_MAX_WINDOW_DIM, COV_MAX_DIM = 174, 30   # OKVIS_BA_COV_MAX_WINDOW_DIM, OKVIS_BA_COV_MAX_DIM
 
@@ -142,6 +153,38 @@ def cov_marshal_batch(selections, dims, want_S0):
             results[i].S0 = out["S0"].ctypes.data_as(_dp)
         outs.append(out)
         keep.append((bt, bi))
+    return specs, results, outs, keep
+
+
+def lmcov_marshal_batch(selections, counts, tap_dims=None):
+    """Arrays of ``LmcovSpecC`` / ``LmcovResultC`` for okvis_ba_landmark_covariance: selections[i] = the landmark indices of the
+    i-th window of the range or None (all of them, window order), counts[i] its number of landmarks, tap_dims[i] = (D, Dp, n_lm,
+    n_pair) when the referee's taps are wanted.  Returns (specs, results, outs, keep)."""
+    n = len(selections)
+    specs, results = (LmcovSpecC * max(1, n))(), (LmcovResultC * max(1, n))()
+    outs, keep = [], []
+    for i, sel in enumerate(selections):
+        if sel is None:
+            m = int(counts[i])
+        else:
+            idx = np.ascontiguousarray(sel, np.int32).reshape(-1)
+            m = idx.size
+            specs[i].n_lm = m
+            buf = idx if m else np.zeros(1, np.int32)      # (an empty list is still a list: a non-NULL pointer)
+            specs[i].lm_idx = buf.ctypes.data_as(_ip)
+            keep.append(buf)
+        out = dict(cov=np.zeros((max(1, m), 9)), flags=np.zeros(max(1, m), np.uint8))
+        results[i].capacity = m
+        results[i].cov = out["cov"].ctypes.data_as(_dp)
+        results[i].flags = out["flags"].ctypes.data_as(_bp)
+        if tap_dims is not None:
+            D, Dp, n_lm, n_pair = (int(x) for x in tap_dims[i])
+            out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)))
+            for k in ("S0", "Spp", "V", "W"):
+                buf = out[k] if out[k].size else np.zeros(1)
+                keep.append(buf)
+                setattr(results[i], k, buf.ctypes.data_as(_dp))
+        outs.append(out)
     return specs, results, outs, keep
 
 
