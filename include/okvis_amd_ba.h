@@ -572,12 +572,13 @@ int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* sp
  * _set_marg_prior_values, _begin, _iterate, _finish (and with them _optimize / _optimize_timed / _evaluate_cost), _fetch_results,
  * _fetch_imu_caches, _download and another _marginalize / _marginalize_begin all return OKVIS_BA_ERR_STATE; only the queries that
  * touch neither the device nor the window (_reduced_dim, _pair_count, _get_limits, ...) and _synchronize are served.  Sizes beyond
- * the LDS route are waited for in _begin (their fall-back needs the call's arguments).  _end looks at the result structure before
+ * the LDS route are waited for in _begin (their fall-back is decided on the host).  _end looks at the result structure before
  * it ends the call: with too little room (OKVIS_BA_ERR_ARG) nothing is lost and _end can be called again with more.  A numeric
  * failure is reported by _end (OKVIS_BA_ERR_NUMERIC). */
 int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* result);
 int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* result);
-/* The same for windows w0 .. w0 + n - 1 of the uploaded batch in one call, specs[i] / results[i] for window w0 + i: what a caller
+/* The same for windows w0 .. w0 + n - 1 of the uploaded batch in one call, specs[i] / results[i] for window w0 + i (there is one
+ * implementation: okvis_ba_marginalize is this call with w0 = w, n = 1): what a caller
  * that keeps many sequences on one GPU does once per frame (the reference's frame loop marginalises right behind the optimisation,
  * ThreadedKFVio.cpp:736 / :765).  Per window the semantics are exactly those of okvis_ba_marginalize — the same argument checks, the
  * same meaning of every field (rank and sweeps included), the same numbers bit for bit — but the batch is linearised once, the
@@ -585,7 +586,7 @@ int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* result);
  * call makes one copy to the device, one back and one synchronisation.  All arguments of all n windows are checked before anything
  * is enqueued: a bad spec, a result with too little room, a window that carries a marg_* prior or a range outside the batch returns
  * the error of the single call, no result has been touched and the solver is as usable as before.  Windows off the LDS route (see
- * above) are served inside the same call by the single call's code, after the others; _batch_begin waits for those.
+ * above) are served inside the same call one after the other, behind the others; _batch_begin waits for those.
  * _batch_begin / _batch_end are the two halves as above: between them the solver refuses the same calls (OKVIS_BA_ERR_STATE), the
  * single-window entries among them, and while a single-window call is pending the batch entries are refused the same way.
  * _batch_end looks at every result structure before it ends the call (OKVIS_BA_ERR_ARG: nothing is lost, call it again with more

@@ -37,6 +37,10 @@ using namespace ba;
 // below: life cycle, options, upload / patch, state, begin / iterate / finish, queries and downloads, measurement hooks; then
 // capi_standalone.inc, capi_marginalize.inc, capi_covariance.inc and capi_landmark_covariance.inc
 
+// okvis_ba_marginalize_end / _batch_end first: between the two halves of a marginalisation the solver takes no edits and hands out
+// no results
+#define REFUSE_BETWEEN_MARG_HALVES(s) do { if ((s) && (s)->marg_pending.active) return OKVIS_BA_ERR_STATE; } while (0)
+
 // =====================================================================================================
 extern "C" {
 
@@ -119,7 +123,6 @@ int okvis_ba_create(okvis_ba_solver** out, int device) {
   lds(&chol_tiles_window_kernel, CT_SMEM_DOUBLES * 8);
   lds(&marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
   lds(&marg_dense_kernel<MAX_D, MAX_MARG_DIM>, MARG_LDS_DOUBLES_LARGE * 8);
-  lds(&marg_dense_batch_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>, MARG_LDS_DOUBLES * 8);
   lds(&cov_kernel, cov_lds_bytes(MAX_D_LDS));
 
   if (e != hipSuccess) {
@@ -546,7 +549,7 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
 }
 
 int okvis_ba_set_state(okvis_ba_solver* s, int w, const double* pose, const double* sb, const double* lm) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !s->uploaded || w < 0 || w >= (int)s->wins.size()) return s && !s->uploaded ? OKVIS_BA_ERR_STATE : OKVIS_BA_ERR_ARG;
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = refresh_acc(s, w)) return rc;
@@ -561,7 +564,7 @@ int okvis_ba_set_state(okvis_ba_solver* s, int w, const double* pose, const doub
 }
 
 int okvis_ba_get_state(okvis_ba_solver* s, int w, double* pose, double* sb, double* lm) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !s->uploaded || w < 0 || w >= (int)s->wins.size()) return s && !s->uploaded ? OKVIS_BA_ERR_STATE : OKVIS_BA_ERR_ARG;
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = refresh_acc(s, w)) return rc;
@@ -615,7 +618,7 @@ static int refresh_mirrors(okvis_ba_solver* s) {
 }
 
 int okvis_ba_patch_window(okvis_ba_solver* s, int w, const okvis_ba_patch* p) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !p) return OKVIS_BA_ERR_ARG;
   if (!s->uploaded || !s->patchable || s->mirrors.size() != s->wins.size()) return OKVIS_BA_ERR_STATE;
   if (w < 0 || w >= (int)s->wins.size()) return OKVIS_BA_ERR_ARG;
@@ -739,7 +742,7 @@ int okvis_ba_patched_view(okvis_ba_solver* s, int w, okvis_ba_window* out) {
 
 int okvis_ba_fetch_results(okvis_ba_solver* s, int w, double* pose, double* sb, double* lm, double* lm_quality,
                            double* imu_sb_ref) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !s->uploaded || w < 0 || w >= (int)s->wins.size()) return s && !s->uploaded ? OKVIS_BA_ERR_STATE : OKVIS_BA_ERR_ARG;
   HIP_TRY(hipSetDevice(s->device));
   HostWin& H = s->wins[w];
@@ -760,7 +763,7 @@ int okvis_ba_fetch_results(okvis_ba_solver* s, int w, double* pose, double* sb, 
 }
 
 int okvis_ba_fetch_imu_caches(okvis_ba_solver* s, int w, double* caches) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !s->uploaded || w < 0 || w >= (int)s->wins.size()) return s && !s->uploaded ? OKVIS_BA_ERR_STATE : OKVIS_BA_ERR_ARG;
   if (!caches) return OKVIS_BA_ERR_ARG;
   HIP_TRY(hipSetDevice(s->device));
@@ -773,7 +776,7 @@ int okvis_ba_fetch_imu_caches(okvis_ba_solver* s, int w, double* caches) {
 }
 
 int okvis_ba_begin(okvis_ba_solver* s) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (s) s->acc_fresh = s->res_staged = s->mirror_fresh = false;
   if (!s) return OKVIS_BA_ERR_ARG;
   if (!s->uploaded) return OKVIS_BA_ERR_STATE;
@@ -796,7 +799,7 @@ int okvis_ba_begin(okvis_ba_solver* s) {
 }
 
 int okvis_ba_iterate(okvis_ba_solver* s, int n) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (s) s->acc_fresh = false;
   if (!s || n < 0) return OKVIS_BA_ERR_ARG;
   if (!s->begun) return OKVIS_BA_ERR_STATE;
@@ -873,7 +876,7 @@ int okvis_ba_last_iterate_ms(okvis_ba_solver* s, float* total_ms) {
 }
 
 int okvis_ba_finish(okvis_ba_solver* s, okvis_ba_summary* summaries) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s) return OKVIS_BA_ERR_ARG;
   if (!s->begun) return OKVIS_BA_ERR_STATE;
   HIP_TRY(hipSetDevice(s->device));
@@ -1094,7 +1097,7 @@ int okvis_ba_array_size(okvis_ba_solver* s, int w, int which, int64_t* n_doubles
 }
 
 int okvis_ba_download(okvis_ba_solver* s, int w, int which, double* out, int64_t n_doubles) {
-  if (s && s->marg_pending.active) return OKVIS_BA_ERR_STATE;   // (okvis_ba_marginalize_end first: between the two halves the solver takes no edits and hands out no results)
+  REFUSE_BETWEEN_MARG_HALVES(s);
   if (!s || !out || !s->uploaded || w < 0 || w >= (int)s->wins.size()) return OKVIS_BA_ERR_ARG;
   HIP_TRY(hipSetDevice(s->device));
   const double* p = nullptr;

@@ -7,7 +7,7 @@
 //
 // Input: the undamped system (H, b0) over all free pose-type / speed-bias blocks of a (sub-)window, exported
 // by solve_kernel(final_only = 2) after the Schur kernel eliminated every landmark with the preconditioned
-// pseudo-inverse, plus the previous prior (H_old, b0_old) over some of those blocks.  One workgroup per call.
+// pseudo-inverse, plus the previous prior (H_old, b0_old) over some of those blocks.  One workgroup per window.
 // The symmetric eigen-decompositions (Eigen::SelfAdjointEigenSolver in the reference) are done by cyclic
 // Jacobi in the round-robin parallel ordering: n/2 disjoint rotations per round, column phase then row phase.
 #pragma once
@@ -26,23 +26,25 @@ constexpr int MARG_LDS_DOUBLES = 18 * 1024;  // 144 KB of dynamic LDS for the ei
 constexpr int MARG_SMALL_PRIOR = 192;
 constexpr int MARG_LDS_DOUBLES_LARGE = 11 * 1024;
 
+// (the pointers are typed as global-address-space pointers on the device, as WinPtrs' are — ba_types.hpp, BA_G: marg_dense_kernel reads
+//  the record from memory, and a pointer read from memory is a generic one otherwise, whose accesses become FLAT instructions)
 struct MargArgs {
-  const unsigned char* pose_marg;  // [n_pose] 1 = eliminate this block in the dense step
-  const unsigned char* sb_marg;    // [n_sb]
+  const BA_G unsigned char* pose_marg;  // [n_pose] 1 = eliminate this block in the dense step
+  const BA_G unsigned char* sb_marg;    // [n_sb]
   int prior_dim, prior_nb;
-  const int* pb_type;   // [prior_nb] 0 = pose-type, 1 = speed/bias
-  const int* pb_idx;    // [prior_nb] block index in the window
-  const int* pb_off;    // [prior_nb] offset inside the prior
-  const double* prior_H;   // [prior_dim^2] row-major
-  const double* prior_b0;  // [prior_dim]
-  double* work;            // marg_work_doubles(D)
-  double* out_H;           // [na*na]
-  double* out_b0;          // [na]
-  double* out_J;           // [na*na]
-  double* out_e0;          // [na]
-  int* out_info;           // [0] na, [1] nm, [2] rank, [3] Jacobi sweeps (V), [4] Jacobi sweeps (H), [8 + i] kept reduced index i
+  const BA_G int* pb_type;   // [prior_nb] 0 = pose-type, 1 = speed/bias
+  const BA_G int* pb_idx;    // [prior_nb] block index in the window
+  const BA_G int* pb_off;    // [prior_nb] offset inside the prior
+  const BA_G double* prior_H;   // [prior_dim^2] row-major
+  const BA_G double* prior_b0;  // [prior_dim]
+  BA_G double* work;            // marg_work_doubles(D)
+  BA_G double* out_H;           // [na*na]
+  BA_G double* out_b0;          // [na]
+  BA_G double* out_J;           // [na*na]
+  BA_G double* out_e0;          // [na]
+  BA_G int* out_info;           // [0] na, [1] nm, [2] rank, [3] Jacobi sweeps (V), [4] Jacobi sweeps (H), [8 + i] kept reduced index i
   // tiled route (ba_marg_tiles.hpp): the kernel stops after M and b0 (stage = 1) and leaves the scaling of the elimination here
-  double* p_out = nullptr; // [D]
+  BA_G double* p_out = nullptr; // [D]
 };
 
 // workspace of marg_dense_kernel: A | Q | M (D^2 each), the 6-row panel of marg_chol_inverse, and the two padded matrices of the
@@ -608,7 +610,7 @@ __device__ bool marg_chol_inverse(double* M, double* X, int n, int n_true, doubl
   return s_okb != 0;
 }
 
-// The dense tail of one window on one workgroup: the body of marg_dense_kernel and of marg_dense_batch_kernel.
+// The dense tail of one window on one workgroup: the body of marg_dense_kernel.
 template <int MAXD, int MAXP>
 __device__ __forceinline__ void marg_dense_body(const WinPtrs& W, const MargArgs& a, int lds_doubles, int stage) {
   extern __shared__ __attribute__((aligned(16))) double marg_lds[];
@@ -924,19 +926,13 @@ __device__ __forceinline__ void marg_dense_body(const WinPtrs& W, const MargArgs
 #undef MSTAMP
 }
 
+// The kernel: workgroup i takes window record wins[i] with the arguments args[i] — a call for one window is a launch of one
+// workgroup.  The kernel is LDS-bound to one workgroup per CU, so a range spreads over as many CUs as it has windows.  The argument
+// record is copied once at the top, before anything is stored: a uniform index into read-only memory, so the copy is a handful of
+// scalar loads and the fields live in scalar registers exactly as kernel arguments would.
 template <int MAXD, int MAXP>
-__global__ __launch_bounds__(MARG_THREADS) void marg_dense_kernel(const WinPtrs* __restrict__ wins, int w, MargArgs a,
+__global__ __launch_bounds__(MARG_THREADS) void marg_dense_kernel(const WinPtrs* __restrict__ wins, const MargArgs* __restrict__ args,
                                                                    int lds_doubles, int stage) {
-  marg_dense_body<MAXD, MAXP>(wins[w], a, lds_doubles, stage);
-}
-
-// A batch of windows (okvis_ba_marginalize_batch): workgroup i takes window record wins[i] with the arguments args[i].  The kernel is
-// LDS-bound to one workgroup per CU, so a batch spreads over as many CUs as it has windows.  The argument record is copied once at
-// the top, before anything is stored: a uniform index into read-only memory, so the copy is a handful of scalar loads and the
-// fields live in scalar registers exactly as the kernel arguments of marg_dense_kernel do.
-template <int MAXD, int MAXP>
-__global__ __launch_bounds__(MARG_THREADS) void marg_dense_batch_kernel(const WinPtrs* __restrict__ wins, const MargArgs* __restrict__ args,
-                                                                         int lds_doubles, int stage) {
   const MargArgs a = args[blockIdx.x];
   marg_dense_body<MAXD, MAXP>(wins[blockIdx.x], a, lds_doubles, stage);
 }

@@ -17,7 +17,8 @@
 //   marg_tiles_decide_kernel     the proof of full rank, as in marg_chol_inverse:  1 / ||L^-1||_F^2 > 4 eps n max_i sum_j |A_ij|
 //
 // When the proof fails (a rank-deficient kept block, a non-positive pivot) nothing of this is used: the caller runs the
-// single-workgroup kernel, which goes on to the eigen-decomposition.
+// single-workgroup kernel (stage 0, with the window's second argument record: no previous prior, it is part of H already), which
+// goes on to the eigen-decomposition.  The kernels here take MargArgs by value; marg_dense_kernel reads its record from the device.
 #pragma once
 #include "ba_chol_tiles.hpp"
 #include "ba_marg.hpp"

@@ -1,5 +1,5 @@
-// Part of ba_capi.hip, inside its extern "C" block, behind capi_marginalize.inc (whose scratch block, window-record copy and
-// option-record swap it uses).  okvis_ba_state_covariance (DESIGN.md "State covariance"): for a range of windows, linearise at the
+// Part of ba_capi.hip, inside its extern "C" block, behind capi_marginalize.inc (whose shared pieces it uses: the scratch block, the
+// window record with export buffers, the option-record swap, schur_and_export).  okvis_ba_state_covariance (DESIGN.md "State covariance"): for a range of windows, linearise at the
 // state the solver holds, eliminate the landmarks with the plain inverse and no damping (OptD::marg_mode = 2), export the reduced
 // system S0 (solve_kernel final_only = 2) — one launch each, as okvis_ba_marginalize_batch does — then cov_kernel (ba_cov.hpp), one
 // workgroup per window.  One copy up, one copy back, one synchronisation.  The control records and the IMU terms' preintegration
@@ -12,7 +12,8 @@ struct CovJob {
   int D = 0, k = 0;
   int rows[COV_MAX_DIM];   // the selected reduced rows, ascending (what the kernel works on)
   int at[COV_MAX_DIM];     // row p of the result (list order) = row at[p] of the kernel's
-  size_t o_S = 0, o_rhs = 0, o_d2 = 0, o_out = 0;
+  ExportAt ex;             // where S0, rhs and the damping are exported to
+  size_t o_out = 0;
 };
 
 int cov_check(const okvis_ba_solver* s, int w, const okvis_ba_cov_spec* spec, const okvis_ba_cov_result* res, CovJob& J) {
@@ -44,7 +45,6 @@ int cov_check(const okvis_ba_solver* s, int w, const okvis_ba_cov_spec* spec, co
 // ---- What okvis_ba_state_covariance and okvis_ba_landmark_covariance (capi_landmark_covariance.inc) share: the assembly ----
 // The scratch block of a call starts with what the host writes (window records with the export buffers attached | the entry's own
 // records | the private option record), then what is kept of the solver, then workspaces and outputs.
-struct CovExport { size_t o_S = 0, o_rhs = 0, o_d2 = 0; };   // where a window's S0 [D][D], rhs [D] and damping [D] are exported to
 struct CovAssembly {
   size_t o_wins = 0, o_opt = 0, o_keep = 0, keep_stride = 0;
   int max_imu = 0;
@@ -68,13 +68,9 @@ void cov_alloc_keep(const okvis_ba_solver* s, Arena& A, CovAssembly& ca) {
 }
 
 // window w0 + i's record with the export buffers attached, and the option record (marg_mode = 2), into the host block
-void cov_fill_host(const okvis_ba_solver* s, int w0, int n, unsigned char* hb, unsigned char* d, const CovAssembly& ca, const CovExport* ex) {
+void cov_fill_host(const okvis_ba_solver* s, int w0, int n, unsigned char* hb, unsigned char* d, const CovAssembly& ca, const ExportAt* ex) {
   for (int i = 0; i < n; ++i) {
-    WinPtrs P = s->wins[w0 + i].ptrs;
-    P.S = (decltype(P.S))(d + ex[i].o_S);
-    P.rhs = (decltype(P.rhs))(d + ex[i].o_rhs);
-    P.Dp2 = (decltype(P.Dp2))(d + ex[i].o_d2);
-    P.grad = nullptr;
+    const WinPtrs P = win_with_export(s->wins[w0 + i], d, ex[i]);
     std::memcpy(&hb[ca.o_wins + sizeof(WinPtrs) * (size_t)i], &P, sizeof(P));
   }
   OptD od = marg_optd(s);
@@ -82,8 +78,7 @@ void cov_fill_host(const okvis_ba_solver* s, int w0, int n, unsigned char* hb, u
   std::memcpy(&hb[ca.o_opt], &od, sizeof(od));
 }
 
-// One copy up; keep; linearise + landmark elimination + export, one launch each for the range (helper workgroups as the plan's own
-// extents have them; either way a chunk's partials are added in chunk order, so a window's system has the same bits); the entry's
+// One copy up; keep; linearise + landmark elimination + export, one launch each for the range (schur_and_export); the entry's
 // own kernels (`stage`, which records its events itself and returns a hipError_t); whatever happened, what was kept goes back.
 // ev_begin / ev_assembled are recorded in front of and behind the assembly.  On an error everything enqueued is waited for.
 extern "C++" {   // (this file sits inside ba_capi.hip's extern "C" block)
@@ -112,12 +107,7 @@ int cov_assemble_and_run(okvis_ba_solver* s, int w0, int n, unsigned char* d, co
     s->d_opt = reinterpret_cast<OptD*>(d + ca.o_opt);
     rc = okvis_ba_begin(s);
     if (rc == OKVIS_BA_OK) {
-      const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
-      hipError_t e = launch_schur(s, sub(s->stream, Extent{w0, n, helpers}));
-      if (e == hipSuccess) {
-        launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
-        e = hipGetLastError();
-      }
+      const hipError_t e = schur_and_export(s, w0, n, d_wins);
       if (e != hipSuccess) {
         s->last_hip_error = (int)e;
         rc = OKVIS_BA_HIP_ERROR_BASE + (int)e;
@@ -160,12 +150,12 @@ int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_
   ca.o_opt = A.alloc(sizeof(OptD));
   const size_t host_part = A.size;   // ONE copy up
   cov_alloc_keep(s, A, ca);
-  std::vector<CovExport> ex((size_t)n);
+  std::vector<ExportAt> ex((size_t)n);
   int Dmax = 1;
   for (int i = 0; i < n; ++i) {
     CovJob& J = jobs[i];
-    J.o_rhs = A.alloc(8 * (size_t)J.D), J.o_d2 = A.alloc(8 * (size_t)J.D);
-    if (!results[i].S0) J.o_S = A.alloc(8 * (size_t)J.D * J.D);
+    J.ex.o_rhs = A.alloc(8 * (size_t)J.D), J.ex.o_d2 = A.alloc(8 * (size_t)J.D);
+    if (!results[i].S0) J.ex.o_S = A.alloc(8 * (size_t)J.D * J.D);
     Dmax = std::max(Dmax, J.D);
   }
   size_t out_base = 0;
@@ -173,8 +163,8 @@ int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_
     CovJob& J = jobs[i];
     J.o_out = A.alloc(8 * cov_out_doubles(J.k));
     if (i == 0) out_base = J.o_out;
-    if (results[i].S0) J.o_S = A.alloc(8 * (size_t)J.D * J.D);
-    ex[i].o_S = J.o_S, ex[i].o_rhs = J.o_rhs, ex[i].o_d2 = J.o_d2;
+    if (results[i].S0) J.ex.o_S = A.alloc(8 * (size_t)J.D * J.D);
+    ex[i] = J.ex;
   }
   const size_t out_total = A.size - out_base;
   s->stage_marg.resize(host_part);
@@ -186,7 +176,7 @@ int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_
     const CovJob& J = jobs[i];
     CovArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.S = reinterpret_cast<const double*>(d + J.o_S);
+    a.S = reinterpret_cast<const double*>(d + J.ex.o_S);
     a.out = reinterpret_cast<double*>(d + J.o_out);
     a.D = J.D, a.k = J.k;
     std::copy(J.rows, J.rows + J.k, a.rows);
@@ -214,7 +204,7 @@ int okvis_ba_state_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_
     R.dim = k;
     R.min_pivot = o[k * k];
     std::memcpy(&R.info, o + k * k + 1, sizeof(int32_t));
-    if (R.S0) std::memcpy(R.S0, s->stage_dl.data() + (J.o_S - out_base), 8 * (size_t)J.D * J.D);
+    if (R.S0) std::memcpy(R.S0, s->stage_dl.data() + (J.ex.o_S - out_base), 8 * (size_t)J.D * J.D);
     if (R.info != 0) rc = OKVIS_BA_ERR_NUMERIC;
   }
   return rc;

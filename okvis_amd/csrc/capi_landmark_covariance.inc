@@ -12,7 +12,7 @@ namespace {
 struct LmcovJob {
   int D = 0, Dp = 0, n = 0, n_lm = 0, n_pair = 0;
   const int32_t* sel = nullptr;   // the caller's list, or null = window order
-  CovExport ex;
+  ExportAt ex;
   size_t o_sel = 0, o_P = 0, o_tail = 0, o_cov = 0, o_flags = 0, o_V = 0, o_W = 0;
 };
 
@@ -87,7 +87,7 @@ int okvis_ba_landmark_covariance(okvis_ba_solver* s, int w0, int n, const okvis_
   if (int rc = marg_reserve_scratch(s, A.size)) return rc;
   unsigned char* d = s->marg_scratch;
   {
-    std::vector<CovExport> ex((size_t)n);
+    std::vector<ExportAt> ex((size_t)n);
     for (int i = 0; i < n; ++i) ex[i] = jobs[i].ex;
     cov_fill_host(s, w0, n, hb, d, ca, ex.data());
   }

@@ -2,9 +2,62 @@
 // MarginalizationError numerics (see include/okvis_amd_ba.h): linearise at the uploaded values, eliminate
 // the landmarks (schur_kernel in marg_mode), export the dense system (solve_kernel final_only = 2), then the
 // dense elimination + eigen-decomposition (marg_dense_kernel).
-// okvis_ba_marginalize_batch / _batch_begin / _batch_end: the same for a range of windows in one call — one linearisation, one Schur
-// launch, one export launch, one launch of the dense tail with a workgroup per window (marg_dense_batch_kernel), one copy each way.
+// There is ONE implementation, for a range of windows (marg_begin / marg_end): one linearisation, one Schur launch, one export
+// launch, one launch of the dense tail with a workgroup per window for every run of windows on the LDS route, one copy each way.
+// okvis_ba_marginalize_batch / _batch_begin / _batch_end are that call; okvis_ba_marginalize / _begin / _end are the range of one.
 namespace {
+
+// ---- What the three range entries share: okvis_ba_marginalize[_batch] (below), okvis_ba_state_covariance (capi_covariance.inc) and
+//      okvis_ba_landmark_covariance (capi_landmark_covariance.inc).  Each lays its scratch block out with an Arena (capi_solver.inc),
+//      what the host writes first so that it goes up in one copy, and keeps the block in s->marg_scratch. ----
+int marg_reserve_scratch(okvis_ba_solver* s, size_t bytes) {
+  if (bytes > s->marg_scratch_bytes) {
+    if (s->marg_scratch) HIP_TRY(hipFree(s->marg_scratch));
+    s->marg_scratch = nullptr;
+    s->marg_scratch_bytes = 0;
+    HIP_TRY(hipMalloc(&s->marg_scratch, bytes));
+    s->marg_scratch_bytes = bytes;
+  }
+  return OKVIS_BA_OK;
+}
+// The pass has its own option record in the scratch block (no trust region: one linearisation, no damping); the launches read it
+// through s->d_opt, which points there for the duration of the call.  The solver's own record is never touched, so nothing has to
+// be restored on the device and captured launch graphs stay valid.
+OptD marg_optd(const okvis_ba_solver* s) {
+  OptD od = make_optd(s->opt, (int)s->wins.size());
+  od.marg_mode = 1;
+  od.dogleg = 0;
+  return od;
+}
+struct MargSwapOptions {
+  okvis_ba_solver* s;
+  OptD* saved;
+  ~MargSwapOptions() { s->d_opt = saved; }
+};
+// where a window's reduced system [D][D], its right-hand side [D] and its damping [D] are exported to (offsets in the scratch block d)
+struct ExportAt { size_t o_S = 0, o_rhs = 0, o_d2 = 0; };
+// the window's record with the export buffers attached
+WinPtrs win_with_export(const HostWin& H, unsigned char* d, const ExportAt& ex) {
+  WinPtrs P = H.ptrs;
+  P.S = (decltype(P.S))(d + ex.o_S);
+  P.rhs = (decltype(P.rhs))(d + ex.o_rhs);
+  P.Dp2 = (decltype(P.Dp2))(d + ex.o_d2);
+  P.grad = nullptr;
+  return P;
+}
+// Landmark elimination + export (solve_kernel, final_only = 2) of windows w0 .. w0 + n - 1 behind okvis_ba_begin, one launch each;
+// d_wins: their records with the export buffers attached.  Helper workgroups as the plan's own extents have them: up to
+// SOLVE_HELPED_MAX_WINDOWS windows they sum the Schur chunk partials, longer ranges sum inside the solving workgroup.  Both add a
+// chunk's partials in chunk order starting from zero (ba_solve.hpp), so a window's exported system has the same bits either way,
+// and a range of one has okvis_ba_marginalize's launch shape.  lds_windows = false: every window of the range is assembled in HBM
+// (such windows leave the solve launch at once; marg_export_large exports them one by one).
+hipError_t schur_and_export(okvis_ba_solver* s, int w0, int n, const WinPtrs* d_wins, bool lds_windows = true) {
+  const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
+  const hipError_t e = launch_schur(s, sub(s->stream, Extent{w0, n, helpers}));
+  if (e != hipSuccess) return e;
+  if (lds_windows && s->plan.solve.k) launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
+  return hipGetLastError();
+}
 
 // One window of a marginalisation call: what the argument check found (the kept blocks, in reduced order: pose-type blocks first),
 // the route its dense tail takes and where its pieces lie in the call's scratch block.
@@ -18,7 +71,9 @@ struct MargJob {
   bool lds_route = false;  // the single workgroup whose matrices stay in LDS
   size_t nn = 1, n1 = 1, out_bytes = 0;
   size_t o_pm = 0, o_sm = 0, o_pt = 0, o_pi = 0, o_po = 0, o_pH = 0, o_pb = 0;   // written by the host
-  size_t o_work = 0, o_S = 0, o_rhs = 0, o_d2 = 0;                               // workspace, exported system
+  size_t o_again = 0;      // ... and, on the tiled route, the argument record of its fall-back
+  size_t o_work = 0;       // workspace
+  ExportAt ex;             // exported system
   size_t o_out = 0, o_info = 0;                                                  // H | J | b0 | e0 | info
   int mt_nT = 0, mt_ntiles = 0;
   size_t o_mtT = 0, o_mtZ = 0, o_mtL = 0, o_mtR = 0, o_mtY = 0, o_mtP = 0, o_mtF = 0, o_mtp = 0, o_mtS = 0, o_mtf = 0;
@@ -87,11 +142,12 @@ void marg_place_host(Arena& A, const HostWin& H, MargJob& J) {
   J.o_pt = A.alloc(sizeof(int) * std::max(1, J.pnb)), J.o_pi = A.alloc(sizeof(int) * std::max(1, J.pnb)),
   J.o_po = A.alloc(sizeof(int) * std::max(1, J.pnb));
   J.o_pH = A.alloc(8 * std::max<size_t>(1, (size_t)J.pd * J.pd)), J.o_pb = A.alloc(8 * std::max(1, J.pd));
+  if (J.tiles) J.o_again = A.alloc(sizeof(MargArgs));
 }
 void marg_place_work(Arena& A, MargJob& J) {
   const int D = J.D;
   J.o_work = A.alloc(8 * marg_work_doubles(std::max(1, D)));
-  J.o_S = A.alloc(8 * std::max<size_t>(1, (size_t)D * D)), J.o_rhs = A.alloc(8 * std::max(1, D)), J.o_d2 = A.alloc(8 * std::max(1, D));
+  J.ex.o_S = A.alloc(8 * std::max<size_t>(1, (size_t)D * D)), J.ex.o_rhs = A.alloc(8 * std::max(1, D)), J.ex.o_d2 = A.alloc(8 * std::max(1, D));
 }
 void marg_place_out(Arena& A, MargJob& J) {   // H | J | b0 | e0 | info: contiguous, ONE copy back
   J.o_out = A.alloc(J.out_span());
@@ -121,58 +177,26 @@ void marg_fill_host(unsigned char* hb, const HostWin& H, const MargJob& J) {
     std::memcpy(&hb[J.o_pb], spec->prior_b0, 8 * (size_t)J.pd);
   }
 }
-// this window's record with the export buffers attached
-WinPtrs marg_win_copy(unsigned char* d, const HostWin& H, const MargJob& J) {
-  WinPtrs P = H.ptrs;
-  P.S = (decltype(P.S))(d + J.o_S);
-  P.rhs = (decltype(P.rhs))(d + J.o_rhs);
-  P.Dp2 = (decltype(P.Dp2))(d + J.o_d2);
-  P.grad = nullptr;
-  return P;
-}
 void marg_args(unsigned char* d, const MargJob& J, MargArgs& ma) {
-  ma.pose_marg = d + J.o_pm;
-  ma.sb_marg = d + J.o_sm;
+#define MARG_AT(field, off) ma.field = (decltype(ma.field))(d + (off))   // (the record's pointers are global-address-space ones)
+  MARG_AT(pose_marg, J.o_pm);
+  MARG_AT(sb_marg, J.o_sm);
   ma.prior_dim = J.pd;
   ma.prior_nb = J.pd > 0 ? J.pnb : 0;
-  ma.pb_type = reinterpret_cast<const int*>(d + J.o_pt);
-  ma.pb_idx = reinterpret_cast<const int*>(d + J.o_pi);
-  ma.pb_off = reinterpret_cast<const int*>(d + J.o_po);
-  ma.prior_H = reinterpret_cast<const double*>(d + J.o_pH);
-  ma.prior_b0 = reinterpret_cast<const double*>(d + J.o_pb);
-  ma.work = reinterpret_cast<double*>(d + J.o_work);
-  double* outp = reinterpret_cast<double*>(d + J.o_out);
-  ma.out_H = outp;
-  ma.out_J = outp + J.nn;
-  ma.out_b0 = outp + 2 * J.nn;
-  ma.out_e0 = outp + 2 * J.nn + J.n1;
-  ma.out_info = reinterpret_cast<int*>(d + J.o_info);
-  ma.p_out = reinterpret_cast<double*>(d + J.o_mtp);
+  MARG_AT(pb_type, J.o_pt);
+  MARG_AT(pb_idx, J.o_pi);
+  MARG_AT(pb_off, J.o_po);
+  MARG_AT(prior_H, J.o_pH);
+  MARG_AT(prior_b0, J.o_pb);
+  MARG_AT(work, J.o_work);
+  MARG_AT(out_H, J.o_out);
+  MARG_AT(out_J, J.o_out + 8 * J.nn);
+  MARG_AT(out_b0, J.o_out + 8 * 2 * J.nn);
+  MARG_AT(out_e0, J.o_out + 8 * (2 * J.nn + J.n1));
+  MARG_AT(out_info, J.o_info);
+  MARG_AT(p_out, J.o_mtp);
+#undef MARG_AT
 }
-int marg_reserve_scratch(okvis_ba_solver* s, size_t bytes) {
-  if (bytes > s->marg_scratch_bytes) {
-    if (s->marg_scratch) HIP_TRY(hipFree(s->marg_scratch));
-    s->marg_scratch = nullptr;
-    s->marg_scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&s->marg_scratch, bytes));
-    s->marg_scratch_bytes = bytes;
-  }
-  return OKVIS_BA_OK;
-}
-// The marginalisation pass has its own option record in the scratch block (no trust region: one linearisation, no damping); the
-// launches read it through s->d_opt, which points there for the duration of the call.  The solver's own record is never touched, so
-// nothing has to be restored on the device and captured launch graphs stay valid.
-OptD marg_optd(const okvis_ba_solver* s) {
-  OptD od = make_optd(s->opt, (int)s->wins.size());
-  od.marg_mode = 1;
-  od.dogleg = 0;
-  return od;
-}
-struct MargSwapOptions {
-  okvis_ba_solver* s;
-  OptD* saved;
-  ~MargSwapOptions() { s->d_opt = saved; }
-};
 // the export of one window whose reduced system is assembled in HBM: assembly of the undamped system, then the kernel that completes
 // it (Schur partials, IMU terms) and, because this copy of the window carries an S pointer, writes it out as one full symmetric
 // D x D matrix
@@ -181,18 +205,20 @@ void marg_export_large(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_wi
   const int nT = (((J.D + 5) / 6) * 6 + CT_TB - 1) / CT_TB;
   hipLaunchKernelGGL(large_export_kernel, dim3(nT * (nT + 1) / 2, 1, CT_TILE / CT_THREADS), dim3(CT_THREADS), 0, s->stream, d_win);
 }
-void marg_dense_launch(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs& args, int stage) {
+// marg_dense_kernel for n consecutive windows of J's size class: workgroup i takes d_win[i] with d_args[i] (both on the device)
+void marg_dense_launch(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs* d_args, int stage, int n = 1) {
   if (J.large || J.pd > MARG_SMALL_PRIOR)
-    hipLaunchKernelGGL((marg_dense_kernel<MAX_D, MAX_MARG_DIM>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES_LARGE * 8, s->stream, d_win, 0,
-                       args, MARG_LDS_DOUBLES_LARGE, stage);
+    hipLaunchKernelGGL((marg_dense_kernel<MAX_D, MAX_MARG_DIM>), dim3((unsigned)n), dim3(MARG_THREADS), MARG_LDS_DOUBLES_LARGE * 8, s->stream, d_win,
+                       d_args, MARG_LDS_DOUBLES_LARGE, stage);
   else
-    hipLaunchKernelGGL((marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3(1), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8, s->stream, d_win, 0,
-                       args, MARG_LDS_DOUBLES, stage);
+    hipLaunchKernelGGL((marg_dense_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3((unsigned)n), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8, s->stream, d_win,
+                       d_args, MARG_LDS_DOUBLES, stage);
 }
-// The dense tail of one window, on the single workgroup or on the tiled route (mt: where that route leaves its verdict).
-void marg_tail(okvis_ba_solver* s, const MargJob& J, unsigned char* d, const WinPtrs* d_win, const MargArgs& ma, MargTiles& mt) {
+// The dense tail of one window off the LDS route, on the single workgroup or on the tiled route (mt: where that route leaves its
+// verdict).  ma: the window's argument record, d_ma: where it lies on the device.
+void marg_tail(okvis_ba_solver* s, const MargJob& J, unsigned char* d, const WinPtrs* d_win, const MargArgs& ma, const MargArgs* d_ma, MargTiles& mt) {
   if (!J.tiles) {
-    marg_dense_launch(s, J, d_win, ma, 0);
+    marg_dense_launch(s, J, d_win, d_ma, 0);
     return;
   }
   // the single workgroup stops after M and b0; Schur complement, scaling, tiled factorisation (matrix core), L^-1 for the proof
@@ -220,13 +246,13 @@ void marg_tail(okvis_ba_solver* s, const MargJob& J, unsigned char* d, const Win
     hipLaunchKernelGGL(marg_prior_add_kernel, dim3((unsigned)(((size_t)pd * pd + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)),
                        dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
   if (nm > 0) {
-    marg_dense_launch(s, J, d_win, ma, 1 | 2 | 4);
+    marg_dense_launch(s, J, d_win, d_ma, 1 | 2 | 4);
     hipLaunchKernelGGL(marg_M_kernel, dim3((unsigned)(((size_t)na * nm + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0,
                        s->stream, d_win, ma);
     hipLaunchKernelGGL(marg_b0_kernel, dim3((unsigned)((na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS)), dim3(MARG_TILES_THREADS), 0, s->stream,
                        d_win, ma);
   } else {
-    marg_dense_launch(s, J, d_win, ma, 1 | 2);   // (nothing to eliminate densely: b0 is a gather)
+    marg_dense_launch(s, J, d_win, d_ma, 1 | 2);   // (nothing to eliminate densely: b0 is a gather)
   }
   const unsigned nb2 = (unsigned)(((size_t)na * na + MARG_TILES_THREADS - 1) / MARG_TILES_THREADS);
   hipLaunchKernelGGL(marg_schur_kernel, dim3(nb2), dim3(MARG_TILES_THREADS), 0, s->stream, d_win, ma);
@@ -241,12 +267,10 @@ void marg_tail(okvis_ba_solver* s, const MargJob& J, unsigned char* d, const Win
   hipLaunchKernelGGL(marg_tiles_decide_kernel, dim3(1), dim3(MARG_THREADS), 0, s->stream, ma, mt);
 }
 // No proof of full rank on the tiled route (a rank-deficient kept block, a pivot that is not positive): the single workgroup takes
-// over — the previous prior is part of H already, everything else is done again — and goes on to the eigen-decomposition
-void marg_tiles_fallback(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs& ma) {
-  MargArgs again = ma;
-  again.prior_dim = 0;
-  again.prior_nb = 0;
-  marg_dense_launch(s, J, d_win, again, 0);
+// over — the previous prior is part of H already, everything else is done again — and goes on to the eigen-decomposition.
+// d_again: the window's argument record without the previous prior (prior_dim = prior_nb = 0), which went up with the call's copy.
+void marg_tiles_fallback(okvis_ba_solver* s, const MargJob& J, const WinPtrs* d_win, const MargArgs* d_again) {
+  marg_dense_launch(s, J, d_win, d_again, 0);
   s->marg_tiles_fallbacks++;
 }
 // what is known without the numbers: the blocks the new prior connects
@@ -292,113 +316,9 @@ int marg_hand_over(okvis_ba_solver* s, const okvis_ba_solver::MargPending::Item&
   return OKVIS_BA_OK;
 }
 
-}  // namespace
-
-int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
-  if (int rc = okvis_ba_marginalize_begin(s, w, spec, res)) return rc;
-  return okvis_ba_marginalize_end(s, res);
-}
-
-int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
-  if (s) s->acc_fresh = false;
-  if (!s || !spec || !res) return OKVIS_BA_ERR_ARG;
-  if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
-  MargJob J;
-  if (int rc = marg_check(s, w, spec, res, J)) return rc;
-  const HostWin& H = s->wins[w];
-  HIP_TRY(hipSetDevice(s->device));
-
-  // ---- one scratch allocation ----
-  Arena A;
-  marg_place_host(A, H, J);
-  const size_t o_win = A.alloc(sizeof(WinPtrs)), o_opt = A.alloc(sizeof(OptD));
-  const size_t host_part = A.size;   // everything up to here is written by the host: ONE copy
-  marg_place_work(A, J);
-  marg_place_out(A, J);
-  marg_place_tiles(A, J);
-  s->stage_marg.resize(host_part);   // page-locked: the one upload of this call is a true asynchronous copy
-  unsigned char* const hb = s->stage_marg.data();
-  marg_fill_host(hb, H, J);
-  if (int rc = marg_reserve_scratch(s, A.size)) return rc;
-  unsigned char* d = s->marg_scratch;
-  const WinPtrs P = marg_win_copy(d, H, J);
-  std::memcpy(&hb[o_win], &P, sizeof(P));
-  const WinPtrs* d_win = reinterpret_cast<const WinPtrs*>(d + o_win);
-  const OptD od = marg_optd(s);
-  std::memcpy(&hb[o_opt], &od, sizeof(od));
-  HIP_TRY(hipMemcpyAsync(d, hb, host_part, hipMemcpyHostToDevice, s->stream));
-  MargSwapOptions swap_options{s, s->d_opt};
-  s->d_opt = reinterpret_cast<OptD*>(d + o_opt);
-
-  // ---- linearise + landmark elimination + export ----
-  int rc = okvis_ba_begin(s);
-  if (rc != OKVIS_BA_OK) return rc;
-  s->begun = false;
-  HIP_TRY(launch_schur(s, sub(s->stream, Extent{w, 1, s->plan.one_helpers})));
-  if (J.large)
-    marg_export_large(s, J, d_win);
-  else
-    launch_solve_kernel(s, s->plan.solve, dim3(1, 1 + s->plan.one_helpers), s->stream, d_win, 2, s->d_ctrl + w);
-  HIP_TRY(hipGetLastError());
-  MargArgs ma;
-  marg_args(d, J, ma);
-  MargTiles mt{};
-  marg_tail(s, J, d, d_win, ma, mt);
-  HIP_TRY(hipGetLastError());
-  // H | J | b0 | e0 | info are contiguous on the device: one copy into page-locked staging, one synchronisation
-  const bool tiles = J.tiles;
-  const size_t out_bytes = J.out_bytes, info_bytes = 8 * sizeof(int);
-  s->stage_dl.resize(out_bytes + info_bytes + sizeof(int));
-  int* const tiles_ok = reinterpret_cast<int*>(s->stage_dl.data() + out_bytes + info_bytes);
-  // (the tiled route may have to fall back on the single workgroup, which needs this call's arguments: it is waited for here;
-  //  the route of the pipeline's sizes only enqueues the copy and leaves the wait to okvis_ba_marginalize_end)
-  auto fetch = [&]() -> hipError_t {
-    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), ma.out_H, out_bytes + info_bytes, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && tiles) e = hipMemcpyAsync(tiles_ok, mt.ok, sizeof(int), hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess && tiles) e = hipStreamSynchronize(s->stream);
-    return e;
-  };
-  *tiles_ok = 1;
-  HIP_TRY(fetch());
-  if (tiles && !*tiles_ok) {
-    marg_tiles_fallback(s, J, d_win, ma);
-    HIP_TRY(hipGetLastError());
-    *tiles_ok = 1;
-    hipError_t e = hipMemcpyAsync(s->stage_dl.data(), ma.out_H, out_bytes + info_bytes, hipMemcpyDeviceToHost, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    HIP_TRY(e);
-  }
-  okvis_ba_solver::MargPending& mp = s->marg_pending;
-  mp.items.assign(1, okvis_ba_solver::MargPending::Item{});
-  marg_pending_item(J, 0, mp.items[0]);
-  marg_report_blocks(mp.items[0], res);
-  mp.active = true;
-  mp.batch = false;
-  mp.synced = tiles;
-  return OKVIS_BA_OK;
-}
-
-int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* res) {
-  if (!s || !res) return OKVIS_BA_ERR_ARG;
-  okvis_ba_solver::MargPending& mp = s->marg_pending;
-  if (!mp.active || mp.batch) return OKVIS_BA_ERR_STATE;   // (a pending batch is ended by okvis_ba_marginalize_batch_end)
-  // the result structure is looked at first: a call with too little room changes nothing and can be repeated with more
-  if (!marg_result_has_room(mp.items[0], res)) return OKVIS_BA_ERR_ARG;
-  mp.active = false;   // (whatever happens below, the call is over)
-  HIP_TRY(hipSetDevice(s->device));
-  if (!mp.synced) HIP_TRY(hipStreamSynchronize(s->stream));
-  if (int rc = marg_hand_over(s, mp.items[0], res)) return rc;
-  s->acc_fresh = true;
-  return OKVIS_BA_OK;
-}
-
-// ---- a range of windows in one call ----
-int okvis_ba_marginalize_batch(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
-  if (int rc = okvis_ba_marginalize_batch_begin(s, w0, n, specs, results)) return rc;
-  return okvis_ba_marginalize_batch_end(s, results);
-}
-
-int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
+// The first half of a call for windows w0 .. w0 + n - 1: everything is enqueued, the kept blocks are reported.  `batch`: which of
+// the two _end entries ends it.
+int marg_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results, bool batch) {
   if (s) s->acc_fresh = false;
   if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
   if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
@@ -420,20 +340,26 @@ int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const ok
   }
   for (int i = 0; i < n; ++i) marg_place_out(A, jobs[i]);
   const size_t out_base = jobs[0].o_out, out_total = A.size - out_base;   // ONE copy back
-  s->stage_marg.resize(host_part);
+  s->stage_marg.resize(host_part);   // page-locked: the one upload of this call is a true asynchronous copy
   unsigned char* const hb = s->stage_marg.data();
   if (int rc = marg_reserve_scratch(s, A.size)) return rc;
   unsigned char* d = s->marg_scratch;
   std::vector<MargArgs> args((size_t)n);
-  bool all_lds = true, any_small = false;
+  bool any_small = false;
   for (int i = 0; i < n; ++i) {
     const HostWin& H = s->wins[w0 + i];
-    marg_fill_host(hb, H, jobs[i]);
-    const WinPtrs P = marg_win_copy(d, H, jobs[i]);
+    const MargJob& J = jobs[i];
+    marg_fill_host(hb, H, J);
+    const WinPtrs P = win_with_export(H, d, J.ex);
     std::memcpy(&hb[o_wins + sizeof(WinPtrs) * (size_t)i], &P, sizeof(P));
-    marg_args(d, jobs[i], args[i]);
-    all_lds = all_lds && jobs[i].lds_route;
-    any_small = any_small || !jobs[i].large;
+    marg_args(d, J, args[i]);
+    if (J.tiles) {   // what marg_tiles_fallback launches with: the previous prior is part of H by then
+      MargArgs again = args[i];
+      again.prior_dim = 0;
+      again.prior_nb = 0;
+      std::memcpy(&hb[J.o_again], &again, sizeof(again));
+    }
+    any_small = any_small || !J.large;
   }
   std::memcpy(&hb[o_args], args.data(), sizeof(MargArgs) * (size_t)n);
   const WinPtrs* d_wins = reinterpret_cast<const WinPtrs*>(d + o_wins);
@@ -445,17 +371,10 @@ int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const ok
   s->d_opt = reinterpret_cast<OptD*>(d + o_opt);
 
   // ---- linearise + landmark elimination + export: one launch each for the range ----
-  // Helper workgroups as the plan's own extents have them: up to SOLVE_HELPED_MAX_WINDOWS windows they sum the Schur chunk partials,
-  // longer ranges sum inside the solving workgroup.  Both add a chunk's partials in chunk order starting from zero (ba_solve.hpp),
-  // so a window's exported system has the bits of the single call's either way.
   int rc = okvis_ba_begin(s);
   if (rc != OKVIS_BA_OK) return rc;
   s->begun = false;
-  const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
-  HIP_TRY(launch_schur(s, sub(s->stream, Extent{w0, n, helpers})));
-  // (windows assembled in HBM leave this launch at once: their export follows, window by window)
-  if (any_small && s->plan.solve.k) launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(schur_and_export(s, w0, n, d_wins, any_small));
   // ---- the dense tail: a workgroup per window, one launch per run of consecutive windows on the LDS route (a range of the
   //      pipeline's sizes is one run) ----
   for (int i = 0; i < n;) {
@@ -465,34 +384,40 @@ int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const ok
     }
     int j = i;
     while (j < n && jobs[j].lds_route) ++j;
-    hipLaunchKernelGGL((marg_dense_batch_kernel<MAX_D_LDS, MARG_SMALL_PRIOR>), dim3((unsigned)(j - i)), dim3(MARG_THREADS), MARG_LDS_DOUBLES * 8,
-                       s->stream, d_wins + i, d_args + i, MARG_LDS_DOUBLES, 0);
+    marg_dense_launch(s, jobs[i], d_wins + i, d_args + i, 0, j - i);
     i = j;
   }
   HIP_TRY(hipGetLastError());
   s->stage_dl.resize(out_total + sizeof(int));
   int* const tiles_ok = reinterpret_cast<int*>(s->stage_dl.data() + out_total);
-  // ---- windows off the LDS route, one after the other as okvis_ba_marginalize serves them (HBM workspace, tiled tail and its
-  //      fall-back, which needs the call's arguments: waited for here) ----
-  for (int i = 0; i < n && !all_lds; ++i) {
+  // ---- windows off the LDS route, one after the other (HBM workspace, tiled tail and its fall-back, which is decided on the
+  //      host: waited for here) ----
+  int last_off = -1;
+  for (int i = 0; i < n; ++i)
+    if (!jobs[i].lds_route) last_off = i;
+  bool copied = false;   // every window's H | J | b0 | e0 | info in ONE copy; the wait is marg_end's
+  for (int i = 0; i <= last_off; ++i) {
     const MargJob& J = jobs[i];
     if (J.lds_route) continue;
     if (J.large) marg_export_large(s, J, d_wins + i);
     MargTiles mt{};
-    marg_tail(s, J, d, d_wins + i, args[i], mt);
+    marg_tail(s, J, d, d_wins + i, args[i], d_args + i, mt);
     HIP_TRY(hipGetLastError());
     if (J.tiles) {
+      // (behind the last such window nothing else is enqueued: the numbers travel in front of the verdict instead of behind a second
+      //  wait, and once more in the rare case that the verdict asks for the fall-back)
+      if (i == last_off) HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
       *tiles_ok = 1;
       HIP_TRY(hipMemcpyAsync(tiles_ok, mt.ok, sizeof(int), hipMemcpyDeviceToHost, s->stream));
       HIP_TRY(hipStreamSynchronize(s->stream));
+      copied = i == last_off && *tiles_ok;
       if (!*tiles_ok) {
-        marg_tiles_fallback(s, J, d_wins + i, args[i]);
+        marg_tiles_fallback(s, J, d_wins + i, reinterpret_cast<const MargArgs*>(d + J.o_again));
         HIP_TRY(hipGetLastError());
       }
     }
   }
-  // every window's H | J | b0 | e0 | info in one copy; the wait is okvis_ba_marginalize_batch_end's
-  HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
+  if (!copied) HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
   okvis_ba_solver::MargPending& mp = s->marg_pending;
   mp.items.assign((size_t)n, okvis_ba_solver::MargPending::Item{});
   for (int i = 0; i < n; ++i) {
@@ -500,15 +425,15 @@ int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const ok
     marg_report_blocks(mp.items[i], &results[i]);
   }
   mp.active = true;
-  mp.batch = true;
-  mp.synced = false;
+  mp.batch = batch;
   return OKVIS_BA_OK;
 }
 
-int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* results) {
+// The second half: the wait and every window's numbers.
+int marg_end(okvis_ba_solver* s, okvis_ba_marg_result* results, bool batch) {
   if (!s || !results) return OKVIS_BA_ERR_ARG;
   okvis_ba_solver::MargPending& mp = s->marg_pending;
-  if (!mp.active || !mp.batch) return OKVIS_BA_ERR_STATE;   // (a pending single call is ended by okvis_ba_marginalize_end)
+  if (!mp.active || mp.batch != batch) return OKVIS_BA_ERR_STATE;   // (a pending call is ended by the _end of its own pair)
   // every result structure is looked at first: a call with too little room anywhere changes nothing and can be repeated with more
   for (size_t i = 0; i < mp.items.size(); ++i)
     if (!marg_result_has_room(mp.items[i], &results[i])) return OKVIS_BA_ERR_ARG;
@@ -523,4 +448,24 @@ int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* res
   if (rc != OKVIS_BA_OK) return rc;
   s->acc_fresh = true;
   return OKVIS_BA_OK;
+}
+
+}  // namespace
+
+int okvis_ba_marginalize_begin(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
+  return marg_begin(s, w, 1, spec, res, false);
+}
+int okvis_ba_marginalize_end(okvis_ba_solver* s, okvis_ba_marg_result* res) { return marg_end(s, res, false); }
+int okvis_ba_marginalize(okvis_ba_solver* s, int w, const okvis_ba_marg_spec* spec, okvis_ba_marg_result* res) {
+  if (int rc = marg_begin(s, w, 1, spec, res, false)) return rc;
+  return marg_end(s, res, false);
+}
+
+int okvis_ba_marginalize_batch_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
+  return marg_begin(s, w0, n, specs, results, true);
+}
+int okvis_ba_marginalize_batch_end(okvis_ba_solver* s, okvis_ba_marg_result* results) { return marg_end(s, results, true); }
+int okvis_ba_marginalize_batch(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results) {
+  if (int rc = marg_begin(s, w0, n, specs, results, true)) return rc;
+  return marg_end(s, results, true);
 }

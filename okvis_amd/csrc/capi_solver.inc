@@ -142,7 +142,7 @@ struct okvis_ba_solver {
   size_t arena_bytes = 0, arena_capacity = 0, wins_capacity = 0;
   WinPtrs* d_wins = nullptr;
   CtrlSlot* d_ctrl = nullptr;    // the control records of the uploaded windows (same allocation, behind the window records)
-  StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize)
+  StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize[_batch]: every window's numbers, one copy)
   StageVec stage, stage_small;   // pinned staging of the arena's data part / of the WinPtrs + OptD records (kept across uploads)
   std::vector<HostWin> wins;
   bool uploaded = false, begun = false;
@@ -158,7 +158,7 @@ struct okvis_ba_solver {
   bool patchable = false;
   std::vector<WindowStore> mirrors;
   WindowStore mirror_edit;   // okvis_ba_patch_window edits a copy: this one
-  long marg_tiles_fallbacks = 0;   // okvis_ba_marginalize calls whose tiled tail gave way to the single workgroup (diagnostics)
+  long marg_tiles_fallbacks = 0;   // windows of okvis_ba_marginalize[_batch] calls whose tiled tail gave way to the single workgroup (diagnostics)
   bool evaluated = false;      // okvis_ba_begin ran since the last upload: every IMU term's cache has been (re)built
   bool mirror_fresh = false;   // the containers hold the values the device holds (nothing optimised / set since)
   bool res_staged = false;  // stage_res holds window 0's packed results as of the last okvis_ba_finish (single-window solvers)
@@ -166,10 +166,10 @@ struct okvis_ba_solver {
   StageVec stage_marg;           // host-written part of okvis_ba_marginalize's scratch block
   StageVec stage_marg_vals;      // okvis_ba_set_marg_prior_values: the staged J | H0 | e0 span ...
   hipEvent_t ev_marg_vals = nullptr;   // ... and the event behind its copy
-  // okvis_ba_marginalize_begin / okvis_ba_marginalize_batch_begin without its _end yet: what _end needs to hand the numbers over,
-  // one item per window of the call (the kept blocks are known at begin)
+  // okvis_ba_marginalize_begin / okvis_ba_marginalize_batch_begin without its _end yet (one implementation, marg_begin / marg_end):
+  // what _end needs to hand the numbers over, one item per window of the call (the kept blocks are known at begin)
   struct MargPending {
-    bool active = false, synced = false;
+    bool active = false;
     bool batch = false;   // begun by okvis_ba_marginalize_batch_begin: ended by okvis_ba_marginalize_batch_end only, and vice versa
     struct Item {
       int w = 0, na = 0;

@@ -1,8 +1,11 @@
 """okvis_ba_marginalize_batch: a range of windows of one solver marginalised in one call.  The contract is bit-identity — on one and
 the same uploaded solver the batched call returns, for every window, the bits okvis_ba_marginalize returns for that window (H, b0, J,
-e0, dim, rank, sweeps, the block lists) — so every case compares with single calls on the same solver by np.array_equal, and with the
-oracle's MarginalizationError at the tolerances of tests/test_gpu_marginalization.py.  Shapes are that file's: the smallest at which
-each branch of the dense tail is taken."""
+e0, dim, rank, sweeps, the block lists).  The single call is the range of one window of the same implementation (marg_begin,
+capi_marginalize.inc), so np.array_equal here compares a launch over a range with launches of one window each: the helper workgroups
+or none, a workgroup of a shared dense launch or a launch of its own, the place in the call's scratch block.  What anchors the numbers
+themselves is independent of that: the oracle's MarginalizationError at the tolerances of tests/test_gpu_marginalization.py in every
+case, and profiles/marg_digest_parent.json (tools/marg_digest.py: the bits of the commit that still had two implementations).  Shapes
+are that file's: the smallest at which each branch of the dense tail is taken."""
 import ctypes as C
 
 import numpy as np
@@ -170,6 +173,49 @@ def test_mixed_routes(oracle, six):
     check(batch[1], oracle.OracleWindow(w).marginalize(*jobs[1]), 1e-8)
     check(batch[2], six.oracle[4], 1e-8)
     b.close()
+
+
+def _gauge_deficient_tiled(oracle):
+    """test_mixed_routes' window without its first-pose prior: 105 kept rows, singular along the gauge directions — the tiled route
+    finds no proof of full rank and the single workgroup takes over (marg_tiles_fallback)"""
+    w = synthetic.small_window(seed=61, K=8, L=30)
+    w.pprior_pose = np.zeros(0, np.int32); w.pprior_meas = np.zeros((0, 7)); w.pprior_sqrtinfo = np.zeros((0, 36))
+    return w, flags(w, [0], [0]) + (None,)
+
+
+def _hbm_workspace(oracle):
+    """test_window_beyond_the_lds_solve_path: D = 300, the system assembled in HBM, the large instantiation"""
+    w = synthetic.make_window(20, 30, 1.0, 2, frame_dt=0.1)
+    return w, flags(w, [0, 1], [0, 1]) + (None,)
+
+
+def _prior_of_291_rows(oracle):
+    """the second stage of test_previous_prior_of_more_than_192_rows: the large instantiation with a previous prior"""
+    w = synthetic.make_window(20, 30, 1.0, 3, frame_dt=0.1)
+    r1 = oracle.OracleWindow(w).marginalize(*flags(w, [], [0]))
+    assert r1["dim"] == 291
+    w2 = observation_free(w)
+    return w2, flags(w2, [0], []) + (dict(block_type=r1["block_type"], block_idx=r1["block_idx"], H=r1["H"], b0=r1["b0"]),)
+
+
+@pytest.mark.parametrize("case", [_gauge_deficient_tiled, _hbm_workspace, _prior_of_291_rows])
+def test_off_the_lds_route_one_window_or_in_a_range(oracle, six, case):
+    """A window off the LDS route between two on it: the single call, the batched call of that one window and the batched call of
+    all three return the same bits, and they are the oracle's numbers."""
+    from okvis_amd import solver
+    w, job = case(oracle)
+    ws, jobs = [six.ws[0], w, six.ws[4]], [six.jobs[0], job, six.jobs[4]]
+    b = solver.WindowBatch(ws, options=default_options())
+    single = b.marginalize(1, *job)
+    one = b.marginalize_batch(1, [job])
+    three = b.marginalize_batch(0, jobs)
+    b.close()
+    assert len(one) == 1 and len(three) == 3
+    same_bits(one[0], single, "batch of one")
+    same_bits(three[1], single, "inside a batch of three")
+    check(single, oracle.OracleWindow(w).marginalize(*job), 1e-8)
+    if case is _gauge_deficient_tiled:   # the tiled route ends only with a proof of full rank: the fall-back ran
+        assert single["rank"] < single["dim"] and single["dim"] > 96, (single["rank"], single["dim"])
 
 
 def test_two_halves(six):
