@@ -707,6 +707,75 @@ int okvis_ba_landmark_covariance(okvis_ba_solver* s, int w0, int n,
  * (cov_pose_kernel) and the landmark stage (lmcov_kernel and, with V / W taps, their copy).  OKVIS_BA_ERR_STATE before the first call. */
 int okvis_ba_last_landmark_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* inverse_ms, float* landmark_ms);
 
+/* ---- predicted measurement covariance -----------------------------------------------------------------
+ * How certain a landmark's predicted pixel is: what a 3D-2D matching gate needs.  A query (lm, pose, ext, cam) has the meaning of a
+ * row of obs_lm / obs_pose / obs_ext / obs_cam: landmark l seen from T_WS = pose[pose] through T_SC = pose[ext] with the intrinsics
+ * of `cam`, at the state the solver holds.  It need not be an observation of the window; the normal case is a landmark projected
+ * into the newest state, which observes nothing yet.
+ *     uv = projectHomogeneous(T_SC^-1 T_WS^-1 hp_W)
+ * and J_l (2 x 3), J_p (2 x 6), J_e (2 x 6) are its derivatives in the solver's tangent coordinates: the landmark's first three
+ * stored coordinates, and (r, alpha) of PoseLocalParameterization — the minimal Jacobians of
+ * ReprojectionError::EvaluateWithMinimalJacobians (implementation/ReprojectionError.hpp:87-242) with squareRootInformation_ = I,
+ * no loss, and the sign of the residual removed.  With S0, V_l, W_l, G_l = W_l V_l^-1, P and rows_l exactly as for
+ * okvis_ba_landmark_covariance, rows_x the reduced rows of the query's free pose / ext blocks (a fixed block has no rows and
+ * contributes nothing) and R = rows_l u rows_x:
+ *     A = J_x E_x - J_l G_l^T E_l            (2 x |R|; E_x, E_l place the blocks' columns into R; where a query block is also one
+ *                                             of the landmark's blocks the two contributions add)
+ *     U = J_l V_l^-1 J_l^T + A P[R, R] A^T   (2 x 2)
+ * This is J Sigma J^T for J = [J_l J_p J_e] and Sigma the corresponding block of the inverse of the full undamped normal matrix:
+ * the marginals Sigma_l and Sigma_xx and the cross term Sigma_lx = -G_l^T P[rows_l, rows_x] are all included.  It is computed in
+ * this form, a sum of two positive semi-definite terms: the large world-frame terms cancel inside A, before P is applied.  U holds
+ * no keypoint measurement noise; the gate adds that.  uv and cov go unchanged into okvis_fe_gate_3d2d (okvis_amd_frontend.h).
+ * The reference computes nothing of the kind: VioKeyframeWindowMatchingAlgorithm::doSetup (VioKeyframeWindowMatchingAlgorithm.cpp:
+ * 200-207) gates with a velocity-scaled pose uncertainty as a stand-in, which this replaces; only the projection Jacobians have
+ * reference lines (above).
+ *
+ * okvis_ba_predicted_measurement serves windows w0 .. w0 + n - 1 in one call, specs[i] / results[i] for window w0 + i, on the
+ * assembly of okvis_ba_state_covariance (one linearisation for the range), then P for every window (an entry of P has the bits
+ * okvis_ba_state_covariance returns for it) and one launch over every query of every window; one copy up, one copy back, one
+ * synchronisation.  A query's numbers have the same bits alone, in any list and in any range of windows.  The solver is left bit
+ * for bit as it was, as by okvis_ba_state_covariance.
+ *  - spec: n_q >= 0 queries (n_q = 0 is served: nothing for that window); repeats allowed (identical rows).
+ *  - result->flags[i] bit 1 (value 1): no covariance — the landmark has no pair, V_l is not positive definite by the three minors
+ *    (the rule of okvis_ba_landmark_covariance), or the result is not finite.  cov is NaN; uv is still given.
+ *    bit 2 (value 2): the point does not project, by the rule of the linearisation (where the reference leaves the projection
+ *    undefined, or the point lies less than 0.2 in front of the camera): uv, cov and jac are NaN.
+ *    Neither bit changes info or the return code.
+ *  - result->info = 1 when S0 cannot be inverted (the rule of okvis_ba_state_covariance): every cov of that window is NaN, every
+ *    flag has bit 1 (uv is still the projection), the other windows are filled as usual and the call returns
+ *    OKVIS_BA_ERR_NUMERIC.  min_pivot as okvis_ba_cov_result.
+ *  - result->S0 / Spp / V / W (each NULL or room for [D][D], [Dp][Dp], [n_lm of the window][6], [n_pair][18] doubles) are the
+ *    referee's taps: the very arrays the kernels read.  result->jac (NULL or [n][30]) is the Jacobians the kernel formed,
+ *    J_l | J_p | J_e row-major — all three, also of a fixed block, whose columns do not enter U.
+ *  - OKVIS_BA_ERR_ARG, with nothing enqueued and no result touched: NULL arguments (uv, cov and flags among them, and a query array
+ *    with n_q > 0), a range outside the batch, n_q < 0, an index out of range, capacity < n_q, or a query whose ext and pose name
+ *    the same block.
+ *  - OKVIS_BA_ERR_UNSUPPORTED and OKVIS_BA_ERR_STATE as for okvis_ba_landmark_covariance. */
+#define OKVIS_BA_PRED_NO_COV 1         /* flags bit 1 */
+#define OKVIS_BA_PRED_NO_PROJECTION 2  /* flags bit 2 */
+
+typedef struct okvis_ba_pred_spec {
+  int32_t n_q;
+  const int32_t *q_lm, *q_pose, *q_ext, *q_cam;   /* [n_q] each, as obs_lm / obs_pose / obs_ext / obs_cam */
+} okvis_ba_pred_spec;
+
+typedef struct okvis_ba_pred_result {
+  int32_t capacity;          /* in: queries uv / cov / flags (and jac) have room for */
+  int32_t n, info;           /* out */
+  double min_pivot;          /* out, as okvis_ba_cov_result */
+  double* uv;                /* [n][2] */
+  double* cov;               /* [n][4] row-major, bitwise symmetric */
+  uint8_t* flags;            /* [n] OKVIS_BA_PRED_* */
+  double *S0, *Spp, *V, *W;  /* referee's taps, each NULL or [D][D], [Dp][Dp], [n_lm of the window][6], [n_pair][18] */
+  double* jac;               /* NULL or [n][30]: J_l [2][3] | J_p [2][6] | J_e [2][6] row-major */
+} okvis_ba_pred_result;
+
+int okvis_ba_predicted_measurement(okvis_ba_solver* s, int w0, int n,
+                                   const okvis_ba_pred_spec* specs, okvis_ba_pred_result* results);
+/* Measurement hook (HIP events of the last successful okvis_ba_predicted_measurement): its assembly launches, the inverse stage
+ * (cov_pose_kernel) and the query stage (predcov_kernel and, with V / W taps, their copy).  OKVIS_BA_ERR_STATE before the first call. */
+int okvis_ba_last_predicted_measurement_ms(okvis_ba_solver* s, float* assembly_ms, float* inverse_ms, float* query_ms);
+
 /* ---- multi-GPU driver --------------------------------------------------------------
  * Windows are independent units: window i of a job runs on rank i mod world, one process per GPU, no data-path
  * collective.  The only exchange is ONE all-gather of these fixed-size records after all windows finished (RCCL over

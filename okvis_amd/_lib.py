@@ -4,7 +4,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 
-from .window import CovResultC, CovSpecC, LimitsC, LmcovResultC, LmcovSpecC, MargResultC, MargSpecC, OptionsC, PatchC, SummaryC, WindowC
+from .window import CovResultC, CovSpecC, LimitsC, LmcovResultC, LmcovSpecC, MargResultC, MargSpecC, OptionsC, PatchC, PredResultC, PredSpecC, SummaryC, WindowC
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OKVIS_AMD_LIB_DIR: a directory holding an instrumented build of the same sources — scripts/host_sanitize.sh)
@@ -22,6 +22,7 @@ SYMBOLS = [
     "okvis_ba_marginalize_batch", "okvis_ba_marginalize_batch_begin", "okvis_ba_marginalize_batch_end",
     "okvis_ba_state_covariance", "okvis_ba_last_covariance_ms",
     "okvis_ba_landmark_covariance", "okvis_ba_last_landmark_covariance_ms",
+    "okvis_ba_predicted_measurement", "okvis_ba_last_predicted_measurement_ms",
     "okvis_ba_store_create", "okvis_ba_store_patch", "okvis_ba_store_view", "okvis_ba_store_destroy", "okvis_ba_set_patchable",
     "okvis_ba_patch_window", "okvis_ba_patched_view", "okvis_ba_set_marg_prior_values",
     "okvis_ba_dense_solve", "okvis_ba_reduced_solve", "okvis_ba_shard", "okvis_ba_batch_run", "okvis_ba_gather_records", "okvis_ba_batch_run_gathered",
@@ -95,6 +96,8 @@ def lib():
     L.okvis_ba_last_covariance_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.okvis_ba_landmark_covariance.argtypes = [vp, C.c_int, C.c_int, C.POINTER(LmcovSpecC), C.POINTER(LmcovResultC)]
     L.okvis_ba_last_landmark_covariance_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 3
+    L.okvis_ba_predicted_measurement.argtypes = [vp, C.c_int, C.c_int, C.POINTER(PredSpecC), C.POINTER(PredResultC)]
+    L.okvis_ba_last_predicted_measurement_ms.argtypes = [vp] + [C.POINTER(C.c_float)] * 3
     L.okvis_ba_evaluate_cost.argtypes = [vp, _dp]
     L.okvis_ba_array_size.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]
     L.okvis_ba_download.argtypes = [vp, C.c_int, C.c_int, _dp, C.c_int64]

@@ -19,6 +19,7 @@
 #include "ba_chol_tiles.hpp"
 #include "ba_cov.hpp"
 #include "ba_lmcov.hpp"
+#include "ba_predcov.hpp"
 #include "ba_linearize.hpp"
 #include "ba_linearize2.hpp"
 #include "ba_schur2.hpp"
@@ -35,7 +36,7 @@ using namespace ba;
 #include "capi_index_build.inc"   // batch_layout, build_batch, build_window and its helpers (the index build)
 #include "capi_launch.inc"        // LDS sizes, the launch plan (make_plan) and the launches, sub-batch fork / join
 // below: life cycle, options, upload / patch, state, begin / iterate / finish, queries and downloads, measurement hooks; then
-// capi_standalone.inc, capi_marginalize.inc, capi_covariance.inc and capi_landmark_covariance.inc
+// capi_standalone.inc, capi_marginalize.inc, capi_covariance.inc, capi_landmark_covariance.inc and capi_predicted_measurement.inc
 
 // okvis_ba_marginalize_end / _batch_end first: between the two halves of a marginalisation the solver takes no edits and hands out
 // no results
@@ -148,6 +149,8 @@ int okvis_ba_destroy(okvis_ba_solver* s) {
   for (auto ev : s->ev_cov)
     if (ev) (void)hipEventDestroy(ev);
   for (auto ev : s->ev_lmcov)
+    if (ev) (void)hipEventDestroy(ev);
+  for (auto ev : s->ev_pred)
     if (ev) (void)hipEventDestroy(ev);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
@@ -1244,5 +1247,6 @@ int okvis_ba_synchronize(okvis_ba_solver* s) {
 
 #include "capi_covariance.inc"    // okvis_ba_state_covariance
 #include "capi_landmark_covariance.inc"   // okvis_ba_landmark_covariance
+#include "capi_predicted_measurement.inc"   // okvis_ba_predicted_measurement
 
 }  // extern "C"

@@ -192,6 +192,7 @@ struct okvis_ba_solver {
   unsigned char* marg_scratch = nullptr;  // grow-only device scratch of okvis_ba_marginalize
   hipEvent_t ev_cov[3] = {nullptr, nullptr, nullptr};   // okvis_ba_state_covariance: in front of the assembly | of cov_kernel | behind it
   hipEvent_t ev_lmcov[4] = {nullptr, nullptr, nullptr, nullptr};   // okvis_ba_landmark_covariance: in front of the assembly | of cov_pose_kernel | of lmcov_kernel | behind it
+  hipEvent_t ev_pred[4] = {nullptr, nullptr, nullptr, nullptr};    // okvis_ba_predicted_measurement: in front of the assembly | of cov_pose_kernel | of predcov_kernel | behind it
   size_t marg_scratch_bytes = 0;
 };
 

@@ -351,6 +351,82 @@ class WindowBatch:
         _lib.check(self._L.okvis_ba_last_landmark_covariance_ms(self._h, C.byref(a), C.byref(k), C.byref(l)), "last_landmark_covariance_ms")
         return dict(assembly=a.value, inverse=k.value, landmark=l.value)
 
+    def newest_state_queries(self, w: int = 0) -> np.ndarray:
+        """The default queries of predicted_measurement for window w, [n_q][4] (lm, pose, ext, cam): every landmark into the newest
+        state — the pose block the window's last IMU term ends at, or without IMU terms the highest pose index an observation
+        names — through each (extrinsics, camera) pair the window uses for it: the pairs of that state's own observations, or,
+        where it observes nothing yet, those of the newest state that does.  Camera by camera, landmarks in window order."""
+        W = self.windows[w]
+        op, oe, oc = (np.asarray(a).reshape(-1) for a in (W.obs_pose, W.obs_ext, W.obs_cam))
+        if op.size == 0:
+            return np.zeros((0, 4), np.int32)
+        newest = int(np.asarray(W.imu_pose1).reshape(-1)[-1]) if W.n_imu else int(op.max())
+        at = op == (newest if np.any(op == newest) else int(op.max()))
+        pairs = sorted(set(zip(oc[at].tolist(), oe[at].tolist())))
+        lm = np.arange(W.n_lm)
+        return np.concatenate([np.stack([lm, np.full_like(lm, newest), np.full_like(lm, e), np.full_like(lm, c)], 1) for c, e in pairs]).astype(np.int32)
+
+    def predicted_measurement(self, queries=None, w0: int = 0, n: int | None = None, want_taps: bool = False) -> list:
+        """okvis_ba_predicted_measurement on windows w0 .. w0 + n - 1 (default: to the end of the batch): for every query (lm, pose,
+        ext, cam) — the meaning of an observation row; it need not be one — the predicted pixel uv and its 2 x 2 covariance under the
+        joint uncertainty of landmark, pose and extrinsics at the state the solver holds, ``J_l V^-1 J_l^T + A P[R, R] A^T`` with
+        ``A = J_x E_x - J_l G^T E_l`` (include/okvis_amd_ba.h has the definition).  No keypoint noise is included.  queries: None =
+        newest_state_queries of every window, one [n_q][4] integer array for every window, or a list of such arrays (an entry may
+        be None).  One linearisation, one copy each way and one synchronisation for the range; the solver is left as it was.  Per
+        window a dict uv [n_q][2], cov [n_q][2][2], flags [n_q] (uint8: bit 1 = no covariance, cov NaN; bit 2 = the point does not
+        project, uv and cov NaN), info, min_pivot and, with want_taps, S0, Spp, V, W (the arrays the kernels read) and jac
+        [n_q][30] (J_l | J_p | J_e as the kernel formed them).  uv and cov go unchanged into ``Frontend.gate_3d2d``.  A window with
+        info = 1 has every cov NaN and bit 1 set everywhere; the call then raises BackendError (OKVIS_BA_ERR_NUMERIC) whose
+        ``results`` attribute holds the list."""
+        from .window import predcov_marshal_batch
+        w0 = int(w0)
+        n = len(self.windows) - w0 if n is None else int(n)
+        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
+            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        if queries is None:
+            qs = [None] * n
+        elif isinstance(queries, np.ndarray) and queries.ndim == 2:
+            qs = [queries] * n
+        else:
+            qs = list(queries)
+            if len(qs) != n:
+                raise ValueError(f"{len(qs)} query lists for {n} windows")
+        qs = [self.newest_state_queries(w0 + i) if q is None else np.asarray(q, np.int32).reshape(-1, 4) for i, q in enumerate(qs)]
+        taps = None
+        if want_taps:
+            taps = []
+            for i in range(n):
+                W = self.windows[w0 + i]
+                np_ = C.c_int32()
+                _lib.check(self._L.okvis_ba_pair_count(self._h, w0 + i, C.byref(np_)))
+                taps.append((self.reduced_dim(w0 + i), 6 * int((np.asarray(W.pose_fixed).reshape(-1) == 0).sum()), int(W.n_lm), np_.value))
+        specs, results, outs, keep = predcov_marshal_batch(qs, taps)
+        st = self._L.okvis_ba_predicted_measurement(self._h, w0, n, specs, results)
+        del keep
+        if st not in (0, -5):
+            _lib.check(st, "predicted_measurement")
+        res = []
+        for i in range(n):
+            m = int(results[i].n)
+            r = dict(uv=outs[i]["uv"][:m].copy(), cov=outs[i]["cov"][:m].reshape(m, 2, 2).copy(), flags=outs[i]["flags"][:m].copy(),
+                     info=int(results[i].info), min_pivot=float(results[i].min_pivot))
+            if want_taps:
+                r.update({k: outs[i][k].copy() for k in ("S0", "Spp", "V", "W")})
+                r["jac"] = outs[i]["jac"][:m].copy()
+            res.append(r)
+        if st != 0:
+            err = _lib.BackendError(st, "predicted_measurement")
+            err.results = res
+            raise err
+        return res
+
+    def last_predicted_measurement_ms(self) -> dict:
+        """okvis_ba_last_predicted_measurement_ms: HIP-event times of the last predicted_measurement call's assembly launches, of the
+        inverse stage (all pose-type columns of the reduced system's inverse) and of the query stage"""
+        a, k, q = C.c_float(), C.c_float(), C.c_float()
+        _lib.check(self._L.okvis_ba_last_predicted_measurement_ms(self._h, C.byref(a), C.byref(k), C.byref(q)), "last_predicted_measurement_ms")
+        return dict(assembly=a.value, inverse=k.value, query=q.value)
+
     def synchronize(self):
         _lib.check(self._L.okvis_ba_synchronize(self._h), "synchronize")
 

@@ -130,6 +130,18 @@ class LmcovResultC(C.Structure):
                 ("cov", _dp), ("flags", _bp), ("S0", _dp), ("Spp", _dp), ("V", _dp), ("W", _dp)]
 
 
+class PredSpecC(C.Structure):
+    """ctypes image of ``okvis_ba_pred_spec``."""
+    _fields_ = [("n_q", C.c_int32), ("q_lm", _ip), ("q_pose", _ip), ("q_ext", _ip), ("q_cam", _ip)]
+
+
+class PredResultC(C.Structure):
+    """ctypes image of ``okvis_ba_pred_result``."""
+    _fields_ = [("capacity", C.c_int32), ("n", C.c_int32), ("info", C.c_int32), ("min_pivot", C.c_double),
+                ("uv", _dp), ("cov", _dp), ("flags", _bp), ("S0", _dp), ("Spp", _dp), ("V", _dp), ("W", _dp), ("jac", _dp)]
+
+
+PRED_NO_COV, PRED_NO_PROJECTION = 1, 2   # OKVIS_BA_PRED_*
 BLOCK_POSE, BLOCK_SPEEDBIAS = 0, 1   # OKVIS_BA_BLOCK_*
 COV_MAX_WINDOW_DIM, COV_MAX_DIM = 174, 30   # OKVIS_BA_COV_MAX_WINDOW_DIM, OKVIS_BA_COV_MAX_DIM
 
@@ -181,6 +193,37 @@ def lmcov_marshal_batch(selections, counts, tap_dims=None):
             D, Dp, n_lm, n_pair = (int(x) for x in tap_dims[i])
             out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)))
             for k in ("S0", "Spp", "V", "W"):
+                buf = out[k] if out[k].size else np.zeros(1)
+                keep.append(buf)
+                setattr(results[i], k, buf.ctypes.data_as(_dp))
+        outs.append(out)
+    return specs, results, outs, keep
+
+
+def predcov_marshal_batch(queries, tap_dims=None):
+    """Arrays of ``PredSpecC`` / ``PredResultC`` for okvis_ba_predicted_measurement: queries[i] = the [n_q][4] integer array (lm,
+    pose, ext, cam) of the i-th window of the range, tap_dims[i] = (D, Dp, n_lm, n_pair) when the referee's taps (and the
+    Jacobians) are wanted.  Returns (specs, results, outs, keep)."""
+    n = len(queries)
+    specs, results = (PredSpecC * max(1, n))(), (PredResultC * max(1, n))()
+    outs, keep = [], []
+    for i, q in enumerate(queries):
+        q = np.asarray(q, np.int32).reshape(-1, 4)
+        m = q.shape[0]
+        cols = [np.ascontiguousarray(q[:, k]) if m else np.zeros(1, np.int32) for k in range(4)]   # (an empty list: non-NULL pointers)
+        specs[i].n_q = m
+        for k, name in enumerate(("q_lm", "q_pose", "q_ext", "q_cam")):
+            setattr(specs[i], name, cols[k].ctypes.data_as(_ip))
+        keep += cols
+        out = dict(uv=np.zeros((max(1, m), 2)), cov=np.zeros((max(1, m), 4)), flags=np.zeros(max(1, m), np.uint8))
+        results[i].capacity = m
+        results[i].uv = out["uv"].ctypes.data_as(_dp)
+        results[i].cov = out["cov"].ctypes.data_as(_dp)
+        results[i].flags = out["flags"].ctypes.data_as(_bp)
+        if tap_dims is not None:
+            D, Dp, n_lm, n_pair = (int(x) for x in tap_dims[i])
+            out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)), jac=np.zeros((max(1, m), 30)))
+            for k in ("S0", "Spp", "V", "W", "jac"):
                 buf = out[k] if out[k].size else np.zeros(1)
                 keep.append(buf)
                 setattr(results[i], k, buf.ctypes.data_as(_dp))
