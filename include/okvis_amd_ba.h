@@ -345,6 +345,10 @@ int okvis_ba_check_window(const okvis_ba_window* w, const okvis_ba_options* opt,
 #define OKVIS_BA_LIST_CHAIN 19          /* one int: > 0 = the window (as a batch of its own) is laid out for the chain solver (okvis_ba_tuning::
                                            solve_mode, ba_chain.hpp), the value is the number of speed/bias blocks; 0 = dense LDL^T.  The mask of
                                            OKVIS_BA_LIST_LDL_COMP then counts the 16-blocks of the POSE system                         */
+#define OKVIS_BA_LIST_CHUNK_RECS 20     /* the chunk launch records of the window as a batch of its own: 128 ints per chunk, [0, 20) the chunk
+                                           descriptor, [32 + 8 b, 32 + 8 b + 8) pose block b's {chunk_diag_begin, list length, the first six
+                                           chunk_diag_out entries of the list (0 behind its end)}; empty for windows the ring loop of the
+                                           matrix-core Schur kernel does not serve (free extrinsics, pose part beyond 63 rows)         */
 int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options* opt, int32_t n_windows, int32_t which,
                                 int32_t* out, int64_t capacity, int64_t* n);
 /* ---- incremental structure updates ---------------------------------------------------------------------

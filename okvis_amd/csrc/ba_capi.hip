@@ -342,6 +342,8 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   // with more than LIN2_PIECES pieces), the chain solver where allowed if EVERY LDS-resident window fits it, else the dense LDL^T
   BatchLayout L = batch_layout(s->opt, n_windows);
   if (int rc = build_batch(windows, n_windows, s->opt, L, A, wins.data())) return rc;
+  size_t rec_off = 0;
+  const int rec_stride = build_chunk_records(A, wins.data(), n_windows, &rec_off);
   const auto t_u1 = std::chrono::steady_clock::now();
   // grow-only device allocations: the per-frame re-upload of okvis_amd::Estimator must not pay hipFree/hipMalloc
   if (A.host.size() < A.size) A.host.resize(A.size, 0);
@@ -375,7 +377,9 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
     wins[i].ptrs.ctrl = (decltype(wins[i].ptrs.ctrl))(&s->d_ctrl[i].c);   // (not the arena's slot: see CtrlSlot)
     ptrs[i] = wins[i].ptrs;
   }
-  const BatchMax M = batch_max(wins.data(), ptrs.data(), n_windows);
+  BatchMax M = batch_max(wins.data(), ptrs.data(), n_windows);
+  M.rec_stride = rec_stride;
+  s->d_recs = rec_stride ? reinterpret_cast<const int*>(s->d_arena + rec_off) : nullptr;
   {
     // one copy: option record, window records and the (zeroed) control records behind them
     const size_t wb = sizeof(WinPtrs) * (size_t)n_windows, all = records_bytes((size_t)n_windows);
@@ -532,6 +536,12 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
     case OKVIS_BA_LIST_PIECE_PATH: count = 1; break;
     case OKVIS_BA_LIST_LDL_COMP: count = 1; break;
     case OKVIS_BA_LIST_CHAIN: count = 1; break;
+    case OKVIS_BA_LIST_CHUNK_RECS: {
+      size_t off = 0;
+      const int stride = build_chunk_records(A, &H, 1, &off);   // (appends to the arena: the lists above stay where they are)
+      src = A.host.data() + off, count = (int64_t)stride * SCHUR_REC_INTS;
+      break;
+    }
     default: return OKVIS_BA_ERR_ARG;
   }
   *n = count;
@@ -1224,6 +1234,8 @@ int okvis_ba_algorithmic_bytes(okvis_ba_solver* s, int64_t* lin, int64_t* schur,
   for (auto& H : s->wins) {
     a += H.bytes_lin;
     b += H.bytes_schur;
+    // (the ring kernels read one chunk launch record per workgroup)
+    if (s->plan.rec_stride) b += (int64_t)H.n_chunk * SCHUR_REC_INTS * (int64_t)sizeof(int);
     c += H.bytes_solve;
     d += H.bytes_small;
   }

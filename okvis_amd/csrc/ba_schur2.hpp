@@ -22,6 +22,11 @@
 //     and 16 consecutive rows at stride 13 doubles write 32 distinct LDS banks.  The ring is zeroed once; a set is zeroed again, two
 //     barriers ahead of its fill, only in front of a stage that does not overwrite it (a pair missing, or the ragged last stage).
 //     The chunk's J^T J / J^T r lists are requested in front of V^-1 and summed behind the first fill.
+//     A workgroup's static structure — chunk descriptor, list ranges and list heads — is ONE launch record of whole lines whose address
+//     comes from the kernel arguments and the workgroup's indices (SCHUR_REC_INTS, ba_types.hpp; build_chunk_records): it is requested
+//     with the window record and the control words, so the first data loads leave one round trip behind the launch (head 3.5 -> 1.9 us).
+//     The output counts (block pair, entry) up from one of a work-item's entries to the next instead of dividing and searching per
+//     entry (partial stores 2.85 -> 2.2 us).  profiles/launch_records_notes.md.
 //   * the serial loop (SCH2_SERIAL; rounds 4-6): n = nlb = 12 landmarks per batch, one work-item per pair, zero / fill / products
 //     with a barrier behind each.  It stays for pose parts of several 96-row tiles (schur_mfma_kernel<9>) and, for one release, as
 //     the referee of the ring loop (okvis_ba_tuning::flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES; OKVIS_BA_ROUTE_SCHUR_KERNEL = 4).
@@ -58,7 +63,8 @@ __host__ __device__ constexpr int sch2_ring_doubles(int trows) { return SCH2_RIN
 // the pipelined loop (OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
 template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows, int final_call, int nlb,
-                                                const CtrlSlot* __restrict__ ctrls, int nodec, const int bx) {
+                                                const CtrlSlot* __restrict__ ctrls, int nodec, const int bx, const int* __restrict__ recs,
+                                                int rec_stride) {
   const WinPtrs& W = wins[blockIdx.y];
   // The control record's address comes from the kernel arguments (CtrlSlot, ba_types.hpp; == W.ctrl): its first words — accepted
   // buffer, pending, first, done — arrive together with the window record, and with them the index of the linearisation buffer
@@ -68,6 +74,28 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   const Ctrl* ctrl = &ctrls[blockIdx.y].c;
   typedef int sch2_i4 __attribute__((ext_vector_type(4)));
   const sch2_i4 chead = *reinterpret_cast<const sch2_i4*>(ctrl);   // acc, pending, first, done
+  // Pipelined loop: the chunk launch record (SCHUR_REC_INTS, ba_types.hpp; build_chunk_records) — the chunk descriptor and every
+  // pose block's list range and list head in whole lines whose address comes from the kernel arguments and the workgroup's indices
+  // (pose parts within 63 rows: one tile pair, workgroup bx = chunk bx; bx < rec_stride = the launch's Schur workgroups per window).
+  // It is requested HERE, next to the window record and the control words and by the lanes that consume its entries, so that the
+  // data loads below leave one round trip behind the launch instead of three (window record -> chunk_desc / chunk_diag_begin ->
+  // chunk_diag_out).  The slots behind a window's last chunk and the entries of absent blocks are zero.
+  const int* rec = SCH2_SERIAL ? nullptr : recs + ((size_t)blockIdx.y * rec_stride + bx) * SCHUR_REC_INTS;
+  constexpr int SCH2_RI = SCH2_SERIAL ? 1 : (SCH2_MAXT_SMALL_ROWS / 6 * 36 + SCHUR_THREADS - 1) / SCHUR_THREADS;
+  sch2_i4 rec_d[SCH2_RI][2], rec_r[2];
+  int rec_pb = 0;
+  if constexpr (!SCH2_SERIAL) {
+    static_assert(SCH2_MAXT_SMALL_ROWS / 6 <= SCHUR_REC_BLOCKS, "every pose block of a small tile has its entry in the record");
+    const int lane_ = threadIdx.x & 63;
+    rec_pb = rec[2 + min(lane_, SCHUR_CHUNK_LM_MAX / 4)];
+#pragma unroll
+    for (int it = 0; it < SCH2_RI; ++it) {   // (blocks the window does not have: zeros, what the lists below start from)
+      const sch2_i4* le = reinterpret_cast<const sch2_i4*>(rec + SCHUR_REC_LISTS + 8 * min(((int)threadIdx.x + it * SCHUR_THREADS) / 36, SCHUR_REC_BLOCKS - 1));
+      rec_d[it][0] = le[0], rec_d[it][1] = le[1];
+    }
+    const sch2_i4* le = reinterpret_cast<const sch2_i4*>(rec + SCHUR_REC_LISTS + 8 * min((int)threadIdx.x / 6, SCHUR_REC_BLOCKS - 1));
+    rec_r[0] = le[0], rec_r[1] = le[1];
+  }
   const int spec = __builtin_amdgcn_readfirstlane(chead.y ? 1 - chead.x : chead.x);
   const int n_tp = W.n_tile * (W.n_tile + 1) / 2;
   if (bx >= W.n_chunk * n_tp) return;
@@ -101,7 +129,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   const double c_mu = nodec ? ctrl->mu : 0.0, c_radius = nodec ? ctrl->radius : 1.0;
   const OptD opt = *optp;
   const int chunk = bx / n_tp;
-  const int* cd = W.chunk_desc + (size_t)chunk * SCHUR_DESC_INTS;   // lm_begin, lm_end, pair ranges: one record
+  const int* cd = SCH2_SERIAL ? W.chunk_desc + (size_t)chunk * SCHUR_DESC_INTS : rec;   // lm_begin, lm_end, pair ranges: one record
   const int lm_begin = cd[0], lm_end = cd[1];
   const int nl = lm_end - lm_begin;
 
@@ -144,7 +172,18 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
 #pragma unroll
     for (int q = 0; q < SCH2_LL; ++q) d_out[it][q] = 0;
   }
-  if (diag) {
+  if constexpr (!SCH2_SERIAL) {
+    // (from the launch record, requested at the head: list begin, length, the first SCH2_LL entries — zeros behind a list's end)
+    static_assert(SCH2_LL == SCHUR_REC_LL, "list heads of the launch record");
+#pragma unroll
+    for (int it = 0; it < SCH2_RI; ++it) {
+      d_q0[it] = rec_d[it][0].x, d_n[it] = rec_d[it][0].y;
+      d_out[it][0] = rec_d[it][0].z, d_out[it][1] = rec_d[it][0].w;
+      d_out[it][2] = rec_d[it][1].x, d_out[it][3] = rec_d[it][1].y, d_out[it][4] = rec_d[it][1].z, d_out[it][5] = rec_d[it][1].w;
+    }
+    r_q0 = rec_r[0].x, r_n = rec_r[0].y;
+    r_out[0] = rec_r[0].z, r_out[1] = rec_r[0].w, r_out[2] = rec_r[1].x, r_out[3] = rec_r[1].y, r_out[4] = rec_r[1].z, r_out[5] = rec_r[1].w;
+  } else if (diag) {
     const int* lb_ = W.chunk_diag_begin + (size_t)chunk * nblk + row0;
 #pragma unroll
     for (int it = 0; it < SCH2_DI; ++it) {
@@ -190,7 +229,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   };
   // pipelined: one range per stage of four landmarks = the descriptor's own entries, lane q of every wave holds entry q
   static_assert(SCH2_NB + 1 <= 64, "one descriptor entry per lane");
-  const int pb_lane = SCH2_SERIAL ? 0 : cd[2 + min(lane, SCH2_NB)];
+  const int pb_lane = SCH2_SERIAL ? 0 : rec_pb;
   auto pb_stage = [&](int st) { return __builtin_amdgcn_readlane(pb_lane, min(st, SCH2_NB)); };   // (st uniform)
   const int nst = (nl + SCH2_STAGE_LM - 1) / SCH2_STAGE_LM;
 
@@ -643,10 +682,22 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     __syncthreads();
     SSTAMP(22);
     const int npairs = diag ? nrow * (nrow + 1) / 2 : nrow * ncol;
+    // pipelined loop: (block pair, entry) of a work-item's entries move by SCHUR_THREADS = 7 x 36 + 4 from one to the next — counted
+    // up, with the row / column block of the lower-triangular enumeration, instead of a division, a square root and a search per entry
+    int pi_ = tid / 36, k_ = tid - 36 * pi_, bi_ = 0, bj_ = pi_;
+    while (bj_ > bi_) bj_ -= ++bi_;
     for (int e = tid; e < npairs * 36; e += SCHUR_THREADS) {
-      const int pi = e / 36, k = e - 36 * pi, ii = k / 6, jj = k - 6 * ii;
+      const int pi = SCH2_SERIAL ? e / 36 : pi_, k = SCH2_SERIAL ? e - 36 * pi : k_, ii = k / 6, jj = k - 6 * ii;
       int bi, bj;
-      if (diag) {
+      if constexpr (!SCH2_SERIAL) {
+        bi = diag ? bi_ : pi / ncol;
+        bj = diag ? bj_ : pi - bi * ncol;
+        const int wrap = k_ + SCHUR_THREADS % 36 >= 36;
+        k_ += SCHUR_THREADS % 36 - 36 * wrap;
+        pi_ += SCHUR_THREADS / 36 + wrap;
+        bj_ += SCHUR_THREADS / 36 + wrap;
+        while (bj_ > bi_) bj_ -= ++bi_;
+      } else if (diag) {
         bi = (int)((sqrtf(8.0f * pi + 1.0f) - 1.0f) * 0.5f);
         while ((bi + 1) * (bi + 2) / 2 <= pi) ++bi;
         while (bi * (bi + 1) / 2 > pi) --bi;
@@ -726,8 +777,9 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
 
 template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_mfma_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp,
-                                                                      int tile_rows, int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec) {
-  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x);
+                                                                      int tile_rows, int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec,
+                                                                      const int* __restrict__ recs, int rec_stride) {
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x, recs, rec_stride);
 }
 
 // The decision-free Schur launch with the EVALUATION of the IMU / prior factors of the same trial riding along (round 6): workgroups
@@ -738,14 +790,15 @@ __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_m
 // 62 KB of LDS of the re-preintegration path put the launch at two workgroups per CU and cost the line 6 %; this half keeps three.)
 template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
 __global__ __launch_bounds__(SCHUR_THREADS, 3) void schur_ride_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows,
-                                                                      int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec, int n_small) {
+                                                                      int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec, int n_small,
+                                                                      const int* __restrict__ recs, int rec_stride) {
   static_assert(SCHUR_THREADS == IMU_THREADS && SCHUR_THREADS == LIN_THREADS, "one block size for both kinds of workgroup");
   if ((int)blockIdx.x < n_small) {
     extern __shared__ __attribute__((aligned(16))) double sch_smem[];
     small_body<2>(wins[blockIdx.y], 0, (int)blockIdx.x, sch_smem);
     return;
   }
-  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small);
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small, recs, rec_stride);
 }
 
 }  // namespace ba

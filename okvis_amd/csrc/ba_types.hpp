@@ -19,6 +19,13 @@ constexpr int SCHUR_LM_BATCH = 16;     // landmarks staged per LDS pass in the S
 constexpr int SCHUR_CHUNK_LM_MAX = 64;   // landmarks of one Schur workgroup (chunk) = GROUP_LM: a chunk is at least one group;
                                         // more would push the kernel past 80 KB of LDS at 96-row tiles (one workgroup per CU)
 constexpr int SCHUR_DESC_INTS = 2 + SCHUR_CHUNK_LM_MAX / 4 + 1 + 1;   // chunk descriptor of the matrix-core Schur kernel (20 ints)
+// Chunk launch record of the ring instantiations of the matrix-core Schur kernel (pose parts within 63 rows: one tile pair, at most
+// SCHUR_REC_BLOCKS pose blocks): whole 128-byte lines, one record per (window, chunk) in ONE array of the batch with a fixed
+// stride per window, so that a workgroup forms its record's address from kernel arguments and blockIdx alone.
+//   [0, SCHUR_DESC_INTS)                   the chunk descriptor
+//   [SCHUR_REC_LISTS + 8 b, ... + 8)       pose block b: chunk_diag_begin, length of its list, the list's first SCHUR_REC_LL entries
+constexpr int SCHUR_REC_INTS = 128, SCHUR_REC_LISTS = 32, SCHUR_REC_LL = 6, SCHUR_REC_BLOCKS = (SCHUR_REC_INTS - SCHUR_REC_LISTS) / 8;
+static_assert(SCHUR_DESC_INTS <= SCHUR_REC_LISTS && SCHUR_REC_LL + 2 == 8, "layout of the chunk launch record");
 constexpr int SOLVE_THREADS = 1024;
 constexpr int MAX_D_LDS = 174;         // reduced systems up to this size are factorised in LDS (block-packed)
 constexpr int MAX_D = 900;             // larger ones (up to this) keep the block matrix in HBM/L2 (slower path)

@@ -1230,6 +1230,43 @@ BatchMax batch_max(const HostWin* H, WinPtrs* P, int n) {
   return M;
 }
 
+// The chunk launch records of a batch (SCHUR_REC_INTS, ba_types.hpp): what a workgroup of the ring instantiations of the matrix-core
+// Schur kernel reads before its first data load — the chunk descriptor and, per pose block, the range and the head of its list of
+// J^T J / J^T r partials — gathered from chunk_desc / chunk_diag_begin / chunk_diag_out (which stay: the serial loop, schur_kernel and
+// the fused reduction read them) into one array of the arena's data part, [window][stride][SCHUR_REC_INTS]; slots behind a window's
+// last chunk are zero (an empty chunk).  H[i].ptrs still hold arena offsets.  Returns the stride = the batch's largest chunk count,
+// or 0 = no records: a window with free extrinsics or a pose part beyond the small tiles, where make_plan selects no ring kernel.
+int build_chunk_records(Arena& A, const HostWin* H, int n, size_t* off) {
+  int stride = 0;
+  for (int i = 0; i < n; ++i) {
+    const WinPtrs& P = H[i].ptrs;
+    if (P.has_ext || !schur_small_tiles(P.Dp) || P.Dp / 6 > SCHUR_REC_BLOCKS) return 0;
+    stride = std::max(stride, P.n_chunk);
+  }
+  if (stride == 0) return 0;
+  const size_t bytes = (size_t)n * stride * SCHUR_REC_INTS * sizeof(int);
+  *off = A.alloc(bytes);
+  if (A.host.size() < A.size) A.host.resize(A.size, 0);
+  std::memset(A.host.data() + *off, 0, bytes);
+  for (int i = 0; i < n; ++i) {
+    const WinPtrs& P = H[i].ptrs;
+    auto list = [&](const void* field) { return reinterpret_cast<const int*>(A.host.data() + reinterpret_cast<size_t>(field)); };
+    const int *desc = list((const void*)P.chunk_desc), *begin = list((const void*)P.chunk_diag_begin), *out = list((const void*)P.chunk_diag_out);
+    const int nb = P.Dp / 6;
+    for (int c = 0; c < P.n_chunk; ++c) {
+      int* r = reinterpret_cast<int*>(A.host.data() + *off) + ((size_t)i * stride + c) * SCHUR_REC_INTS;
+      std::memcpy(r, desc + (size_t)c * SCHUR_DESC_INTS, SCHUR_DESC_INTS * sizeof(int));
+      for (int b = 0; b < nb; ++b) {
+        int* e = r + SCHUR_REC_LISTS + 8 * b;
+        const int q0 = begin[(size_t)c * nb + b], nq = begin[(size_t)c * nb + b + 1] - q0;
+        e[0] = q0, e[1] = nq;
+        for (int q = 0; q < std::min(nq, SCHUR_REC_LL); ++q) e[2 + q] = out[q0 + q];
+      }
+    }
+  }
+  return stride;
+}
+
 // convert the arena offsets stored in the pointer fields to device addresses
 void relocate(WinPtrs& P, unsigned char* base, unsigned char* zbase, int debug) {
   unsigned char** fields = reinterpret_cast<unsigned char**>(&P.pose[0]);

@@ -111,7 +111,9 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
       p.nlb = sch2_serial_nlb(p.trows);
       // the small tiles: stages of four landmarks pipelined over a ring of three tile sets (39 KB at 60 rows: three per CU as well);
       // OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES keeps the batch loop above as the referee
-      const bool serial = !small_tiles || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES);
+      // (the ring loop's workgroups start from the batch's chunk launch records: a batch without them keeps the serial loop)
+      const bool serial = !small_tiles || M.rec_stride == 0 || (o.tuning.flags & OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES);
+      p.rec_stride = serial ? 0 : M.rec_stride;
       if (!serial) p.nlb = SCH2_STAGE_LM;
       const int sm = (serial ? sch2_tile_doubles(p.trows, p.nlb) : sch2_ring_doubles(p.trows)) * (int)sizeof(double);
       // The EVALUATION of the IMU / prior factors rides in the decision-free launch with the small tiles (schur_ride_kernel) where
@@ -224,14 +226,16 @@ hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
   const dim3 grid((unsigned)p.schur.gx, (unsigned)b.nw), blk(SCHUR_THREADS);
   const WinPtrs* wins = s->d_wins + b.w0;
   const CtrlSlot* ctrls = s->d_ctrl + b.w0;
+  // (the ring instantiations only: the records of window b.w0 onwards, p.rec_stride of them per window)
+  const int* recs = p.rec_stride ? s->d_recs + (size_t)b.w0 * p.rec_stride * SCHUR_REC_INTS : nullptr;
   switch (p.schur.k) {
     case SCHUR_NONE: return hipSuccess;
     case SCHUR_VALU: hipLaunchKernelGGL(schur_kernel, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call); break;
-    case SCHUR_MFMA3: hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
-    case SCHUR_MFMA9: hipLaunchKernelGGL(schur_mfma_kernel<9>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
-    case SCHUR_RIDE3: hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small); break;
-    case SCHUR_MFMA3_SERIAL: hipLaunchKernelGGL((schur_mfma_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec); break;
-    case SCHUR_RIDE3_SERIAL: hipLaunchKernelGGL((schur_ride_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small); break;
+    case SCHUR_MFMA3: hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
+    case SCHUR_MFMA9: hipLaunchKernelGGL(schur_mfma_kernel<9>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
+    case SCHUR_RIDE3: hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride); break;
+    case SCHUR_MFMA3_SERIAL: hipLaunchKernelGGL((schur_mfma_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
+    case SCHUR_RIDE3_SERIAL: hipLaunchKernelGGL((schur_ride_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride); break;
   }
   return hipGetLastError();
 }

@@ -101,6 +101,7 @@ struct BatchMax {
   // launch takes no decision (schur_mfma_kernel, nodec) and reduces the trial buffer into that buffer's own set of partials, the
   // solve kernel decides (its DBUF instantiation, as in fused mode).  OKVIS_BA_TUNE_SCHUR_DECIDES keeps the decision in the Schur launch.
   bool spec_schur = false;
+  int rec_stride = 0;   // chunk launch records per window (build_chunk_records; 0 = the batch has none: no ring kernel)
 };
 struct Launch {   // one launch: the instantiation (capi_launch.inc, 0 = none), grid.x (grid.y = windows), dynamic LDS in bytes
   int k = 0, gx = 0, lds = 0;
@@ -113,7 +114,7 @@ struct Extent {   // windows [w0, w0 + nw) of one launch, and the helper workgro
 // arguments.  (ints only, no padding: plans are compared byte for byte)
 struct PlanFixed {
   int lin2 = 0, split_small = 0, fused = 0, nodec = 0, rides = 0, graph = 0;   // the route
-  Launch schur; int trows = 0, nlb = 0, n_small = 0;   // (nodec above)
+  Launch schur; int trows = 0, nlb = 0, n_small = 0, rec_stride = 0;   // (nodec above; the chunk launch records per window)
   Launch solve, tiled; int nT = 0;                     // the LDS-resident windows / the windows solved in HBM (+ their tiles per dimension)
   Launch small_init, small_iter, lin; int lin_n_small = 0, sd = 0;   // the factors' launch of okvis_ba_begin / of an iteration; linearise
   Launch take_back; int budget = 0;                    // imu_take_back_kernel; add_budget_kernel in front of the iterations
@@ -142,6 +143,7 @@ struct okvis_ba_solver {
   size_t arena_bytes = 0, arena_capacity = 0, wins_capacity = 0;
   WinPtrs* d_wins = nullptr;
   CtrlSlot* d_ctrl = nullptr;    // the control records of the uploaded windows (same allocation, behind the window records)
+  const int* d_recs = nullptr;   // the chunk launch records of the uploaded windows (in the arena; BatchMax::rec_stride of them per window)
   StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize[_batch]: every window's numbers, one copy)
   StageVec stage, stage_small;   // pinned staging of the arena's data part / of the WinPtrs + OptD records (kept across uploads)
   std::vector<HostWin> wins;
@@ -272,10 +274,10 @@ void destroy_graphs(okvis_ba_solver* s) {
   for (auto& kv : s->sub_graphs) (void)hipGraphExecDestroy(kv.second);
   s->sub_graphs.clear();
 }
-// Captured graphs hold the plan's launches, the addresses of the window / option / control records and the sub-batch streams: a
+// Captured graphs hold the plan's launches, the addresses of the window / option / control / chunk launch records and the sub-batch streams: a
 // re-upload or an option change that leaves all of that as it was (equally shaped windows: the per-frame pattern) keeps them.
 void keep_graphs(okvis_ba_solver* s) {
-  std::vector<const void*> addr = {s->d_wins, s->d_opt, s->d_ctrl};
+  std::vector<const void*> addr = {s->d_wins, s->d_opt, s->d_ctrl, s->d_recs};
   for (auto st : s->sub_streams) addr.push_back(st);
   if (s->plan == s->graph_plan && addr == s->graph_addr) return;
   destroy_graphs(s);
