@@ -43,6 +43,13 @@
  *                                (okvis_multisensor_processing/src/ThreadedKFVio.cpp:416-418), and the IMU-rate chain of
  *                                ThreadedKFVio::imuConsumerLoop through Frontend::propagation (:559-598, Frontend.cpp:274-292)
  *
+ * and the decision that consumes the matching's result:
+ *
+ *   okvis_fe_keyframe_decision   Frontend::doWeNeedANewKeyframe (okvis_frontend/src/Frontend.cpp:295-369): per camera image the convex
+ *                                hulls of all and of the matched keypoints, their areas, the keypoints inside the matched hull, and
+ *                                the decision per multiframe, many multiframes per call; exact (hull, area and inside test are stated
+ *                                from their definitions, see the entry)
+ *
  * What stays with the caller is what needs the estimator's book-keeping or image data: which keypoints carry a landmark,
  * addLandmark / addObservation.  G = PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
@@ -304,6 +311,60 @@ int okvis_fe_imu_propagate(okvis_fe_context* ctx, int32_t n_params, const okvis_
                            const int64_t* s_t, const double* s_gyr, const double* s_acc, int32_t n_ends, const int64_t* ends,
                            int32_t n_jobs, const okvis_fe_imu_job* jobs, double* T_WS, double* sb, double* cov, double* jac,
                            int32_t* count);
+
+#define OKVIS_FE_KF_FEW_POINTS 1u  /* the image has fewer than 3 keypoints: skipped (Frontend.cpp:332-333)                          */
+#define OKVIS_FE_KF_FEW_MATCHES 2u /* 3 or more keypoints, fewer than 3 of them with a landmark: skipped (:335-336)                  */
+
+typedef struct okvis_fe_kf_image { /* one camera image: keypoints kp_begin .. kp_begin + kp_count - 1 of the pool */
+  int32_t kp_begin, kp_count;      /* kp_count 0..8192; 0 is valid */
+} okvis_fe_kf_image;
+
+typedef struct okvis_fe_kf_job { /* one multiframe */
+  int32_t im_begin, n_cams;      /* its images im_begin .. im_begin + n_cams - 1 of the image pool, in camera order; n_cams 1..8 */
+  int32_t num_frames;            /* estimator.numFrames() (:299), >= 0                                                           */
+  int32_t initialized;           /* isInitialized_ (:304), zero or not                                                           */
+  float overlap_threshold;       /* keyframeInsertionOverlapThreshold_ (Frontend.hpp:312; the reference's comment says 0.6)      */
+  float ratio_threshold;         /* keyframeInsertionMatchingRatioThreshold_ (Frontend.hpp:319; 0.2)                             */
+} okvis_fe_kf_job;
+
+/* Frontend::doWeNeedANewKeyframe (okvis_frontend/src/Frontend.cpp:295-369) for many multiframes per call: the step between
+ * matchToKeyframes and matchToLastFrame (:196).  kp [n_kp][3] float (x, y, size; size is not read) and matched [n_kp] (non-zero where
+ * landmarkId(im, k) != 0, :327) are pools; images index the pools, jobs index the images.  Images and jobs may share ranges.
+ *
+ * cv::convexHull, cv::contourArea and cv::pointPolygonTest (:334-349) are OpenCV's, and OpenCV's source is not part of the reference
+ * tree: the three are stated here from their mathematical definitions and are NOT pinned to OpenCV; everything around them is the
+ * reference's, operation for operation.  Keypoints are float, so every quantity has an exact rational value and the statement is
+ * exact; near an edge OpenCV's rounded test may answer differently from the exact one.
+ *   orient(a, b, c)  the exact sign of (bx-ax)(cy-ay) - (by-ay)(cx-ax) over the rationals the floats are
+ *   hull             the vertices of the convex hull, strict (no coincident vertices, none on the segment between its neighbours),
+ *                    starting at the point with the smallest (y, then x), in the order with orient(v_i, v_i+1, v_i+2) > 0; every
+ *                    vertex is reported as the lowest keypoint index with its coordinates (indices count from the image's first
+ *                    keypoint).  All points coincident: size 1; all collinear: size 2, the two extremes in that order.
+ *   area             a = 0; prev = last vertex; for p in order: a += (double)prev.x * p.y - (double)prev.y * p.x, prev = p;
+ *                    area = fabs(a * 0.5), in IEEE double without fused multiply-adds (both products are exact).  Size 1 or 2: 0.
+ *   inside           keypoint k (of all, matched or not) is inside iff the matched hull has at least 3 vertices and
+ *                    orient(v_i, v_i+1, p_k) > 0 for every edge: vertices and points on an edge are not inside
+ *                    (pointPolygonTest(...) > 0).
+ * Per image in camera order, with (overlap, ratio) = (0, 0) carried along (:307-361): fewer than 3 keypoints or fewer than 3 matched:
+ * skipped (flag set, hull sizes, areas and n_inside are 0); else overlapArea = area_matched / area_all and matchingRatio =
+ * (double)n_matched / (double)n_inside as IEEE divisions (0/0 = NaN, x/0 = inf), and overlap = (overlapArea < overlap) ? overlap :
+ * overlapArea — std::max with its NaN behaviour: a NaN replaces the running value, and the next image replaces the NaN — ratio alike.
+ * decision (1 = a new keyframe is needed): num_frames < 2 -> 1; else !initialized -> 0; else
+ * !(overlap > (double)overlap_threshold && ratio > (double)ratio_threshold).
+ * Out, each may be NULL (leaving one out changes none of the others): per job decision, overlap, ratio [n_jobs]; per image n_matched,
+ * hull_all_size, hull_matched_size, area_all, area_matched, n_inside, flags (OKVIS_FE_KF_*) [n_images]; for referees hull_all,
+ * hull_matched [sum of kp_count]: image i's list starts at the sum of kp_count of the images before it, holds its size indices
+ * and then -1 up to kp_count entries.  Every image of the pool is computed, whether a job names it or not.
+ * One staging copy in, one launch (one wave per image; the per-job fold runs on the host from the per-image results), one copy back.
+ * OKVIS_BA_ERR_ARG, before anything is enqueued and with nothing written: NULL context or required pointer (jobs, images, kp and
+ * matched where their counts are positive), a negative count, kp_count outside 0..8192, n_cams outside 1..8, num_frames < 0, a
+ * keypoint or image range outside its pool, more than INT32_MAX hull entries, a non-finite x or y of a keypoint that an image names.
+ * n_jobs = 0 and an image without keypoints are valid. */
+int okvis_fe_keyframe_decision(okvis_fe_context* ctx, int32_t n_kp, const float* kp, const uint8_t* matched, int32_t n_images,
+                               const okvis_fe_kf_image* images, int32_t n_jobs, const okvis_fe_kf_job* jobs, uint8_t* decision,
+                               double* overlap, double* ratio, int32_t* n_matched, int32_t* hull_all_size, int32_t* hull_matched_size,
+                               double* area_all, double* area_matched, int32_t* n_inside, uint8_t* flags, int32_t* hull_all,
+                               int32_t* hull_matched);
 
 #ifdef __cplusplus
 }

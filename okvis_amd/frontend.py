@@ -1,7 +1,8 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
 with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
-best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch") and the IMU state
-propagation with covariance and Jacobian on the MI355X.  No CPU path."""
+best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the IMU state
+propagation with covariance and Jacobian and the keyframe decision (exact hulls, areas and inside counts) on the MI355X.  No CPU
+path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,10 +17,12 @@ PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = ra
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
-           "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate"]
+           "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 IMU_COV, IMU_JAC = 1, 2
+KF_FEW_POINTS, KF_FEW_MATCHES = 1, 2
+KF_MAX_KEYPOINTS, KF_MAX_CAMS = 8192, 8
 
 
 class CameraC(C.Structure):
@@ -57,6 +60,17 @@ class ImuJobC(C.Structure):
     """okvis_fe_imu_job"""
     _fields_ = [("s_begin", C.c_int32), ("s_count", C.c_int32), ("e_begin", C.c_int32), ("e_count", C.c_int32), ("prm", C.c_int32),
                 ("flags", C.c_int32), ("t_start", C.c_int64), ("T_WS", C.c_double * 7), ("sb", C.c_double * 9)]
+
+
+class KfImageC(C.Structure):
+    """okvis_fe_kf_image"""
+    _fields_ = [("kp_begin", C.c_int32), ("kp_count", C.c_int32)]
+
+
+class KfJobC(C.Structure):
+    """okvis_fe_kf_job"""
+    _fields_ = [("im_begin", C.c_int32), ("n_cams", C.c_int32), ("num_frames", C.c_int32), ("initialized", C.c_int32),
+                ("overlap_threshold", C.c_float), ("ratio_threshold", C.c_float)]
 
 
 def camera(intr, model, width=752, height=480) -> CameraC:
@@ -117,6 +131,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
+        L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
 
 
 class Frontend:
@@ -300,6 +315,19 @@ class Frontend:
                    len(jobs), table, T.ctypes.data, sb.ctypes.data, cov.ctypes.data, jac.ctypes.data, count.ctypes.data)
         return T, sb, count, cov, jac
 
+    def keyframe_decision(self, jobs, want_hulls=False):
+        """Frontend::doWeNeedANewKeyframe for many multiframes in one call.  jobs: dicts with images (a list of 1..8 (kp [n][3] or
+        [n][2], matched [n]) pairs in camera order; matched is landmarkId != 0 after matchToKeyframes), and optionally num_frames
+        (default 2), initialized (default True), overlap_threshold (0.6), ratio_threshold (0.2).
+        -> per job a dict: decision (bool: a new keyframe is needed), overlap, ratio, and images: per image a dict with n_matched,
+        hull_all_size, hull_matched_size, area_all, area_matched, n_inside, flags (KF_FEW_POINTS | KF_FEW_MATCHES) and, under
+        want_hulls, hull_all / hull_matched (keypoint indices in hull order).  Exact: see okvis_fe_keyframe_decision."""
+        kp, matched, images, table, counts = keyframe_job_table(jobs)
+        out = keyframe_outputs(len(jobs), len(counts), sum(counts), want_hulls)
+        self._call("keyframe_decision", len(matched), kp.ctypes.data, matched.ctypes.data, len(counts), images, len(jobs), table,
+                   *[_ptr(out[k]) for k in KF_OUTPUTS])
+        return keyframe_results(table, counts, out, want_hulls)
+
 
 def landmark_covariance_in_camera(Sigma, T_CW):
     """A landmark's covariance rotated into a camera frame: ``R Sigma R^T``, R the rotation of T_CW (world to camera).  Sigma
@@ -335,6 +363,64 @@ def imu_pools(params, s_t, s_gyr, s_acc, ends):
     if not len(s_t) == len(s_gyr) == len(s_acc):
         raise ValueError("arrays of different lengths")
     return prm, s_t, s_gyr, s_acc, ends
+
+
+KF_OUTPUTS = ("decision", "overlap", "ratio", "n_matched", "hull_all_size", "hull_matched_size", "area_all", "area_matched", "n_inside",
+              "flags", "hull_all", "hull_matched")   # in the entry's argument order
+
+
+def keyframe_job_table(jobs):
+    """-> (kp pool [N][3] float32, matched pool [N] uint8, okvis_fe_kf_image array, okvis_fe_kf_job array, the images' keypoint
+    counts): every image of every job goes into the pools once, in job and camera order"""
+    kps, ms, counts = [], [], []
+    table = (KfJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        t = table[j]
+        t.im_begin, t.n_cams = len(counts), len(job["images"])
+        t.num_frames, t.initialized = int(job.get("num_frames", 2)), int(bool(job.get("initialized", True)))
+        t.overlap_threshold, t.ratio_threshold = float(job.get("overlap_threshold", 0.6)), float(job.get("ratio_threshold", 0.2))
+        for kp, m in job["images"]:
+            kp = np.asarray(kp, np.float32)
+            kp = kp.reshape(-1, kp.shape[-1] if kp.ndim == 2 else 3)
+            if kp.shape[1] == 2:
+                kp = np.concatenate([kp, np.zeros((len(kp), 1), np.float32)], axis=1)
+            m = (np.asarray(m).reshape(-1) != 0).astype(np.uint8)
+            if kp.shape[1] != 3 or len(m) != len(kp):
+                raise ValueError("an image is (kp [n][3] or [n][2], matched [n])")
+            kps.append(kp), ms.append(m), counts.append(len(kp))
+    kp = np.ascontiguousarray(np.concatenate(kps) if kps else np.zeros((0, 3)), np.float32).reshape(-1, 3)
+    matched = np.ascontiguousarray(np.concatenate(ms) if ms else np.zeros(0), np.uint8)
+    images = (KfImageC * max(1, len(counts)))()
+    at = 0
+    for i, n in enumerate(counts):
+        images[i].kp_begin, images[i].kp_count = at, n
+        at += n
+    return kp, matched, images, table, counts
+
+
+def keyframe_outputs(n_jobs, n_images, n_hull, want_hulls=False):
+    """the output arrays of okvis_fe_keyframe_decision by name (KF_OUTPUTS); the hull lists are None unless asked for"""
+    i32 = lambda n: np.zeros(n, np.int32)
+    return {"decision": np.zeros(n_jobs, np.uint8), "overlap": np.zeros(n_jobs), "ratio": np.zeros(n_jobs), "n_matched": i32(n_images),
+            "hull_all_size": i32(n_images), "hull_matched_size": i32(n_images), "area_all": np.zeros(n_images),
+            "area_matched": np.zeros(n_images), "n_inside": i32(n_images), "flags": np.zeros(n_images, np.uint8),
+            "hull_all": i32(n_hull) if want_hulls else None, "hull_matched": i32(n_hull) if want_hulls else None}
+
+
+def keyframe_results(table, counts, out, want_hulls=False):
+    """the filled arrays of keyframe_outputs as one dict per job"""
+    starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    res = []
+    for j in range(len(out["decision"])):
+        ims = []
+        for i in range(table[j].im_begin, table[j].im_begin + table[j].n_cams):
+            r = {k: out[k][i].item() for k in ("n_matched", "hull_all_size", "hull_matched_size", "area_all", "area_matched", "n_inside", "flags")}
+            if want_hulls:
+                r["hull_all"] = out["hull_all"][starts[i]:starts[i] + r["hull_all_size"]].copy()
+                r["hull_matched"] = out["hull_matched"][starts[i]:starts[i] + r["hull_matched_size"]].copy()
+            ims.append(r)
+        res.append({"decision": bool(out["decision"][j]), "overlap": float(out["overlap"][j]), "ratio": float(out["ratio"][j]), "images": ims})
+    return res
 
 
 def imu_job_table(jobs):
