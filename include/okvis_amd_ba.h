@@ -182,7 +182,7 @@ typedef struct okvis_ba_window {
  * SCHUR_SERIAL_BATCHES test_gpu_schur_referee.py and test_gpu_schur_pipeline.py; group_lm test_gpu_structure_paths.py and
  * test_gpu_schur_referee.py; solve_mode test_gpu_chain_solve.py and test_gpu_variants.py; NO_LDL_COMP / LDL_COMP_ALL
  * test_oracle_referee.py and test_index_build.py; H0_ON_HOST, NO_MARG_TILES test_gpu_marginalization.py; lin2_occupancy
- * test_gpu_fp32_linearize.py; solve_helpers test_gpu_batch64.py.  stagger_us is driven by no test.  The library reads ONE environment variable, OKVIS_BA_DEBUG
+ * test_gpu_fp32_linearize.py; solve_helpers test_gpu_batch64.py; LIN_NO_RECORDS test_gpu_lin_records.py.  stagger_us is driven by no test.  The library reads ONE environment variable, OKVIS_BA_DEBUG
  * (a comma-separated list of print-only diagnostics: "build", "upload", "marg", "arena=<file>"); it never changes a result.
  */
 #define OKVIS_BA_TUNE_SCHUR_DECIDES 0x1u      /* the separate Schur launch takes the trust-region decision itself (rounds 1-4) instead of
@@ -199,6 +199,9 @@ typedef struct okvis_ba_window {
 #define OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES 0x200u /* small tiles of the matrix-core Schur kernel: the serial loop over batches of 12 landmarks
                                                  (rounds 4-6) instead of the pipelined ring of 4-landmark stages — the referee of the new
                                                  loop for one release, the same sums bit for bit (OKVIS_BA_ROUTE_SCHUR_KERNEL reports 4)      */
+#define OKVIS_BA_TUNE_LIN_NO_RECORDS 0x400u    /* piece path, factors in a launch of their own: linearize2_kernel reading its group and operands
+                                                 through the window record instead of linearize2_rec_kernel (group launch records) — the
+                                                 referee, the same bits (OKVIS_BA_ROUTE_LIN_RECORDS reports 0; tests/test_gpu_lin_records.py) */
 #define OKVIS_BA_SOLVE_AUTO 0                  /* the library picks (OKVIS_BA_ROUTE_SOLVE_MODE reports what it picked)                     */
 #define OKVIS_BA_SOLVE_DENSE 1                /* blocked LDL^T of the whole D x D reduced system in LDS (rounds 3-5)                      */
 #define OKVIS_BA_SOLVE_CHAIN 2                /* speed/bias blocks eliminated along the IMU chain first, dense pose system behind it      */
@@ -349,6 +352,9 @@ int okvis_ba_check_window(const okvis_ba_window* w, const okvis_ba_options* opt,
                                            descriptor, [32 + 8 b, 32 + 8 b + 8) pose block b's {chunk_diag_begin, list length, the first six
                                            chunk_diag_out entries of the list (0 behind its end)}; empty for windows the ring loop of the
                                            matrix-core Schur kernel does not serve (free extrinsics, pose part beyond 63 rows)         */
+#define OKVIS_BA_LIST_GROUP_RECS 21     /* the group launch records of the window as a batch of its own: 32 ints per group, [0, 16) the group
+                                           record, [16, 20) its landmark / observation / pair / task counts, [20] = 1; empty for windows
+                                           that are not on the piece path                                                             */
 int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options* opt, int32_t n_windows, int32_t which,
                                 int32_t* out, int64_t capacity, int64_t* n);
 /* ---- incremental structure updates ---------------------------------------------------------------------
@@ -522,7 +528,8 @@ int okvis_ba_helper_timeouts(okvis_ba_solver* s, int64_t* count);
 #define OKVIS_BA_ROUTE_SOLVE_MODE 14            /* OKVIS_BA_SOLVE_* the LDS-resident windows are solved with                         */
 #define OKVIS_BA_ROUTE_SMALL_RIDES 15           /* 1 = the IMU / prior factors are evaluated inside the Schur launch (schur_ride_kernel),
                                                    small_prepare_kernel behind the solve launch only keeps the preintegrations up to date */
-#define OKVIS_BA_ROUTE_COUNT 16
+#define OKVIS_BA_ROUTE_LIN_RECORDS 16           /* 1 = linearize2_rec_kernel: the linearise workgroups start from the group launch records */
+#define OKVIS_BA_ROUTE_COUNT 17
 int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route);
 
 /* ---- marginalisation -------------------------------------------------------

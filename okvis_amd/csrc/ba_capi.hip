@@ -344,6 +344,8 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   if (int rc = build_batch(windows, n_windows, s->opt, L, A, wins.data())) return rc;
   size_t rec_off = 0;
   const int rec_stride = build_chunk_records(A, wins.data(), n_windows, &rec_off);
+  size_t grec_off = 0;
+  const int grec_stride = build_group_records(A, wins.data(), n_windows, &grec_off);
   const auto t_u1 = std::chrono::steady_clock::now();
   // grow-only device allocations: the per-frame re-upload of okvis_amd::Estimator must not pay hipFree/hipMalloc
   if (A.host.size() < A.size) A.host.resize(A.size, 0);
@@ -380,6 +382,8 @@ static int upload_impl(okvis_ba_solver* s, int n_windows, const okvis_ba_window*
   BatchMax M = batch_max(wins.data(), ptrs.data(), n_windows);
   M.rec_stride = rec_stride;
   s->d_recs = rec_stride ? reinterpret_cast<const int*>(s->d_arena + rec_off) : nullptr;
+  M.grec_stride = grec_stride;
+  s->d_grecs = grec_stride ? reinterpret_cast<const int*>(s->d_arena + grec_off) : nullptr;
   {
     // one copy: option record, window records and the (zeroed) control records behind them
     const size_t wb = sizeof(WinPtrs) * (size_t)n_windows, all = records_bytes((size_t)n_windows);
@@ -540,6 +544,12 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
       size_t off = 0;
       const int stride = build_chunk_records(A, &H, 1, &off);   // (appends to the arena: the lists above stay where they are)
       src = A.host.data() + off, count = (int64_t)stride * SCHUR_REC_INTS;
+      break;
+    }
+    case OKVIS_BA_LIST_GROUP_RECS: {
+      size_t off = 0;
+      const int stride = build_group_records(A, &H, 1, &off);   // (appends to the arena too)
+      src = A.host.data() + off, count = (int64_t)stride * LIN_REC_INTS;
       break;
     }
     default: return OKVIS_BA_ERR_ARG;
@@ -1055,6 +1065,8 @@ int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route) {
   route[OKVIS_BA_ROUTE_MAX_CHUNKS] = s->max.chunks;
   route[OKVIS_BA_ROUTE_SLOTS] = (int32_t)std::min<long long>(s->slots, 0x7fffffff);
   route[OKVIS_BA_ROUTE_SMALL_RIDES] = p.rides;
+  // (linearize2_rec_kernel: the group launch records; 0 = linearize2_kernel through the window record, OKVIS_BA_TUNE_LIN_NO_RECORDS)
+  route[OKVIS_BA_ROUTE_LIN_RECORDS] = p.grec_stride > 0;
   route[OKVIS_BA_ROUTE_SOLVE_MODE] = p.solve.k == SOLVE_NONE ? 0 : p.solve.k >= SOLVE_CHAIN ? OKVIS_BA_SOLVE_CHAIN : OKVIS_BA_SOLVE_DENSE;
   return OKVIS_BA_OK;
 }
@@ -1096,6 +1108,8 @@ static int locate(okvis_ba_solver* s, int w, int which, const double** ptr, int6
     case 98: *ptr = nullptr; *n = H.n_imu; return 0;  // diagnostics: re-preintegration count per IMU factor
     case 97: *ptr = nullptr; *n = 24; return 0;       // diagnostics: trust-region control record
     case 96: *ptr = nullptr; *n = 1; return 0;        // diagnostics: launch slots since okvis_ba_begin
+    case 95: *ptr = nullptr; *n = 1 + (int64_t)s->max.grec_stride * LIN_REC_INTS; return 0;   // diagnostics: [0] the batch's group launch
+                                    // records per window (0 = none), then the slots of window w, all of them, as the DEVICE holds them
     case OKVIS_BA_ARR_IMU_SB_REF: *ptr = nullptr; *n = 9 * (int64_t)H.n_imu; return 0;
     case OKVIS_BA_ARR_IMU_RESIDUAL: *ptr = nullptr; *n = 15 * (int64_t)H.n_imu; return 0;
     case OKVIS_BA_ARR_IMU_LIN: *ptr = nullptr; *n = OKVIS_BA_IMU_LIN_DOUBLES * (int64_t)H.n_imu; return 0;
@@ -1131,6 +1145,15 @@ int okvis_ba_download(okvis_ba_solver* s, int w, int which, double* out, int64_t
   }
   if (which == 96) {   // diagnostics: launch slots since okvis_ba_begin (the same for every window of the batch)
     out[0] = (double)s->slots;
+    return OKVIS_BA_OK;
+  }
+  if (which == 95) {
+    const int stride = s->max.grec_stride;
+    std::vector<int> r((size_t)stride * LIN_REC_INTS);
+    HIP_TRY(hipStreamSynchronize(s->stream));   // (the upload's copy of the arena)
+    if (stride) HIP_TRY(hipMemcpy(r.data(), s->d_grecs + (size_t)w * stride * LIN_REC_INTS, r.size() * sizeof(int), hipMemcpyDeviceToHost));
+    out[0] = stride;
+    for (size_t i = 0; i < r.size(); ++i) out[1 + i] = r[i];
     return OKVIS_BA_OK;
   }
   if (which == 97) {
@@ -1236,6 +1259,8 @@ int okvis_ba_algorithmic_bytes(okvis_ba_solver* s, int64_t* lin, int64_t* schur,
     b += H.bytes_schur;
     // (the ring kernels read one chunk launch record per workgroup)
     if (s->plan.rec_stride) b += (int64_t)H.n_chunk * SCHUR_REC_INTS * (int64_t)sizeof(int);
+    // (... and the record instantiations of the linearise kernel one group launch record)
+    if (s->plan.grec_stride) a += (int64_t)H.n_group * LIN_REC_INTS * (int64_t)sizeof(int);
     c += H.bytes_solve;
     d += H.bytes_small;
   }

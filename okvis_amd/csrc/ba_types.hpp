@@ -56,6 +56,14 @@ struct Group {  // one linearise workgroup: whole landmarks, <= GROUP_OBS observ
   int piece_begin, pw1, pw2, pw3;
 };
 static_assert(sizeof(Group) == 64, "Group is fetched as 16 dwords");
+// Group launch record of the record instantiations of linearize2_kernel (linearize2_rec_kernel, ba_linearize2.hpp): one 128-byte
+// line per (window, group) in ONE array of the batch with a fixed stride per window (build_group_records), so that a workgroup
+// forms its record's address from kernel arguments and blockIdx alone, like the chunk launch records of the Schur kernel below.
+//   [0, 16)                    the Group record, field for field
+//   [LIN_REC_COUNTS, ... + 4)  landmarks, observations, pairs, tasks of the group (the ends minus the begins)
+//   [LIN_REC_VALID]            1; a slot behind the window's last group is all zero: every count zero, and the workgroup leaves
+constexpr int LIN_REC_INTS = 32, LIN_REC_COUNTS = 16, LIN_REC_VALID = 20;
+static_assert(sizeof(Group) / sizeof(int) == LIN_REC_COUNTS && LIN_REC_INTS * sizeof(int) == 128, "layout of the group launch record");
 
 // reduction task of a group: accumulate over a list of the group's observations
 //   type 0: block Hessian/gradient of a pose-role block   out = 27 doubles (21 upper-tri A + 6 g)

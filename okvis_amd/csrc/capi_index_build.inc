@@ -1267,6 +1267,38 @@ int build_chunk_records(Arena& A, const HostWin* H, int n, size_t* off) {
   return stride;
 }
 
+// The group launch records of a batch (LIN_REC_INTS, ba_types.hpp): what a workgroup of linearize2_rec_kernel reads before it can
+// request its operands — the Group record and the group's four counts — copied from the windows' group arrays (which stay:
+// linearize_kernel, the fused and the SMALL instantiations of linearize2_kernel read them) into one array of the arena's data part,
+// [window][stride][LIN_REC_INTS]; slots behind a window's last group are zero.  H[i].ptrs still hold arena offsets.  Returns the
+// stride = the batch's largest group count, or 0 = no records: a window that is not laid out for the piece path.
+int build_group_records(Arena& A, const HostWin* H, int n, size_t* off) {
+  int stride = 0;
+  for (int i = 0; i < n; ++i) {
+    const WinPtrs& P = H[i].ptrs;
+    if (!P.lin2 || P.has_ext) return 0;
+    stride = std::max(stride, P.n_group);
+  }
+  if (stride == 0) return 0;
+  const size_t bytes = (size_t)n * stride * LIN_REC_INTS * sizeof(int);
+  *off = A.alloc(bytes);
+  if (A.host.size() < A.size) A.host.resize(A.size, 0);
+  std::memset(A.host.data() + *off, 0, bytes);
+  for (int i = 0; i < n; ++i) {
+    const WinPtrs& P = H[i].ptrs;
+    const Group* groups = reinterpret_cast<const Group*>(A.host.data() + reinterpret_cast<size_t>((const void*)P.groups));
+    for (int g = 0; g < P.n_group; ++g) {
+      const Group G = groups[g];   // (a copy: the records may lie in the same, just resized, buffer)
+      int* r = reinterpret_cast<int*>(A.host.data() + *off) + ((size_t)i * stride + g) * LIN_REC_INTS;
+      std::memcpy(r, &G, sizeof(Group));
+      r[LIN_REC_COUNTS] = G.lm_end - G.lm_begin, r[LIN_REC_COUNTS + 1] = G.obs_end - G.obs_begin;
+      r[LIN_REC_COUNTS + 2] = G.pair_end - G.pair_begin, r[LIN_REC_COUNTS + 3] = G.task_end - G.task_begin;
+      r[LIN_REC_VALID] = 1;
+    }
+  }
+  return stride;
+}
+
 // convert the arena offsets stored in the pointer fields to device addresses
 void relocate(WinPtrs& P, unsigned char* base, unsigned char* zbase, int debug) {
   unsigned char** fields = reinterpret_cast<unsigned char**>(&P.pose[0]);

@@ -63,7 +63,10 @@ std::vector<std::pair<const void*, size_t>> plan_kernels() {
           {f(&linearize_kernel<false, float, true>), pf}, {f(&linearize_kernel<false, float, false>), pf},
           {f(&linearize_kernel<false, double, true>), pd}, {f(&linearize_kernel<false, double, false>), pd},
           // (the serial batch loop of the small tiles: the referee of the pipelined one, OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
-          {f(&schur_ride_kernel<3, true>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3, true>), wide}};
+          {f(&schur_ride_kernel<3, true>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3, true>), wide},
+          // (the record instantiations of the piece path, behind everything that was there before them)
+          {f(&linearize2_rec_kernel<double, 3>), d}, {f(&linearize2_rec_kernel<double, 4, 14>), d},
+          {f(&linearize2_rec_kernel<float, 3>), s}, {f(&linearize2_rec_kernel<float, 4, 14>), s}};
 }
 
 // ---- The instantiations a launch plan names (Launch::k is the index in the table of its kind) ----
@@ -80,6 +83,10 @@ const Lin2Fn LIN2[10] = {&linearize2_kernel<double, true, false>, &linearize2_ke
                          &linearize2_kernel<double, false, false, 3>, &linearize2_kernel<double, false, false, 4, 14>,
                          &linearize2_kernel<float, true, false>, &linearize2_kernel<float, true, true>, &linearize2_kernel<float, false, true>,
                          &linearize2_kernel<float, false, false, 3>, &linearize2_kernel<float, false, false, 4, 14>};
+// ... and its record instantiations (group launch records; LIN2_OCC3 / LIN2_OCC4 only): [2 * fp32 + (LIN2_* - LIN2_OCC3)]
+using Lin2RecFn = decltype(&linearize2_rec_kernel<double, 3>);
+const Lin2RecFn LIN2R[4] = {&linearize2_rec_kernel<double, 3>, &linearize2_rec_kernel<double, 4, 14>, &linearize2_rec_kernel<float, 3>,
+                            &linearize2_rec_kernel<float, 4, 14>};
 // the reduced solve: the LDS-resident windows (dense or chain; DBUF: one set of Schur partials per linearisation buffer), the tiled ones
 enum { SOLVE_NONE, SOLVE_DENSE, SOLVE_DENSE_DBUF, SOLVE_CHAIN, SOLVE_CHAIN_DBUF, SOLVE_TILED };
 const SolveFn SOLVE[6] = {nullptr, &solve_kernel<false, false>, &solve_kernel<false, true>, &solve_kernel<false, false, true>,
@@ -148,6 +155,9 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
       const bool two_rounds = !p.fused && occ >= 4;   // block records in two rounds: 37 KB of LDS, four workgroups per CU
       p.lin = Launch{t + (p.fused ? LIN2_FUSED : occ >= 4 ? LIN2_OCC4 : LIN2_OCC3), M.group,
                      two_rounds ? (int)lin2_smem(M.Dp, false, f32, true) : smem2};
+      // the workgroups of the unfused launch start from the batch's group launch records (linearize2_rec_kernel); a batch without
+      // them, and OKVIS_BA_TUNE_LIN_NO_RECORDS (the referee), keep linearize2_kernel, which reads through the window record
+      if (!p.fused && M.grec_stride > 0 && !(o.tuning.flags & OKVIS_BA_TUNE_LIN_NO_RECORDS)) p.grec_stride = M.grec_stride;
     } else {
       p.lin = Launch{t + (p.fused ? LIN2_FUSED_SMALL : LIN2_SMALL), p.n_small + M.group, std::max(smem2, (int)small_smem())};
       p.lin_n_small = p.n_small;
@@ -268,7 +278,12 @@ hipError_t launch_lin(okvis_ba_solver* s, Sub b, int init) {
   if (f.k == SMALL_ALL) hipLaunchKernelGGL(small_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins, init);
   if (f.k == SMALL_PREPARE) hipLaunchKernelGGL(small_prepare_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins);
   const dim3 grid((unsigned)p.lin.gx, (unsigned)b.nw);
-  if (p.lin2) {
+  if (p.lin2 && p.grec_stride) {
+    // (the records of window b.w0 onwards, p.grec_stride of them per window; the control records as in launch_schur)
+    const Lin2RecFn fn = LIN2R[2 * (p.lin.k >= 5) + (p.lin.k % 5 - LIN2_OCC3)];
+    hipLaunchKernelGGL(fn, grid, dim3(LIN_THREADS), p.lin.lds, b.st, wins, s->d_opt, init, p.sd, s->d_ctrl + b.w0,
+                       s->d_grecs + (size_t)b.w0 * p.grec_stride * LIN_REC_INTS, p.grec_stride);
+  } else if (p.lin2) {
     const Lin2Fn fn = LIN2[p.lin.k];
     hipLaunchKernelGGL(fn, grid, dim3(LIN_THREADS), p.lin.lds, b.st, wins, s->d_opt, init, p.lin_n_small, p.sd);
   } else {

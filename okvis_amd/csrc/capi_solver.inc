@@ -102,6 +102,7 @@ struct BatchMax {
   // solve kernel decides (its DBUF instantiation, as in fused mode).  OKVIS_BA_TUNE_SCHUR_DECIDES keeps the decision in the Schur launch.
   bool spec_schur = false;
   int rec_stride = 0;   // chunk launch records per window (build_chunk_records; 0 = the batch has none: no ring kernel)
+  int grec_stride = 0;  // group launch records per window (build_group_records; 0 = none: linearize2_kernel reads the window record)
 };
 struct Launch {   // one launch: the instantiation (capi_launch.inc, 0 = none), grid.x (grid.y = windows), dynamic LDS in bytes
   int k = 0, gx = 0, lds = 0;
@@ -117,6 +118,7 @@ struct PlanFixed {
   Launch schur; int trows = 0, nlb = 0, n_small = 0, rec_stride = 0;   // (nodec above; the chunk launch records per window)
   Launch solve, tiled; int nT = 0;                     // the LDS-resident windows / the windows solved in HBM (+ their tiles per dimension)
   Launch small_init, small_iter, lin; int lin_n_small = 0, sd = 0;   // the factors' launch of okvis_ba_begin / of an iteration; linearise
+  int grec_stride = 0;   // > 0: lin names a record instantiation (LIN2R, capi_launch.inc); its group launch records per window
   Launch take_back; int budget = 0;                    // imu_take_back_kernel; add_budget_kernel in front of the iterations
   Extent whole; int one_helpers = 0;                   // okvis_ba_begin / okvis_ba_finish; okvis_ba_marginalize (one window)
 };
@@ -144,6 +146,7 @@ struct okvis_ba_solver {
   WinPtrs* d_wins = nullptr;
   CtrlSlot* d_ctrl = nullptr;    // the control records of the uploaded windows (same allocation, behind the window records)
   const int* d_recs = nullptr;   // the chunk launch records of the uploaded windows (in the arena; BatchMax::rec_stride of them per window)
+  const int* d_grecs = nullptr;  // the group launch records (in the arena; BatchMax::grec_stride of them per window)
   StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize[_batch]: every window's numbers, one copy)
   StageVec stage, stage_small;   // pinned staging of the arena's data part / of the WinPtrs + OptD records (kept across uploads)
   std::vector<HostWin> wins;
@@ -277,7 +280,7 @@ void destroy_graphs(okvis_ba_solver* s) {
 // Captured graphs hold the plan's launches, the addresses of the window / option / control / chunk launch records and the sub-batch streams: a
 // re-upload or an option change that leaves all of that as it was (equally shaped windows: the per-frame pattern) keeps them.
 void keep_graphs(okvis_ba_solver* s) {
-  std::vector<const void*> addr = {s->d_wins, s->d_opt, s->d_ctrl, s->d_recs};
+  std::vector<const void*> addr = {s->d_wins, s->d_opt, s->d_ctrl, s->d_recs, s->d_grecs};
   for (auto st : s->sub_streams) addr.push_back(st);
   if (s->plan == s->graph_plan && addr == s->graph_addr) return;
   destroy_graphs(s);

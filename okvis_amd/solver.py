@@ -19,7 +19,7 @@ from .window import LimitsC, OptionsC, SummaryC, Window, WindowC, default_option
 # buffer H = J^T J as the packed lower triangle (index a (a + 1) / 2 + b) over the factor's own columns pose0(6) | sb0(9) |
 # pose1(6) | sb1(9) (465), g = J^T r (30), the weighted residual r (15), the cost (1) — reshape(-1, 511).
 ARR = dict(POSE=0, SB=1, LM=2, OBS_RESIDUAL=3, LM_V=4, LM_B=5, LM_HQ=6, PAIR_W=7, REDUCED_S=8,
-           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, DAMPING=15, IMU_SB_REF=16, IMU_LIN=17, PROF=99, IMU_REDO_COUNT=98, CTRL=97, SLOTS=96)
+           REDUCED_RHS=9, STEP=10, LM_QUALITY=11, GRADIENT=12, IMU_RESIDUAL=13, HPP=14, DAMPING=15, IMU_SB_REF=16, IMU_LIN=17, PROF=99, IMU_REDO_COUNT=98, CTRL=97, SLOTS=96, GROUP_RECS=95)
 _dp = C.POINTER(C.c_double)
 
 
@@ -43,7 +43,7 @@ def check_window(window: Window, options: OptionsC | None = None) -> dict:
 
 INDEX_LISTS = ("groups", "lm_obs_begin", "lm_pair_begin", "pair_lm", "pair_block", "pair_off", "pair_role", "lm_piece_begin",
                "pair_piece", "pair_list_begin", "pair_list", "tasks", "task_list", "chunks", "chunk_diag_begin", "chunk_diag_out",
-               "chunk_desc", "piece_path", "ldl_comp", "chain", "chunk_recs")   # OKVIS_BA_LIST_* in this order
+               "chunk_desc", "piece_path", "ldl_comp", "chain", "chunk_recs", "group_recs")   # OKVIS_BA_LIST_* in this order
 
 
 def index_lists(window: Window, options: OptionsC | None = None, n_windows: int = 1) -> dict:
@@ -67,6 +67,7 @@ def index_lists(window: Window, options: OptionsC | None = None, n_windows: int 
     out["tasks"] = out["tasks"].reshape(-1, 6)
     out["chunks"] = out["chunks"].reshape(-1, 2)
     out["chunk_recs"] = out["chunk_recs"].reshape(-1, 128)
+    out["group_recs"] = out["group_recs"].reshape(-1, 32)
     out["piece_path"] = int(out["piece_path"][0])
     out["ldl_comp"] = int(out["ldl_comp"][0]) & 0xFFFFFFFF
     out["chain"] = int(out["chain"][0])
@@ -509,11 +510,12 @@ class WindowBatch:
         return n.value
 
     ROUTE = ("windows", "fused", "decision_free_schur", "piece_path", "split_small", "sub_batches", "sub_batch_max_windows",
-             "schur_kernel", "solve_dbuf", "solve_tiled", "solve_helpers", "graph", "max_chunks", "slots", "solve_mode", "small_rides")
+             "schur_kernel", "solve_dbuf", "solve_tiled", "solve_helpers", "graph", "max_chunks", "slots", "solve_mode", "small_rides",
+             "lin_records")
 
     def launch_route(self) -> dict:
         """okvis_ba_launch_route: which launches this batch takes under the current options (read-only)"""
-        r = (C.c_int32 * 16)()
+        r = (C.c_int32 * len(self.ROUTE))()
         _lib.check(self._L.okvis_ba_launch_route(self._h, r), "launch_route")
         return {n: int(r[i]) for i, n in enumerate(self.ROUTE)}
 
