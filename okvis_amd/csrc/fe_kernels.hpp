@@ -453,7 +453,9 @@ __device__ inline unsigned gate_3d2d(const double* uv, const double* U, const fl
   // err^T U^-1 err with U^-1 = [u11 -u01; -u10 u00] / det
   const double chi2 = e0 * ((u11 * idet) * e0 + (-u01 * idet) * e1) + e1 * ((-u10 * idet) * e0 + (u00 * idet) * e1);
   unsigned f = 0;
-  if (chi2 < 4.0 && chi2 > -1.0) f |= OKVIS_FE_GATE_VERIFIED;  // `const int chi2 = ...; chi2 < 4.0`: truncation towards zero
+  // `const int chi2 = ...; chi2 < 4.0`: truncation towards zero, so [3, 4) still passes and so does every negative chi2 (a U that
+  // is not positive definite): the truncated integer is below 4 exactly when chi2 is
+  if (chi2 < 4.0) f |= OKVIS_FE_GATE_VERIFIED;
   if (!(chi2 > 4.0)) f |= OKVIS_FE_GATE_ACCEPTED;
   if (sqrt(u00 * u00 + u01 * u01 + u10 * u10 + u11 * u11) > 25.0 / (s2 * sqrt(2.0))) f |= OKVIS_FE_GATE_UNCERTAIN;
   *chi2_out = chi2;
