@@ -182,7 +182,8 @@ typedef struct okvis_ba_window {
  * SCHUR_SERIAL_BATCHES test_gpu_schur_referee.py and test_gpu_schur_pipeline.py; group_lm test_gpu_structure_paths.py and
  * test_gpu_schur_referee.py; solve_mode test_gpu_chain_solve.py and test_gpu_variants.py; NO_LDL_COMP / LDL_COMP_ALL
  * test_oracle_referee.py and test_index_build.py; H0_ON_HOST, NO_MARG_TILES test_gpu_marginalization.py; lin2_occupancy
- * test_gpu_fp32_linearize.py; solve_helpers test_gpu_batch64.py; LIN_NO_RECORDS test_gpu_lin_records.py.  stagger_us is driven by no test.  The library reads ONE environment variable, OKVIS_BA_DEBUG
+ * test_gpu_fp32_linearize.py; solve_helpers test_gpu_batch64.py; LIN_NO_RECORDS test_gpu_lin_records.py; FOUR_LAUNCH
+ * test_gpu_three_launch.py and test_three_launch_host.py.  stagger_us is driven by no test.  The library reads ONE environment variable, OKVIS_BA_DEBUG
  * (a comma-separated list of print-only diagnostics: "build", "upload", "marg", "arena=<file>"); it never changes a result.
  */
 #define OKVIS_BA_TUNE_SCHUR_DECIDES 0x1u      /* the separate Schur launch takes the trust-region decision itself (rounds 1-4) instead of
@@ -202,6 +203,10 @@ typedef struct okvis_ba_window {
 #define OKVIS_BA_TUNE_LIN_NO_RECORDS 0x400u    /* piece path, factors in a launch of their own: linearize2_kernel reading its group and operands
                                                  through the window record instead of linearize2_rec_kernel (group launch records) — the
                                                  referee, the same bits (OKVIS_BA_ROUTE_LIN_RECORDS reports 0; tests/test_gpu_lin_records.py) */
+#define OKVIS_BA_TUNE_FOUR_LAUNCH 0x800u       /* riding route under an iteration budget: small_prepare_kernel in every slot (four launches per
+                                                 iteration) instead of the three-launch iteration that runs it only for windows the solve
+                                                 kernel paused — the referee, the same bits (OKVIS_BA_ROUTE_THREE_LAUNCH reports 0;
+                                                 tests/test_gpu_three_launch.py)                                                              */
 #define OKVIS_BA_SOLVE_AUTO 0                  /* the library picks (OKVIS_BA_ROUTE_SOLVE_MODE reports what it picked)                     */
 #define OKVIS_BA_SOLVE_DENSE 1                /* blocked LDL^T of the whole D x D reduced system in LDS (rounds 3-5)                      */
 #define OKVIS_BA_SOLVE_CHAIN 2                /* speed/bias blocks eliminated along the IMU chain first, dense pose system behind it      */
@@ -355,6 +360,10 @@ int okvis_ba_check_window(const okvis_ba_window* w, const okvis_ba_options* opt,
 #define OKVIS_BA_LIST_GROUP_RECS 21     /* the group launch records of the window as a batch of its own: 32 ints per group, [0, 16) the group
                                            record, [16, 20) its landmark / observation / pair / task counts, [20] = 1; empty for windows
                                            that are not on the piece path                                                             */
+#define OKVIS_BA_LIST_PLAN 22           /* eight ints of the launch plan of a batch of n_windows windows shaped like this one: {three-launch
+                                           iteration, factors ride in the Schur launch, the iteration's factor launch is small_prepare_kernel
+                                           alone, iteration budget, fused, solve instantiation, the keys of the captured graphs of a call of
+                                           10 iterations on the three-launch and on the four-launch route}                               */
 int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options* opt, int32_t n_windows, int32_t which,
                                 int32_t* out, int64_t capacity, int64_t* n);
 /* ---- incremental structure updates ---------------------------------------------------------------------
@@ -529,8 +538,14 @@ int okvis_ba_helper_timeouts(okvis_ba_solver* s, int64_t* count);
 #define OKVIS_BA_ROUTE_SMALL_RIDES 15           /* 1 = the IMU / prior factors are evaluated inside the Schur launch (schur_ride_kernel),
                                                    small_prepare_kernel behind the solve launch only keeps the preintegrations up to date */
 #define OKVIS_BA_ROUTE_LIN_RECORDS 16           /* 1 = linearize2_rec_kernel: the linearise workgroups start from the group launch records */
-#define OKVIS_BA_ROUTE_COUNT 17
+#define OKVIS_BA_ROUTE_THREE_LAUNCH 17          /* 1 = an iteration is three launches, Schur -> solve -> linearise: the solve kernel's tail checks
+                                                   the IMU terms and pauses a window whose preintegrations need small_prepare_kernel; the
+                                                   host adds that launch for it (0 = the launch is in every slot, OKVIS_BA_TUNE_FOUR_LAUNCH)  */
+#define OKVIS_BA_ROUTE_COUNT 18
 int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route);
+/* The three-launch iteration (OKVIS_BA_ROUTE_THREE_LAUNCH): windows paused by the solve kernel since okvis_ba_begin, each pause counted
+ * once.  The host resumes them at the next okvis_ba_iterate / in okvis_ba_finish; results do not depend on it.  Synchronises. */
+int okvis_ba_pause_count(okvis_ba_solver* s, int64_t* count);
 
 /* ---- marginalisation -------------------------------------------------------
  * Numeric core of okvis::Estimator::applyMarginalizationStrategy (Estimator.cpp:434-773), i.e. what the

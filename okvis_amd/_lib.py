@@ -18,7 +18,7 @@ SYMBOLS = [
     "okvis_ba_evaluate_cost", "okvis_ba_get_state", "okvis_ba_fetch_results", "okvis_ba_fetch_imu_caches", "okvis_ba_array_size", "okvis_ba_download",
     "okvis_ba_reduced_dim", "okvis_ba_pair_count", "okvis_ba_pairs", "okvis_ba_last_iterate_ms",
     "okvis_ba_profile_iterations", "okvis_ba_profile_launches", "okvis_ba_algorithmic_bytes", "okvis_ba_synchronize",
-    "okvis_ba_helper_timeouts", "okvis_ba_launch_route", "okvis_ba_marginalize", "okvis_ba_marginalize_begin", "okvis_ba_marginalize_end",
+    "okvis_ba_helper_timeouts", "okvis_ba_launch_route", "okvis_ba_pause_count", "okvis_ba_marginalize", "okvis_ba_marginalize_begin", "okvis_ba_marginalize_end",
     "okvis_ba_marginalize_batch", "okvis_ba_marginalize_batch_begin", "okvis_ba_marginalize_batch_end",
     "okvis_ba_state_covariance", "okvis_ba_last_covariance_ms",
     "okvis_ba_landmark_covariance", "okvis_ba_last_landmark_covariance_ms",
@@ -104,6 +104,7 @@ def lib():
     L.okvis_ba_reduced_dim.argtypes = [vp, C.c_int, _ip]
     L.okvis_ba_pair_count.argtypes = [vp, C.c_int, _ip]
     L.okvis_ba_helper_timeouts.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.okvis_ba_pause_count.argtypes = [vp, C.POINTER(C.c_int64)]
     L.okvis_ba_launch_route.argtypes = [vp, _ip]
     L.okvis_ba_pairs.argtypes = [vp, C.c_int, _ip, _ip]
     L.okvis_ba_last_iterate_ms.argtypes = [vp, C.POINTER(C.c_float)]

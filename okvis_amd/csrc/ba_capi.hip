@@ -108,6 +108,12 @@ int okvis_ba_create(okvis_ba_solver** out, int device) {
   if (e == hipSuccess) e = hipEventCreate(&s->ev0);
   if (e == hipSuccess) e = hipEventCreate(&s->ev1);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming);
+  // the word the three-launch iteration's solve kernel bumps when it pauses a window: page-locked, mapped, coherent
+  if (e == hipSuccess) e = hipHostMalloc((void**)&s->h_pause, 64, hipHostMallocMapped | hipHostMallocCoherent);
+  if (e == hipSuccess) {
+    s->h_pause[0] = 0;
+    e = hipHostGetDevicePointer((void**)&s->d_pause, s->h_pause, 0);
+  }
   // the option record and the window records share one allocation — [OptD, padded | WinPtrs x capacity] — so that an upload
   // refreshes both with ONE copy
   if (e == hipSuccess) e = hipMalloc(&s->d_opt, records_bytes(1));
@@ -145,6 +151,8 @@ int okvis_ba_destroy(okvis_ba_solver* s) {
   if (s->d_opt) (void)hipFree(s->d_opt);   // (d_wins lives in the same allocation)
   if (s->h_ctrl_stage) (void)hipHostFree(s->h_ctrl_stage);
   if (s->d_ctrl_stage) (void)hipFree(s->d_ctrl_stage);
+  if (s->h_pause) (void)hipHostFree(s->h_pause);
+  if (s->d_redo_mark) (void)hipFree(s->d_redo_mark);
   if (s->marg_scratch) (void)hipFree(s->marg_scratch);
   for (auto ev : s->ev_cov)
     if (ev) (void)hipEventDestroy(ev);
@@ -508,6 +516,7 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
   const void* src = nullptr;
   int64_t count = 0;
   int width = 4;   // bytes per entry
+  std::vector<int32_t> plan_ints;
   switch (which) {
     case OKVIS_BA_LIST_GROUPS: src = at((const void*)P.groups), count = 16 * (int64_t)P.n_group; break;
     case OKVIS_BA_LIST_LM_OBS_BEGIN: src = at((const void*)P.lm_obs_begin), count = P.n_lm + 1; break;
@@ -550,6 +559,17 @@ int okvis_ba_check_window_lists(const okvis_ba_window* w, const okvis_ba_options
       size_t off = 0;
       const int stride = build_group_records(A, &H, 1, &off);   // (appends to the arena too)
       src = A.host.data() + off, count = (int64_t)stride * LIN_REC_INTS;
+      break;
+    }
+    case OKVIS_BA_LIST_PLAN: {
+      // the launch plan of a batch of n_windows windows shaped like this one (host only: make_plan on what the index build says)
+      size_t off = 0;
+      BatchMax M = batch_max(&H, &H.ptrs, 1);
+      M.rec_stride = build_chunk_records(A, &H, 1, &off);
+      M.grec_stride = build_group_records(A, &H, 1, &off);
+      const LaunchPlan p = make_plan(L, M, o, n_windows);
+      plan_ints = {p.three, p.rides, p.small_iter.k == SMALL_PREPARE, p.budget, p.fused, p.solve.k, graph_key(10, false), graph_key(10, true)};
+      src = plan_ints.data(), count = (int64_t)plan_ints.size();
       break;
     }
     default: return OKVIS_BA_ERR_ARG;
@@ -816,8 +836,47 @@ int okvis_ba_begin(okvis_ba_solver* s) {
     HIP_TRY(hipGetLastError());
   }
   HIP_TRY(launch_lin(s, whole(s), 1));
+  if (s->plan.three) {
+    // the three-launch iteration: what the iterations re-preintegrate is counted from here (okvis_ba_finish reads it: start_four)
+    const size_t n = s->wins.size();
+    if (s->redo_mark_windows < n) {
+      if (s->d_redo_mark) HIP_TRY(hipFree(s->d_redo_mark));
+      s->d_redo_mark = nullptr, s->redo_mark_windows = 0;
+      HIP_TRY(hipMalloc((void**)&s->d_redo_mark, sizeof(int) * n));
+      s->redo_mark_windows = n;
+    }
+    hipLaunchKernelGGL(redo_mark_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s->stream, s->d_wins, s->d_redo_mark, (int)n);
+    HIP_TRY(hipGetLastError());
+  }
+  // (pauses belong to one begin ... finish: whoever pauses a window resumes it before okvis_ba_finish returns)
+  s->pause_begin = s->pause_seen = __atomic_load_n(s->h_pause, __ATOMIC_ACQUIRE);
+  s->three_unseen = false;
   s->begun = true;
   s->evaluated = true;
+  return OKVIS_BA_OK;
+}
+
+// The route of the next iterations (true = four launches) and the host's part of the three-launch iteration: a three-launch call of
+// this begin ... finish that nobody has waited for may have paused windows — they would sit out the whole next call — so it is
+// waited for, and the word the pausing workgroups bump is looked at.  Unchanged: three launches.  Changed: the paused windows are
+// brought level on the four-launch route (resume_paused) and the call that follows takes that route too — where one term moved past
+// the threshold, others are about to.
+static int settle_pauses(okvis_ba_solver* s, bool* four) {
+  *four = true;
+  if (!s->plan.three) return OKVIS_BA_OK;
+  if (s->three_unseen) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    s->three_unseen = false;
+  }
+  const int word = __atomic_load_n(s->h_pause, __ATOMIC_ACQUIRE);
+  if (word != s->pause_seen) {
+    s->pause_seen = word;
+    std::vector<Ctrl> cs;
+    if (int rc = fetch_ctrl(s, cs)) return rc;
+    int n_paused = 0;
+    return resume_paused(s, cs, &n_paused);
+  }
+  *four = s->start_four;
   return OKVIS_BA_OK;
 }
 
@@ -828,30 +887,52 @@ int okvis_ba_iterate(okvis_ba_solver* s, int n) {
   if (!s->begun) return OKVIS_BA_ERR_STATE;
   if (n == 0) return OKVIS_BA_OK;
   HIP_TRY(hipSetDevice(s->device));
+  bool four = true;
+  if (int rc = settle_pauses(s, &four)) return rc;
+  if (s->plan.three && !four) s->three_unseen = true;
   s->slots += n;
-  HIP_TRY(hipEventRecord(s->ev0, s->stream));
   const int nsub = (int)s->sub_streams.size();
+  // The graph of sub-batch k's chain (nsub > 1: one graph per sub-batch, each replayed on its own stream — independent launches
+  // overlap; branches inside ONE captured graph were measured not to) or of the whole call (k = -1), on the route `r`: captured at
+  // its first use.  A plan with the three-launch iteration captures a call length's graphs of BOTH routes at its first use: which
+  // route a later call of that length takes is the device's news, and a caller who replays a call length it has issued before
+  // expects no capture in it.
+  auto graph_of = [&](int k, bool r, hipGraphExec_t* exec) -> int {
+    const int key = graph_key(n, r);
+    if (k >= 0) {
+      auto it = s->sub_graphs.find({key, k});
+      if (it != s->sub_graphs.end()) return *exec = it->second, OKVIS_BA_OK;
+    } else {
+      auto it = s->graphs.find(key);
+      if (it != s->graphs.end()) return *exec = it->second, OKVIS_BA_OK;
+    }
+    hipGraph_t graph = nullptr;
+    const hipStream_t st = k >= 0 ? s->sub_streams[k] : s->stream;
+    HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeRelaxed));
+    hipError_t e = k >= 0 ? launch_chain(s, sub(st, s->plan.subs[k]), n, n, r) : launch_iterations_forked(s, n, -1, r);
+    hipError_t e2 = hipStreamEndCapture(st, &graph);
+    if (e != hipSuccess) HIP_TRY(e);
+    HIP_TRY(e2);
+    HIP_TRY(hipGraphInstantiate(exec, graph, nullptr, nullptr, 0));
+    HIP_TRY(hipGraphDestroy(graph));
+    if (k >= 0) s->sub_graphs[{key, k}] = *exec;
+    else s->graphs[key] = *exec;
+    return OKVIS_BA_OK;
+  };
+  std::vector<hipGraphExec_t> execs;
+  if (s->plan.graph) {
+    for (int k = nsub > 1 ? 0 : -1; k < (nsub > 1 ? nsub : 0); ++k) {
+      hipGraphExec_t exec = nullptr, other = nullptr;
+      if (int rc = graph_of(k, four, &exec)) return rc;
+      if (s->plan.three)
+        if (int rc = graph_of(k, !four, &other)) return rc;
+      execs.push_back(exec);
+    }
+  }
+  HIP_TRY(hipEventRecord(s->ev0, s->stream));   // (behind the captures: a capture swallows an event record)
   if (s->plan.graph && nsub > 1) {
-    // one graph per sub-batch, each replayed on its own stream (independent launches overlap; branches
-    // inside ONE captured graph were measured not to)
     HIP_TRY(hipEventRecord(s->ev_fork, s->stream));
     for (int k = 0; k < nsub; ++k) {
-      hipGraphExec_t exec = nullptr;
-      auto it = s->sub_graphs.find({n, k});
-      if (it == s->sub_graphs.end()) {
-        hipGraph_t graph = nullptr;
-        const Sub b = sub(s->sub_streams[k], s->plan.subs[k]);
-        HIP_TRY(hipStreamBeginCapture(b.st, hipStreamCaptureModeRelaxed));
-        hipError_t e = launch_chain(s, b, n, n);
-        hipError_t e2 = hipStreamEndCapture(b.st, &graph);
-        if (e != hipSuccess) HIP_TRY(e);
-        HIP_TRY(e2);
-        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-        HIP_TRY(hipGraphDestroy(graph));
-        s->sub_graphs[{n, k}] = exec;
-      } else {
-        exec = it->second;
-      }
       HIP_TRY(hipStreamWaitEvent(s->sub_streams[k], s->ev_fork, 0));
       // the sub-batches start staggered by a third (1 / nsub) of one iteration chain: started together, the streams lock into
       // one of two interleavings (0.162 or 0.179 ms per step at 64 windows, whole timed regions in either); the stagger
@@ -860,31 +941,14 @@ int okvis_ba_iterate(okvis_ba_solver* s, int n) {
         hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(64), 0, s->sub_streams[k], (long long)k * s->stagger_ticks);
         HIP_TRY(hipGetLastError());
       }
-      HIP_TRY(hipGraphLaunch(exec, s->sub_streams[k]));
+      HIP_TRY(hipGraphLaunch(execs[k], s->sub_streams[k]));
       HIP_TRY(hipEventRecord(s->sub_events[k], s->sub_streams[k]));
       HIP_TRY(hipStreamWaitEvent(s->stream, s->sub_events[k], 0));
     }
   } else if (s->plan.graph) {
-    hipGraphExec_t exec = nullptr;
-    auto it = s->graphs.find(n);
-    if (it == s->graphs.end()) {
-      hipGraph_t graph = nullptr;
-      HIP_TRY(hipStreamBeginCapture(s->stream, hipStreamCaptureModeRelaxed));
-      hipError_t e = launch_iterations_forked(s, n);
-      hipError_t e2 = hipStreamEndCapture(s->stream, &graph);
-      if (e != hipSuccess) HIP_TRY(e);
-      HIP_TRY(e2);
-      HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-      HIP_TRY(hipGraphDestroy(graph));
-      s->graphs[n] = exec;
-      // the capture swallowed the first event record: re-record outside the graph
-      HIP_TRY(hipEventRecord(s->ev0, s->stream));
-    } else {
-      exec = it->second;
-    }
-    HIP_TRY(hipGraphLaunch(exec, s->stream));
+    HIP_TRY(hipGraphLaunch(execs[0], s->stream));
   } else {
-    HIP_TRY(launch_iterations_forked(s, n));
+    HIP_TRY(launch_iterations_forked(s, n, -1, four));
   }
   HIP_TRY(hipEventRecord(s->ev1, s->stream));
   return OKVIS_BA_OK;
@@ -926,10 +990,27 @@ int okvis_ba_finish(okvis_ba_solver* s, okvis_ba_summary* summaries) {
         HIP_TRY(hipMemcpyAsync(s->stage_res.data(), H0.ptrs.results, res_bytes, hipMemcpyDeviceToHost, s->stream));
       }
     }
-    return fetch_ctrl(s, cs);
+    return fetch_ctrl(s, cs, s->plan.three != 0);
   };
   int rc = finalize();
   if (rc != OKVIS_BA_OK) return rc;
+  if (s->plan.three) {
+    // The three-launch iteration: a window the solve kernel paused (the launches above skipped it like a finished one) still owes
+    // iterations.  It gets them on the four-launch route, where nothing pauses; then the final decision is taken again.
+    s->three_unseen = false;
+    int n_paused = 0;
+    if ((rc = resume_paused(s, cs, &n_paused)) != OKVIS_BA_OK) return rc;
+    if (n_paused > 0) {
+      HIP_TRY(launch_schur(s, whole(s), 1));
+      HIP_TRY(launch_solve(s, whole(s), 1));
+      if ((rc = finalize()) != OKVIS_BA_OK) return rc;
+    }
+    // the next begin ... finish starts on the four-launch route if this one paused or re-preintegrated: its windows are on the move
+    long redone = 0;
+    for (const Ctrl& c : cs) redone += c.pad2;
+    s->pause_seen = __atomic_load_n(s->h_pause, __ATOMIC_ACQUIRE);
+    s->start_four = s->pause_seen != s->pause_begin || redone > 0;
+  }
   if (s->opt.strategy == OKVIS_BA_STRATEGY_DOGLEG && !s->opt.gauss_newton) {
     // Dogleg: a launch slot that had to redo a mis-speculated Gauss-Newton trial as an explicit dogleg step did not
     // finish an iteration, and the decision just taken may itself ask for such a redo.  Windows that still owe
@@ -946,7 +1027,7 @@ int okvis_ba_finish(okvis_ba_solver* s, okvis_ba_summary* summaries) {
       }
       if (need <= 0) break;
       s->slots += need;
-      HIP_TRY(launch_iterations_forked(s, need, 0));   // (on the sub-batch streams like every other iteration; no new budget)
+      HIP_TRY(launch_iterations_forked(s, need, 0, true));   // (on the sub-batch streams like every other iteration; no new budget)
       HIP_TRY(launch_schur(s, whole(s), 1));
       HIP_TRY(launch_solve(s, whole(s), 1));
       rc = finalize();
@@ -1068,6 +1149,15 @@ int okvis_ba_launch_route(okvis_ba_solver* s, int32_t* route) {
   // (linearize2_rec_kernel: the group launch records; 0 = linearize2_kernel through the window record, OKVIS_BA_TUNE_LIN_NO_RECORDS)
   route[OKVIS_BA_ROUTE_LIN_RECORDS] = p.grec_stride > 0;
   route[OKVIS_BA_ROUTE_SOLVE_MODE] = p.solve.k == SOLVE_NONE ? 0 : p.solve.k >= SOLVE_CHAIN ? OKVIS_BA_SOLVE_CHAIN : OKVIS_BA_SOLVE_DENSE;
+  route[OKVIS_BA_ROUTE_THREE_LAUNCH] = p.three;
+  return OKVIS_BA_OK;
+}
+int okvis_ba_pause_count(okvis_ba_solver* s, int64_t* count) {
+  if (!s || !count) return OKVIS_BA_ERR_ARG;
+  if (!s->uploaded) return OKVIS_BA_ERR_STATE;
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  *count = __atomic_load_n(s->h_pause, __ATOMIC_ACQUIRE) - s->pause_begin;
   return OKVIS_BA_OK;
 }
 int okvis_ba_pair_count(okvis_ba_solver* s, int w, int32_t* n_pair) {

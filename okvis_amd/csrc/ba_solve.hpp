@@ -137,6 +137,14 @@ constexpr int SOLVE_HELPERS = 4;   // workgroups per window (blockIdx.y < SOLVE_
 constexpr int SOLVE_HELPED_MAX_WINDOWS = 8;   // launches of more windows sum inside the solving workgroup (a helper takes a whole CU)
 constexpr int MARG_BLOCKS_MAX = MAX_MARG_DIM / 6;   // blocks of a marginalisation prior (staged in LDS by assemble_base)
 constexpr int PRE_BLOCKS = 32;  // pose / speed-bias blocks whose accepted values the solve kernel stages in LDS ahead of time
+// The three-launch iteration (no small_prepare_kernel behind the solve launch; make_plan, capi_launch.inc): windows of at most this
+// many IMU terms; Ctrl::done of a window whose IMU records need that launch before its trial can be evaluated (the host clears it:
+// resume_paused, capi_launch.inc; it never reaches a summary)
+constexpr int PAUSE_MAX_TERMS = 16;
+constexpr int DONE_PAUSED = 64;
+// |b_g - b_g,ref| * dt above this is "not quiet": below ImuError.cpp:549's 1e-4 by more than the two evaluations of the product can
+// differ in rounding, so that a re-preintegration imu_factor<1> would start is never missed
+constexpr double PAUSE_BIAS_THRESHOLD = 1e-4 * (1.0 - 1e-6);
 
 // IMU Hessian blocks, priors and the marginalisation prior of linearisation buffer `acc`, accumulated into S
 // (block layout LY), g and d2.  (The reprojection part U_pp / U_pe / g_p arrives inside the Schur partials.)
@@ -505,8 +513,13 @@ __device__ __forceinline__ void solve_failed_dl(Ctrl* c, const OptD& opt) {
 // and solved by chain_solve — speed/bias blocks eliminated along the IMU chain, then the dense pose system.
 template <bool LARGE, bool DBUF, bool CHAIN = false>
 __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __restrict__ wins,
-                                                              const OptD* __restrict__ optp, int final_only, CtrlSlot* ctrls) {
+                                                              const OptD* __restrict__ optp, int final_only, CtrlSlot* ctrls,
+                                                              int* pause_word) {
   static_assert(!(LARGE && DBUF), "windows solved in HBM are never fused");
+  // The three-launch iteration (pause_word != nullptr: Schur -> solve -> linearise, no small_prepare_kernel behind this launch): the
+  // tail repeats the first half of every IMU term's factor (imu_factor<1>, ba_imu.hpp) far enough to know that it would do nothing,
+  // and pauses the window where it cannot tell (see pause_check below).  Only the instantiations such a route names carry the code.
+  constexpr bool PAUSE = !LARGE && DBUF;
   static_assert(!(LARGE && CHAIN), "the chain solver is an LDS solver");
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const long long t_start = clock64();   // (diagnostics: stamp 43)
@@ -702,6 +715,32 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
                         imu_v##j = src[on ? idx : 0]; }   /* (a lane without an entry: masked behind the barrier, see BA_IMU_MASK) */
     BA_IMU_REQ(0) BA_IMU_REQ(1) BA_IMU_REQ(2) BA_IMU_REQ(3) BA_IMU_REQ(4) BA_IMU_REQ(5)
 #undef BA_IMU_REQ
+  }
+  // the three-launch route's check of the IMU terms (PAUSE): what it needs of term f is requested here with everything else, two
+  // 64-bit words (and one int) per work-item of the wave behind the staged states — work-item 64 + 10 PRE_BLOCKS + 16 r + f has role r
+  // for term f: 0 = the validity words of its record and of the record's kept predecessor (+ its speed/bias block), 1 / 2 = the gyro
+  // part of the record's reference bias, 3 = its two time stamps.  Parked in LDS by stage_stores.  (Roles, not one work-item per
+  // term: thirteen registers held from here to there cost the chain instantiation 26 spilled registers; this way they are five.)
+  __shared__ double s_pz_ref[3 * PAUSE_MAX_TERMS], s_pz_dt[PAUSE_MAX_TERMS];
+  __shared__ int s_pz_ok[PAUSE_MAX_TERMS], s_pz_sb[PAUSE_MAX_TERMS], s_pause;
+  static_assert(PAUSE_MAX_TERMS == 16 && offsetof(ImuCacheD, valid) % 8 == 0, "16 terms x 4 roles = one wave; valid | redo_count is one word");
+  long long pz_a = 0, pz_b = 0;
+  int pz_c = 0;
+  const bool pz_on = PAUSE && pause_word != nullptr && W.n_imu > 0;   // (uniform)
+  if constexpr (PAUSE) {
+    if (pz_on) {
+      typedef const __attribute__((address_space(1))) long long* gll;
+      const int u = tl - PRE_BLOCKS * 10, role = (u >> 4) & 3, f = u & 15;
+      const int fc = (u >= 0 && f < W.n_imu) ? f : 0;
+      auto cg = W.imu_cache + fc;
+      auto cp = W.imu_cache_prev + fc;
+      const gll pa = role == 0 ? (gll)(&cg->valid) : role == 1 ? (gll)(&cg->sb_ref[3])
+                     : role == 2 ? (gll)(&cg->sb_ref[5]) : as_global(W.imu_t0) + fc;
+      const gll pb = role == 0 ? (gll)(&cp->valid) : role == 1 ? (gll)(&cg->sb_ref[4])
+                     : role == 2 ? (gll)(&cg->sb_ref[5]) : as_global(W.imu_t1) + fc;
+      pz_a = *pa, pz_b = *pb;
+      pz_c = W.imu_sb0[fc];
+    }
   }
   // ---- the entries of the staged priors (formed by wave 0 behind its decision, added behind the IMU records): J^T J / J^T r
   // with the expressions of add_small_factor (same bits).  Pose prior p and speed/bias prior p never share a block, so they go
@@ -905,6 +944,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
       s_old_cost = c.cost;
       s_lm_gmax = 0;
       s_fail = 0;
+      if constexpr (PAUSE) s_pause = 0;
       if (opt.dogleg) {
         if (pending) {
           c.last_rho = dl.rho;
@@ -1060,6 +1100,19 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
         } else if (pre_on && t64 < PRE_BLOCKS * 10) {
           const int to = t64 - PRE_BLOCKS * 8;
           s_preoff[to] = to < PRE_BLOCKS ? (to < W.n_pose ? pre_po : -1) : (to - PRE_BLOCKS < W.n_sb ? pre_so : -1);
+        } else if (PAUSE && pz_on && t64 < PRE_BLOCKS * 10 + 4 * PAUSE_MAX_TERMS) {
+          const int u = t64 - PRE_BLOCKS * 10, role = u >> 4, f = u & 15;
+          if (role == 0) {
+            // 1 = a record that stands (valid == 1) and no kept predecessor to take back or drop; -1 = no such term
+            s_pz_ok[f] = f < W.n_imu ? ((int)pz_a == 1 && (int)pz_b == 0) : -1;
+            s_pz_sb[f] = pz_c;
+          } else if (role == 1) {
+            s_pz_ref[3 * f] = __longlong_as_double(pz_a), s_pz_ref[3 * f + 1] = __longlong_as_double(pz_b);
+          } else if (role == 2) {
+            s_pz_ref[3 * f + 2] = __longlong_as_double(pz_a);
+          } else {
+            s_pz_dt[f] = ns_to_sec(pz_b - pz_a);
+          }
         }
       };
       // The flag the other waves follow carries this launch's count (a stale word of an earlier workgroup on this CU cannot
@@ -1381,6 +1434,55 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
     }
   }
   STAMP(6);
+  // ---- the three-launch route's check (PAUSE), behind trial_states and in front of the barrier of the step's scalars: work-item
+  // 192 + f forms the trial gyro bias of IMU term f from the LDS copies with the single addition trial_states stores (the same
+  // bits) and repeats the bias check of imu_factor<1> with a margin (PAUSE_BIAS_THRESHOLD).  A term whose record does not simply
+  // stand (first use, a record handed over or built ahead, a kept predecessor) or whose bias may have moved past the threshold
+  // pauses the window: imu_factor<1> alone takes the exact decision, in the launch the host then adds.
+  auto pause_check = [&]() {
+    if constexpr (PAUSE) {
+      const int f = tid - 192;
+      if (pz_on && f >= 0 && f < PAUSE_MAX_TERMS) {
+        if (Wl.n_imu > PAUSE_MAX_TERMS) s_pause = 1;   // (never on a route make_plan names: terms nobody looked at)
+        const int ok = s_pz_ok[f];
+        if (ok >= 0) {
+          const int b = s_pz_sb[f];
+          double v[3];
+          int off;
+          if (b < PRE_BLOCKS) {
+            off = s_preoff[PRE_BLOCKS + b];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = s_pre[PRE_BLOCKS * 7 + 9 * b + 3 + k];
+          } else {
+            off = Wl.sb_off[b];
+            auto xp = as_global(Wl.sb[acc] + 9 * (size_t)b);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) v[k] = xp[3 + k];
+          }
+          double q = 0;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const double d = off >= 0 ? s_x[off + 3 + k] : 0.0;
+            const double db = (v[k] + d) - s_pz_ref[3 * f + k];
+            q += db * db;
+          }
+          if (!(ok == 1 && sqrt(q) * s_pz_dt[f] <= PAUSE_BIAS_THRESHOLD)) s_pause = 1;
+        }
+      }
+    }
+  };
+  // (work-item 0, behind that barrier: the window pauses — its trial is published as usual, every kernel skips it until the host has
+  //  run the prepare launch for it, and one word of pinned host memory tells the host so)
+  auto pause_mark = [&]() {
+    if constexpr (PAUSE) {
+      if (pz_on && s_pause) c.done = DONE_PAUSED;
+    }
+  };
+  auto pause_tell = [&]() {
+    if constexpr (PAUSE) {
+      if (pz_on && s_pause) __hip_atomic_fetch_add(pause_word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  };
   if constexpr (!LARGE) {
     if (opt.dogleg && c.explicit_next) {
       // ------------------------------------------------------------ explicit dogleg step (no factorisation)
@@ -1443,6 +1545,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
       __syncthreads();
       double s2 = 0, x2 = 0;
       trial_states(Wl, acc, s_x, tid, true, &s2, &x2, pre_on ? s_pre : nullptr, pre_on ? s_preoff : nullptr);
+      pause_check();
       s2 = wave_sum_full(s2);
       x2 = wave_sum_full(x2);
       if ((tid & 63) == 0) {
@@ -1464,7 +1567,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
         c.explicit_next = 0;
         c.lambda = mu;
         c.pending = 1;
+        pause_mark();
         *gctrl = c;
+        pause_tell();
       }
       return;
     }
@@ -1534,6 +1639,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
     STAMP(31);
     double x2 = 0, s2a = 0;
     trial_states(Wl, acc, s_x, tid, opt.dogleg != 0, &s2a, &x2, pre_on ? s_pre : nullptr, pre_on ? s_preoff : nullptr);
+    pause_check();
     STAMP(32);
     if (opt.dogleg) s2 = s2a;   // Ceres' step_norm is |x - x_plus_delta| over the ambient coordinates
     __shared__ double s_sc[4][SOLVE_THREADS / 64];
@@ -1568,7 +1674,9 @@ __global__ __launch_bounds__(SOLVE_THREADS) void solve_kernel(const WinPtrs* __r
       c.have_tot = 0;
       c.iter++;
       c.pending = 1;
+      pause_mark();
       *gctrl = c;
+      pause_tell();
     }
   }
   STAMP(9);

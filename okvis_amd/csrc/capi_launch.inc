@@ -98,6 +98,7 @@ enum { SMALL_NONE, SMALL_ALL, SMALL_PREPARE };
 // okvis_ba_upload computes it, okvis_ba_set_options again for the options of an uploaded batch, and every launch of the solver reads
 // it.  The layout fixed at upload bounds what later options can select: a batch uploaded under LM keeps its deciding Schur launch
 // after a switch to DOGLEG.
+Extent make_extent(int w0, int nw) { return Extent{w0, nw, nw <= SOLVE_HELPED_MAX_WINDOWS ? SOLVE_HELPERS : 0}; }
 LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_options& o, int n_windows) {
   LaunchPlan p;
   const bool f32 = o.fp32_linearize != 0;
@@ -169,6 +170,13 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
   // the preintegrations a discarded speculative evaluation left behind (DOGLEG), taken back before results leave the device
   if (M.imu > 0 && o.strategy == OKVIS_BA_STRATEGY_DOGLEG && !o.gauss_newton) p.take_back = Launch{1, M.imu, 0};
   p.budget = o.strategy == OKVIS_BA_STRATEGY_DOGLEG;
+  // The three-launch iteration: where the factors' launch of an iteration is small_prepare_kernel alone, that launch does nothing
+  // while no IMU term needs a new preintegration.  The solve kernel's tail finds out (its DBUF instantiations, which the riding
+  // route always names) and pauses the windows that need it; the host adds the launch for them (resume_paused).  It takes the
+  // iteration budget (a paused window is level again after the slots it owes) and windows of at most PAUSE_MAX_TERMS IMU terms
+  // solved in LDS.  okvis_ba_tuning::flags & OKVIS_BA_TUNE_FOUR_LAUNCH keeps small_prepare_kernel in every slot (the referee).
+  p.three = p.small_iter.k == SMALL_PREPARE && p.budget && M.imu <= PAUSE_MAX_TERMS && p.solve.k != SOLVE_NONE && p.tiled.k == SOLVE_NONE &&
+            !(o.tuning.flags & OKVIS_BA_TUNE_FOUR_LAUNCH);
   // ---- sub-batches: opt.n_streams (0 = auto).  Measured at 64 windows (scripts/sweep_streams.sh, r02): 1 stream 272 k,
   //      2: 300 k, 3: 325 k, 4: 198 k window-iterations/s — the streams of the process that have work, or ever had, must not
   //      exceed four (whatever GPU_MAX_HW_QUEUES and the stream priorities say: scripts/r06_streams.sh, r06_streams2.sh,
@@ -181,7 +189,7 @@ LaunchPlan make_plan(const BatchLayout& L, const BatchMax& M, const okvis_ba_opt
   nsub = std::max(1, std::min(nsub, n_windows));
   // helper workgroups per window sum the Schur chunk partials for the solving one; launches of more windows sum inside the
   // solving workgroup (a helper takes a whole CU)
-  auto extent = [](int w0, int nw) { return Extent{w0, nw, nw <= SOLVE_HELPED_MAX_WINDOWS ? SOLVE_HELPERS : 0}; };
+  auto extent = [](int w0, int nw) { return make_extent(w0, nw); };
   for (int k = 0; k < nsub; ++k) {
     const int w0 = (int)((int64_t)n_windows * k / nsub), w1 = (int)((int64_t)n_windows * (k + 1) / nsub);
     p.subs.push_back(extent(w0, w1 - w0));
@@ -214,10 +222,34 @@ __global__ void begin_kernel(const WinPtrs* wins, const int* accs, double initia
   }
 }
 // the control records of all windows into one contiguous array (one device-to-host copy instead of one per window)
-__global__ void gather_ctrl_kernel(const WinPtrs* wins, Ctrl* out, int n) {
+// (redo_mark != nullptr: the copy's spare word pad2 = the re-preintegrations of the window's IMU terms since redo_mark_kernel)
+__global__ void gather_ctrl_kernel(const WinPtrs* wins, Ctrl* out, int n, const int* redo_mark) {
   const int w = blockIdx.x * (blockDim.x / 64) + threadIdx.x / 64, lane = threadIdx.x & 63;
-  if (w < n && lane < (int)(sizeof(Ctrl) / 8))
-    reinterpret_cast<double*>(out + w)[lane] = reinterpret_cast<const double*>(wins[w].ctrl)[lane];
+  if (w >= n) return;
+  constexpr int last = (int)(sizeof(Ctrl) / 8) - 1;   // (have_tot | pad2)
+  static_assert(offsetof(Ctrl, pad2) == sizeof(Ctrl) - 4, "the spare word closes the record");
+  if (lane > last) return;
+  union { double d; int i[2]; } v;
+  v.d = reinterpret_cast<const double*>(wins[w].ctrl)[lane];
+  if (redo_mark && lane == last) {   // (a dozen terms: the work-item that copies the word)
+    int r = 0;
+    for (int f = 0; f < wins[w].n_imu; ++f) r += wins[w].imu_cache[f].redo_count;
+    v.i[1] = r - redo_mark[w];
+  }
+  reinterpret_cast<double*>(out + w)[lane] = v.d;
+}
+// the re-preintegrations every window has seen so far (behind okvis_ba_begin's evaluation: what the iterations add is what counts)
+__global__ void redo_mark_kernel(const WinPtrs* wins, int* redo_mark, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w >= n) return;
+  int r = 0;
+  for (int f = 0; f < wins[w].n_imu; ++f) r += wins[w].imu_cache[f].redo_count;
+  redo_mark[w] = r;
+}
+// a paused window runs again (its trial is still pending: the factors' launch and linearise come next)
+__global__ void resume_kernel(const WinPtrs* wins, int n) {
+  const int w = blockIdx.x * blockDim.x + threadIdx.x;
+  if (w < n && wins[w].ctrl->done == DONE_PAUSED) wins[w].ctrl->done = 0;
 }
 
 // keeps one wave busy for `ticks` of the 100 MHz wall clock (the start stagger of the sub-batch streams)
@@ -250,13 +282,15 @@ hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
   return hipGetLastError();
 }
 // one solve_kernel launch (l: the plan's solve or tiled) on the window records `wins`
-void launch_solve_kernel(okvis_ba_solver* s, const Launch& l, dim3 grid, hipStream_t st, const WinPtrs* wins, int final_only, CtrlSlot* ctrls) {
+// (pause: the three-launch iteration's word, nullptr on every other route and in every launch that is not an iteration's)
+void launch_solve_kernel(okvis_ba_solver* s, const Launch& l, dim3 grid, hipStream_t st, const WinPtrs* wins, int final_only, CtrlSlot* ctrls,
+                         int* pause = nullptr) {
   const SolveFn fn = SOLVE[l.k];
-  hipLaunchKernelGGL(fn, grid, dim3(SOLVE_THREADS), l.lds, st, wins, s->d_opt, final_only, ctrls);
+  hipLaunchKernelGGL(fn, grid, dim3(SOLVE_THREADS), l.lds, st, wins, s->d_opt, final_only, ctrls, pause);
 }
-hipError_t launch_solve(okvis_ba_solver* s, Sub b, int final_only) {
+hipError_t launch_solve(okvis_ba_solver* s, Sub b, int final_only, int* pause = nullptr) {
   const LaunchPlan& p = s->plan;
-  if (p.solve.k) launch_solve_kernel(s, p.solve, dim3((unsigned)b.nw, 1 + b.helpers), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0);
+  if (p.solve.k) launch_solve_kernel(s, p.solve, dim3((unsigned)b.nw, 1 + b.helpers), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0, pause);
   if (p.tiled.k) {
     launch_solve_kernel(s, p.tiled, dim3((unsigned)b.nw), b.st, s->d_wins + b.w0, final_only, s->d_ctrl + b.w0);
     if (!final_only) {
@@ -271,10 +305,12 @@ hipError_t launch_solve(okvis_ba_solver* s, Sub b, int final_only) {
   return hipGetLastError();
 }
 // the IMU / prior factors' launch of their own (init: okvis_ba_begin's), then the linearise launch
-hipError_t launch_lin(okvis_ba_solver* s, Sub b, int init) {
+// (factors = false: the three-launch iteration, whose small_iter — small_prepare_kernel — runs only for windows that paused)
+hipError_t launch_lin(okvis_ba_solver* s, Sub b, int init, bool factors = true) {
   const LaunchPlan& p = s->plan;
   const WinPtrs* wins = s->d_wins + b.w0;
-  const Launch& f = init ? p.small_init : p.small_iter;
+  const Launch none;
+  const Launch& f = !factors ? none : init ? p.small_init : p.small_iter;
   if (f.k == SMALL_ALL) hipLaunchKernelGGL(small_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins, init);
   if (f.k == SMALL_PREPARE) hipLaunchKernelGGL(small_prepare_kernel, dim3((unsigned)f.gx, (unsigned)b.nw), dim3(LIN_THREADS), f.lds, b.st, wins);
   const dim3 grid((unsigned)p.lin.gx, (unsigned)b.nw);
@@ -297,32 +333,38 @@ hipError_t launch_imu_take_back(okvis_ba_solver* s, int w0, int nw) {
   hipLaunchKernelGGL(imu_take_back_kernel, dim3((unsigned)s->plan.take_back.gx, (unsigned)nw), dim3(64), 0, s->stream, s->d_wins + w0);
   return hipGetLastError();
 }
-hipError_t launch_iteration(okvis_ba_solver* s, Sub b) {
+// One iteration on the plan's route.  four = false asks for the three-launch iteration where the plan has it (LaunchPlan::three):
+// Schur -> solve (with the pause check) -> linearise; otherwise every launch of the plan (four of them where three exists: the referee
+// and the fall-back).
+hipError_t launch_iteration(okvis_ba_solver* s, Sub b, bool four) {
+  const bool three = s->plan.three && !four;
   hipError_t e;
   if ((e = launch_schur(s, b)) != hipSuccess) return e;
-  if ((e = launch_solve(s, b, 0)) != hipSuccess) return e;
-  return launch_lin(s, b, 0);
+  if ((e = launch_solve(s, b, 0, three ? s->d_pause : nullptr)) != hipSuccess) return e;
+  return launch_lin(s, b, 0, !three);
 }
+// captured graphs are keyed on the call length and the route
+inline int graph_key(int n, bool four) { return 2 * n + (four ? 1 : 0); }
 hipError_t launch_budget(okvis_ba_solver* s, Sub b, int n) {
   if (!s->plan.budget || n <= 0) return hipSuccess;
   hipLaunchKernelGGL(add_budget_kernel, dim3((unsigned)b.nw), dim3(64), 0, b.st, s->d_wins + b.w0, n);
   return hipGetLastError();
 }
 // the chain of one sub-batch: the iteration budget, then n iterations (eager, or captured into the sub-batch's graph)
-hipError_t launch_chain(okvis_ba_solver* s, Sub b, int n, int budget) {
+hipError_t launch_chain(okvis_ba_solver* s, Sub b, int n, int budget, bool four) {
   hipError_t e = launch_budget(s, b, budget);
-  for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, b);
+  for (int i = 0; i < n && e == hipSuccess; ++i) e = launch_iteration(s, b, four);
   return e;
 }
 // n iterations of every sub-batch: fork from the main stream, one chain per sub-stream, join
-hipError_t launch_iterations_forked(okvis_ba_solver* s, int n, int budget = -1) {
+hipError_t launch_iterations_forked(okvis_ba_solver* s, int n, int budget, bool four) {
   const int nsub = (int)s->sub_streams.size();
   if (budget < 0) budget = n;
-  if (nsub <= 1) return launch_chain(s, whole(s), n, budget);
+  if (nsub <= 1) return launch_chain(s, whole(s), n, budget, four);
   hipError_t e = hipEventRecord(s->ev_fork, s->stream);
   for (int k = 0; k < nsub && e == hipSuccess; ++k) {
     e = hipStreamWaitEvent(s->sub_streams[k], s->ev_fork, 0);
-    if (e == hipSuccess) e = launch_chain(s, sub(s->sub_streams[k], s->plan.subs[k]), n, budget);
+    if (e == hipSuccess) e = launch_chain(s, sub(s->sub_streams[k], s->plan.subs[k]), n, budget, four);
     if (e == hipSuccess) e = hipEventRecord(s->sub_events[k], s->sub_streams[k]);
     if (e == hipSuccess) e = hipStreamWaitEvent(s->stream, s->sub_events[k], 0);
   }
@@ -341,7 +383,7 @@ int refresh_acc(okvis_ba_solver* s, int w) {
 
 // grow-only staging for begin_kernel's buffer indices and the gathered control records (pinned host + device)
 hipError_t reserve_ctrl_stage(okvis_ba_solver* s, size_t n_windows) {
-  const size_t bytes = std::max(sizeof(Ctrl), sizeof(int)) * n_windows;
+  const size_t bytes = std::max(sizeof(Ctrl), sizeof(int)) * n_windows;   // (begin_kernel's indices or the gathered records, never both)
   if (bytes <= s->ctrl_stage_bytes) return hipSuccess;
   if (s->h_ctrl_stage) (void)hipHostFree(s->h_ctrl_stage);
   if (s->d_ctrl_stage) (void)hipFree(s->d_ctrl_stage);
@@ -353,15 +395,49 @@ hipError_t reserve_ctrl_stage(okvis_ba_solver* s, size_t n_windows) {
   return e;
 }
 
-int fetch_ctrl(okvis_ba_solver* s, std::vector<Ctrl>& out) {
+// (redo: Ctrl::pad2 of the copies = the window's re-preintegrations since okvis_ba_begin's evaluation — plans with the three-launch
+// iteration, whose okvis_ba_begin left the mark)
+int fetch_ctrl(okvis_ba_solver* s, std::vector<Ctrl>& out, bool redo = false) {
   const size_t n = s->wins.size();
   out.resize(n);
   HIP_TRY(reserve_ctrl_stage(s, n));
-  hipLaunchKernelGGL(gather_ctrl_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s->stream, s->d_wins, reinterpret_cast<Ctrl*>(s->d_ctrl_stage), (int)n);
+  hipLaunchKernelGGL(gather_ctrl_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s->stream, s->d_wins, reinterpret_cast<Ctrl*>(s->d_ctrl_stage), (int)n,
+                     redo && s->redo_mark_windows >= n ? s->d_redo_mark : nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(s->h_ctrl_stage, s->d_ctrl_stage, sizeof(Ctrl) * n, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   std::memcpy(out.data(), s->h_ctrl_stage, sizeof(Ctrl) * n);
+  return OKVIS_BA_OK;
+}
+
+// The host's part of the three-launch iteration: the windows the solve kernel paused (cs: their control records, just fetched; the
+// stream is idle) get what the skipped slots would have given them, on the four-launch route — the factors' launch and linearise for
+// the trial that is pending, then the slots they owe of the budget granted so far.  Runs of neighbouring windows that owe the same
+// number of slots share their launches; no other window is touched (a window that owes nothing must not meet a slot: the budget
+// would end it for good).  *n_paused: how many there were.
+int resume_paused(okvis_ba_solver* s, const std::vector<Ctrl>& cs, int* n_paused) {
+  const int n = (int)cs.size();
+  auto owes = [&](int w) { return cs[w].done == DONE_PAUSED ? std::max(0, cs[w].max_iter - cs[w].iter) : -1; };
+  int most = 0;
+  *n_paused = 0;
+  for (int w0 = 0; w0 < n;) {
+    const int need = owes(w0);
+    int w1 = w0 + 1;
+    if (need < 0) {
+      w0 = w1;
+      continue;
+    }
+    while (w1 < n && owes(w1) == need) ++w1;
+    const Sub b = sub(s->stream, make_extent(w0, w1 - w0));
+    hipLaunchKernelGGL(resume_kernel, dim3((unsigned)((b.nw + 63) / 64)), dim3(64), 0, b.st, s->d_wins + b.w0, b.nw);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lin(s, b, 0));
+    HIP_TRY(launch_chain(s, b, need, 0, true));
+    most = std::max(most, need);
+    *n_paused += b.nw;
+    w0 = w1;
+  }
+  s->slots += most;
   return OKVIS_BA_OK;
 }
 

@@ -120,6 +120,7 @@ struct PlanFixed {
   Launch small_init, small_iter, lin; int lin_n_small = 0, sd = 0;   // the factors' launch of okvis_ba_begin / of an iteration; linearise
   int grec_stride = 0;   // > 0: lin names a record instantiation (LIN2R, capi_launch.inc); its group launch records per window
   Launch take_back; int budget = 0;                    // imu_take_back_kernel; add_budget_kernel in front of the iterations
+  int three = 0;   // 1 = the three-launch iteration is this plan's default: Schur -> solve -> linearise, small_iter only for windows that paused
   Extent whole; int one_helpers = 0;                   // okvis_ba_begin / okvis_ba_finish; okvis_ba_marginalize (one window)
 };
 struct LaunchPlan : PlanFixed {
@@ -190,8 +191,18 @@ struct okvis_ba_solver {
   long long stagger_ticks = 0;   // start offset between consecutive sub-batch streams (wall_clock64 ticks, 100 MHz); okvis_ba_tuning::stagger_us
   bool skip_topup = false;   // okvis_ba_optimize_timed ran out of time: finish() must not grant the slots mis-speculated steps still owe
   long long slots = 0;   // launch slots (schur + solve + linearise triples) since okvis_ba_begin: diagnostics (array 96)
+  // captured graphs, keyed on the call length and the route (graph_key, capi_launch.inc); per sub-batch: (key, sub) -> its chain's graph
   std::map<int, hipGraphExec_t> graphs;
-  std::map<std::pair<int, int>, hipGraphExec_t> sub_graphs;  // (n, sub) -> graph of that sub-batch's chain
+  std::map<std::pair<int, int>, hipGraphExec_t> sub_graphs;
+  // ---- the three-launch iteration (LaunchPlan::three) ----
+  int* h_pause = nullptr;      // pinned, device-visible: [0] bumped by every solve workgroup that pauses its window (system-scope atomic)
+  int* d_pause = nullptr;      // the device's address of h_pause
+  int pause_seen = 0;          // h_pause[0] as of the last entry that looked at it
+  int pause_begin = 0;         // ... as of okvis_ba_begin
+  bool three_unseen = false;   // a three-launch call of this begin ... finish has not been waited for yet (it may hold pauses)
+  bool start_four = false;     // the previous begin ... finish paused or re-preintegrated: this one runs on the four-launch route
+  int* d_redo_mark = nullptr;  // [window] sum of its terms' redo_count behind okvis_ba_begin's evaluation (grow-only)
+  size_t redo_mark_windows = 0;
   float last_iterate_ms = 0.f;
   int last_hip_error = 0;
   unsigned char* marg_scratch = nullptr;  // grow-only device scratch of okvis_ba_marginalize

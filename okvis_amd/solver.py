@@ -43,7 +43,7 @@ def check_window(window: Window, options: OptionsC | None = None) -> dict:
 
 INDEX_LISTS = ("groups", "lm_obs_begin", "lm_pair_begin", "pair_lm", "pair_block", "pair_off", "pair_role", "lm_piece_begin",
                "pair_piece", "pair_list_begin", "pair_list", "tasks", "task_list", "chunks", "chunk_diag_begin", "chunk_diag_out",
-               "chunk_desc", "piece_path", "ldl_comp", "chain", "chunk_recs", "group_recs")   # OKVIS_BA_LIST_* in this order
+               "chunk_desc", "piece_path", "ldl_comp", "chain", "chunk_recs", "group_recs", "plan")   # OKVIS_BA_LIST_* in this order
 
 
 def index_lists(window: Window, options: OptionsC | None = None, n_windows: int = 1) -> dict:
@@ -509,9 +509,15 @@ class WindowBatch:
         _lib.check(self._L.okvis_ba_helper_timeouts(self._h, C.byref(n)))
         return n.value
 
+    def pause_count(self) -> int:
+        """okvis_ba_pause_count: windows the three-launch iteration's solve kernel paused since begin() (0 in a steady run)"""
+        n = C.c_int64()
+        _lib.check(self._L.okvis_ba_pause_count(self._h, C.byref(n)))
+        return n.value
+
     ROUTE = ("windows", "fused", "decision_free_schur", "piece_path", "split_small", "sub_batches", "sub_batch_max_windows",
              "schur_kernel", "solve_dbuf", "solve_tiled", "solve_helpers", "graph", "max_chunks", "slots", "solve_mode", "small_rides",
-             "lin_records")
+             "lin_records", "three_launch")
 
     def launch_route(self) -> dict:
         """okvis_ba_launch_route: which launches this batch takes under the current options (read-only)"""
