@@ -154,12 +154,7 @@ int okvis_ba_destroy(okvis_ba_solver* s) {
   if (s->h_pause) (void)hipHostFree(s->h_pause);
   if (s->d_redo_mark) (void)hipFree(s->d_redo_mark);
   if (s->marg_scratch) (void)hipFree(s->marg_scratch);
-  for (auto ev : s->ev_cov)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : s->ev_lmcov)
-    if (ev) (void)hipEventDestroy(ev);
-  for (auto ev : s->ev_pred)
-    if (ev) (void)hipEventDestroy(ev);
+  for (CovEvents* ev : {&s->ev_cov, &s->ev_lmcov, &s->ev_pred}) cov_events_destroy(*ev);
   if (s->ev0) (void)hipEventDestroy(s->ev0);
   if (s->ev1) (void)hipEventDestroy(s->ev1);
   if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);

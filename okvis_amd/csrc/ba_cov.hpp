@@ -11,7 +11,9 @@
 //      of the result itself;
 //   4. Sigma_K = diag(d_K) X_K diag(d_K): the entry of the lower triangle (in ascending row order) is computed, the upper mirrored.
 // The body is the device function cov_solve, shared by cov_kernel (a list of rows: okvis_ba_state_covariance) and cov_pose_kernel
-// (all pose-type rows, written to HBM: stage one of okvis_ba_landmark_covariance, ba_lmcov.hpp).
+// (all pose-type rows, written to HBM: stage one of okvis_ba_landmark_covariance and okvis_ba_predicted_measurement, ba_lmcov.hpp,
+// ba_predcov.hpp).  The file also holds cov_dot2_step, the error-free accumulation step of every refinement in the three entries,
+// and cov_keep_kernel, which keeps and restores what the assembly launches overwrite.
 // Route chosen among the two of the issue: unit vectors, not "K last and the trailing Schur complement".  The trailing block needs
 // no second array but cannot be refined (its error is in the complement, not in the small inverse); the unit vectors need D x 15
 // doubles next to the packed triangle (119 + 20 KB at D = 174) and give every column the same arithmetic whatever else is
@@ -39,6 +41,20 @@ struct CovArgs {
 
 __host__ __device__ constexpr size_t cov_lds_bytes(int D) { return 8 * ((size_t)D * (D + 1) / 2 + (size_t)D * COV_KC + D); }
 __host__ __device__ constexpr size_t cov_out_doubles(int k) { return (size_t)k * k + 2; }
+
+// One step of a dot product in twice the working precision (Ogita / Rump / Oishi's Dot2): hi + lo += a b, the product and the sum
+// as error-free transformations.  Every refinement of the covariance entries forms its residual with it: cov_solve below, the
+// 3 x 3 steps of ba_lmcov.hpp and ba_predcov.hpp.
+__device__ __forceinline__ void cov_dot2_step(double a, double b, double& hi, double& lo) {
+#pragma clang fp contract(off)   // (the sums below are error-free only as written)
+  const double p = a * b;
+  const double pe = __builtin_fma(a, b, -p);
+  const double sum = hi + p;
+  const double bb = sum - hi;
+  const double se = (hi - (sum - bb)) + (p - bb);
+  hi = sum;
+  lo += pe + se;
+}
 
 // Which reduced rows are selected: a list (cov_kernel) or the leading k (cov_pose_kernel).  Ascending either way.
 struct CovRowList {
@@ -195,7 +211,6 @@ __device__ __forceinline__ void cov_solve(const double* S, double* out, double* 
         lo[c] = 0.0;
       }
       if (row) {
-#pragma clang fp contract(off)   // (the sums below are error-free only as written)
         const double di = sd[tid];
         double s_next = S[tid];
         for (int j = 0; j < D; ++j) {
@@ -204,15 +219,7 @@ __device__ __forceinline__ void cov_solve(const double* S, double* out, double* 
           const double s = -((s_raw * di) * sd[j]);   // (the symmetric entry: consecutive work-items, consecutive addresses)
           const double* w = Wm + j * COV_KC;
 #pragma unroll
-          for (int c = 0; c < COV_KC; ++c) {
-            const double p = s * w[c];
-            const double pe = __builtin_fma(s, w[c], -p);
-            const double sum = hi[c] + p;
-            const double bb = sum - hi[c];
-            const double se = (hi[c] - (sum - bb)) + (p - bb);
-            hi[c] = sum;
-            lo[c] += pe + se;
-          }
+          for (int c = 0; c < COV_KC; ++c) cov_dot2_step(s, w[c], hi[c], lo[c]);
         }
       }
       __syncthreads();

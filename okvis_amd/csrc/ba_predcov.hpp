@@ -20,6 +20,8 @@
 // |R| reaches 84 with per-frame extrinsics (12 landmark blocks + 2 query blocks): every phase loops over the rows.
 // fp64 throughout, explicit fused multiply-adds, every sum in an order that depends on the query alone: its numbers have the same
 // bits alone, in any list and in any range of windows.  The matrix core is not used: the products have two columns.
+// This file holds what is the query's own: the projection (predcov_project), N (predcov_solve3), phase 1 and the flags.  The
+// landmark head, phases 2 and 3, the wave-level sync and the tap kernel are the wave core in ba_lmcov.hpp, with NC = 2.
 #pragma once
 #include "ba_lmcov.hpp"
 #include "ba_math.hpp"
@@ -33,16 +35,12 @@ constexpr int PREDCOV_MAX_ROWS = MAX_D_LDS;   // R is a set of rows of distinct 
 constexpr int PREDCOV_JAC = 30;               // J_l [2][3] | J_p [2][6] | J_e [2][6], row-major
 constexpr uint8_t PREDCOV_NO_COV = 1, PREDCOV_NO_PROJECTION = 2;
 
-struct PredcovArgs {
-  const double* P;     // [Dp][Dp] pose-type part of S0^-1 (NaN throughout when S0 could not be inverted)
+struct PredcovArgs : CovWaveArgs {
   const int4* q;       // [n] lm, pose, ext, cam
   double* uv;          // [n][2]
   double* cov;         // [n][4]
   uint8_t* flags;      // [n]
   double* jac;         // null or [n][PREDCOV_JAC]: the Jacobians the wave formed
-  double* tapV;        // null or [n_lm][6]: the referee's copy of V ...
-  double* tapW;        // null or [n_pair][18]: ... and of W, from the buffer the kernel reads
-  int n;
 };
 
 // The predicted pixel and its minimal Jacobians: the algebra of reproj_linearize (ba_math.hpp; ReprojectionError.hpp:87-242) for the
@@ -122,24 +120,12 @@ __device__ __forceinline__ void predcov_solve3(const double* v, const double* x,
     double n0[3], res[3];
 #pragma unroll
     for (int i = 0; i < 3; ++i) n0[i] = __builtin_fma(X[i][2], Jl[3 * j + 2], __builtin_fma(X[i][1], Jl[3 * j + 1], X[i][0] * Jl[3 * j]));
-    {
-#pragma clang fp contract(off)   // (the sums below are error-free only as written)
 #pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        double hi = Jl[3 * j + i], lo = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      double hi = Jl[3 * j + i], lo = 0.0;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          const double a = -V[i][k], b = n0[k];
-          const double p = a * b;
-          const double pe = __builtin_fma(a, b, -p);
-          const double sum = hi + p;
-          const double bb = sum - hi;
-          const double se = (hi - (sum - bb)) + (p - bb);
-          hi = sum;
-          lo += pe + se;
-        }
-        res[i] = hi + lo;
-      }
+      for (int k = 0; k < 3; ++k) cov_dot2_step(-V[i][k], n0[k], hi, lo);
+      res[i] = hi + lo;
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) N[3 * j + i] = n0[i] + __builtin_fma(X[i][2], res[2], __builtin_fma(X[i][1], res[1], X[i][0] * res[0]));
@@ -168,15 +154,9 @@ __global__ __launch_bounds__(PREDCOV_THREADS) void predcov_kernel(const WinPtrs*
   int* const rows = s_row[wave];
   const double nan = __builtin_nan(""), inf = __builtin_inf();
 
-  // V_l^-1 (every lane the same numbers) and whether its terms show a positive definite V_l: Sylvester's three minors
   double v[6], vi[6];
-  {
-    const BA_G double* Vl = W.V[acc] + 6 * (size_t)l;
-#pragma unroll
-    for (int e = 0; e < 6; ++e) v[e] = Vl[e];
-  }
-  inv3sym(v, vi);
-  lmcov_refine3(v, vi);
+  cov_wave_landmark(W.V[acc] + 6 * (size_t)l, v, vi);
+  // (cov_wave_positive_definite(v), written out: ba_lmcov.hpp says why)
   const double m2 = v[0] * v[3] - v[1] * v[1];
   const double det = v[0] * (v[3] * v[5] - v[4] * v[4]) + v[1] * (v[2] * v[4] - v[1] * v[5]) + v[2] * (v[1] * v[4] - v[2] * v[3]);
   bool ok = Rl > 0 && Rl <= PREDCOV_MAX_ROWS && v[0] > 0.0 && m2 > 0.0 && det > 0.0 && det < inf;
@@ -212,7 +192,7 @@ __global__ __launch_bounds__(PREDCOV_THREADS) void predcov_kernel(const WinPtrs*
     }
     J[PREDCOV_JAC] = lin.uv[0], J[PREDCOV_JAC + 1] = lin.uv[1];
   }
-  lmcov_wave_sync();
+  cov_wave_sync();
   if (lane < 2) Q.uv[(size_t)item * 2 + lane] = projects ? J[PREDCOV_JAC + lane] : nan;
   if (Q.jac && lane < PREDCOV_JAC) Q.jac[(size_t)item * PREDCOV_JAC + lane] = projects ? J[lane] : nan;
   double N[6];   // V_l^-1 J_l^T: J_l G^T = (W N)^T and J_l V_l^-1 J_l^T = J_l N
@@ -268,38 +248,13 @@ __global__ __launch_bounds__(PREDCOV_THREADS) void predcov_kernel(const WinPtrs*
     }
   }
   if (ok) {
-    lmcov_wave_sync();
-    // ---- 2. T = P[R, R] A^T
-    const double* P = Q.P;
-    for (int r = lane; r < R; r += 64) {
-      const double* Pr = P + rows[r];
-      double t0 = 0.0, t1 = 0.0;
-      for (int c = 0; c < R; c += 6) {   // (a block's six rows are consecutive: six loads in flight, added in order)
-        const size_t base = (size_t)rows[c] * Dp;
-        double pc[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) pc[k] = Pr[base + (size_t)k * Dp];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-          const double* a = A + 2 * (c + k);
-          t0 = __builtin_fma(pc[k], a[0], t0);
-          t1 = __builtin_fma(pc[k], a[1], t1);
-        }
-      }
-      T[2 * r + 0] = t0, T[2 * r + 1] = t1;
-    }
-    lmcov_wave_sync();
+    cov_wave_sync();
+    cov_wave_gather<2>(Q.P, Dp, rows, R, A, T, lane);   // ---- 2. T = P[R, R] A^T
+    cov_wave_sync();
   }
-  // ---- 3. the lower triangle: entry e = (i, j) in the order 00 10 11; lanes 16 e .. 16 e + 15
-  const int e = lane >> 4, seg = lane & 15;
-  const int ei = e == 0 ? 0 : 1, ej = e == 2 ? 1 : 0;
-  double part = 0.0;
-  if (ok && e < 3)
-    for (int r = seg; r < R; r += 16) part = __builtin_fma(A[2 * r + ei], T[2 * r + ej], part);
-  part += __shfl_xor(part, 1);
-  part += __shfl_xor(part, 2);
-  part += __shfl_xor(part, 4);
-  part += __shfl_xor(part, 8);
+  // ---- 3. the lower triangle of A T, entry e on lanes 16 e .. 16 e + 15 in the order 00 10 11
+  const int e = lane >> 4;
+  const double part = cov_wave_triangle<2>(A, T, R, lane, ok);
   // J_l V_l^-1 J_l^T = J_l N
   const double l00 = __builtin_fma(Jl[2], N[2], __builtin_fma(Jl[1], N[1], Jl[0] * N[0]));
   const double l10 = __builtin_fma(Jl[5], N[2], __builtin_fma(Jl[4], N[1], Jl[3] * N[0]));
@@ -310,17 +265,6 @@ __global__ __launch_bounds__(PREDCOV_THREADS) void predcov_kernel(const WinPtrs*
   const double o = __shfl(val, 16 * (lane == 0 ? 0 : (lane == 3 ? 2 : 1)));
   if (lane < 4) Q.cov[(size_t)item * 4 + lane] = ok ? o : nan;
   if (lane == 0) Q.flags[item] = (uint8_t)((no_cov ? PREDCOV_NO_COV : 0) | (projects ? 0 : PREDCOV_NO_PROJECTION));
-}
-
-// The referee's taps of V and W: the very buffers predcov_kernel reads.  One workgroup per window.
-__global__ void predcov_tap_kernel(const WinPtrs* __restrict__ wins, const PredcovArgs* __restrict__ args) {
-  const PredcovArgs& Q = args[blockIdx.x];
-  const WinPtrs& W = wins[blockIdx.x];
-  const int acc = W.ctrl->acc & 1;
-  if (Q.tapV)
-    for (int i = threadIdx.x; i < 6 * W.n_lm; i += blockDim.x) Q.tapV[i] = W.V[acc][i];
-  if (Q.tapW)
-    for (int i = threadIdx.x; i < 18 * W.n_pair; i += blockDim.x) Q.tapW[i] = W.W[acc][i];
 }
 
 }  // namespace ba

@@ -1,22 +1,20 @@
-// Part of ba_capi.hip, inside its extern "C" block, behind capi_covariance.inc (whose assembly — scratch layout, keep / restore, the
-// private option record, cov_assemble_and_run — it shares).  okvis_ba_landmark_covariance (DESIGN.md "Landmark covariance"): the
-// assembly of okvis_ba_state_covariance for a range of windows, then cov_pose_kernel (ba_cov.hpp; P = the pose-type part of S0^-1,
-// one workgroup per window) and lmcov_kernel (ba_lmcov.hpp; one wave per selected landmark, all windows in one launch).  One copy
-// up, one copy back, one synchronisation.  V and W are read where the assembly left them: okvis_ba_begin linearises into the trial
+// Part of ba_capi.hip, inside its extern "C" block, behind capi_covariance.inc, whose plan of a covariance call (CovPlan: guard,
+// scratch layout, host records, stage runner, download and scatter of the shared arrays) it uses.  okvis_ba_landmark_covariance
+// (DESIGN.md "Landmark covariance") keeps here what is its own: its check, its job, its argument records with the selections, the
+// launch of lmcov_kernel (ba_lmcov.hpp; one wave per selected landmark, all windows in one launch) behind cov_pose_kernel, and the
+// scatter of cov and flags.  V and W are read where the assembly left them: okvis_ba_begin linearises into the trial
 // buffer, the Schur launch and the solve launch (final_only = 2) take the same decision on it and reduce / accept it, and the
 // control record the solve launch writes names that buffer — on the piece path and the staged path, with the fused reduction or a
 // Schur launch of its own, with helper workgroups or without: all of them read W.V[acc] / W.W[acc] of the buffer the decision names
 // and none writes to them (damping is added to a copy).  The kernels run in front of the restore and read the record's `acc`.
 namespace {
 
-struct LmcovJob {
-  int D = 0, Dp = 0, n = 0, n_lm = 0, n_pair = 0;
+struct LmcovJob : CovWin {
   const int32_t* sel = nullptr;   // the caller's list, or null = window order
-  ExportAt ex;
-  size_t o_sel = 0, o_P = 0, o_tail = 0, o_cov = 0, o_flags = 0, o_V = 0, o_W = 0;
+  size_t o_sel = 0, o_cov = 0, o_flags = 0;
 };
 
-int lmcov_check(const okvis_ba_solver* s, int w, const okvis_ba_lmcov_spec* spec, const okvis_ba_lmcov_result* res, LmcovJob& J) {
+int lmcov_check(const okvis_ba_solver* s, int w, const okvis_ba_lmcov_spec* spec, okvis_ba_lmcov_result* res, LmcovJob& J) {
   const HostWin& H = s->wins[w];
   if (!res->cov || !res->flags) return OKVIS_BA_ERR_ARG;
   int n = H.n_lm;
@@ -27,9 +25,9 @@ int lmcov_check(const okvis_ba_solver* s, int w, const okvis_ba_lmcov_spec* spec
       if (spec->lm_idx[i] < 0 || spec->lm_idx[i] >= H.n_lm) return OKVIS_BA_ERR_ARG;
   }
   if (res->capacity < n) return OKVIS_BA_ERR_ARG;
-  if (H.D > OKVIS_BA_COV_MAX_WINDOW_DIM || H.ptrs.Sg != nullptr) return OKVIS_BA_ERR_UNSUPPORTED;
   J = LmcovJob{};
-  J.D = H.D, J.Dp = H.Dp, J.n = n, J.n_lm = H.n_lm, J.n_pair = H.n_pair;
+  if (int rc = cov_win_init(H, CovTaps{res->S0, res->Spp, res->V, res->W, &res->min_pivot, &res->info}, J)) return rc;
+  J.n = n;
   J.sel = spec->lm_idx;
   return OKVIS_BA_OK;
 }
@@ -37,134 +35,46 @@ int lmcov_check(const okvis_ba_solver* s, int w, const okvis_ba_lmcov_spec* spec
 }  // namespace
 
 int okvis_ba_landmark_covariance(okvis_ba_solver* s, int w0, int n, const okvis_ba_lmcov_spec* specs, okvis_ba_lmcov_result* results) {
-  if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
-  if (!s->uploaded || s->begun || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
-  if (n <= 0 || w0 < 0 || (int64_t)w0 + n > (int64_t)s->wins.size()) return OKVIS_BA_ERR_ARG;
-  // every window's arguments before anything is enqueued
-  std::vector<LmcovJob> jobs((size_t)n);
-  for (int i = 0; i < n; ++i)
-    if (int rc = lmcov_check(s, w0 + i, &specs[i], &results[i], jobs[i])) return rc;
-  HIP_TRY(hipSetDevice(s->device));
-  if (int rc = cov_refresh_acc(s)) return rc;
-
-  // ---- one scratch allocation: what the host writes (with the selections) | what is kept | workspaces | every window's outputs ----
-  Arena A;
-  CovAssembly ca;
-  ca.o_wins = A.alloc(sizeof(WinPtrs) * (size_t)n);
-  const size_t o_pargs = A.alloc(sizeof(CovPoseArgs) * (size_t)n), o_largs = A.alloc(sizeof(LmcovArgs) * (size_t)n);
-  ca.o_opt = A.alloc(sizeof(OptD));
-  for (int i = 0; i < n; ++i)
-    if (jobs[i].sel) jobs[i].o_sel = A.alloc(sizeof(int32_t) * (size_t)std::max(1, jobs[i].n));
-  const size_t host_part = A.size;   // ONE copy up
-  cov_alloc_keep(s, A, ca);
-  int Dmax = 1, nmax = 0;
-  bool tap_vw = false;
-  for (int i = 0; i < n; ++i) {
-    LmcovJob& J = jobs[i];
-    const okvis_ba_lmcov_result& R = results[i];
-    J.ex.o_rhs = A.alloc(8 * (size_t)J.D), J.ex.o_d2 = A.alloc(8 * (size_t)J.D);
-    if (!R.S0) J.ex.o_S = A.alloc(8 * (size_t)J.D * J.D);
-    if (!R.Spp) J.o_P = A.alloc(8 * (size_t)std::max(1, J.Dp * J.Dp));
-    Dmax = std::max(Dmax, J.D), nmax = std::max(nmax, J.n);
-    tap_vw = tap_vw || R.V || R.W;
-  }
-  size_t out_base = 0;
-  for (int i = 0; i < n; ++i) {   // min_pivot | info | cov | flags | the taps asked for: contiguous over the range, ONE copy back
-    LmcovJob& J = jobs[i];
-    const okvis_ba_lmcov_result& R = results[i];
-    J.o_tail = A.alloc(16);
-    if (i == 0) out_base = J.o_tail;
-    J.o_cov = A.alloc(72 * (size_t)std::max(1, J.n));
-    J.o_flags = A.alloc((size_t)std::max(1, J.n));
-    if (R.S0) J.ex.o_S = A.alloc(8 * (size_t)J.D * J.D);
-    if (R.Spp) J.o_P = A.alloc(8 * (size_t)std::max(1, J.Dp * J.Dp));
-    if (R.V) J.o_V = A.alloc(48 * (size_t)std::max(1, J.n_lm));
-    if (R.W) J.o_W = A.alloc(144 * (size_t)std::max(1, J.n_pair));
-  }
-  const size_t out_total = A.size - out_base;
-  s->stage_marg.resize(host_part);
-  unsigned char* const hb = s->stage_marg.data();
-  if (int rc = marg_reserve_scratch(s, A.size)) return rc;
-  unsigned char* d = s->marg_scratch;
-  {
-    std::vector<ExportAt> ex((size_t)n);
-    for (int i = 0; i < n; ++i) ex[i] = jobs[i].ex;
-    cov_fill_host(s, w0, n, hb, d, ca, ex.data());
-  }
+  std::vector<LmcovJob> jobs;
+  if (int rc = cov_enter(s, w0, n, specs, results, jobs, lmcov_check)) return rc;
+  CovPlan P{s, w0, n, true};
+  P.head(sizeof(LmcovArgs));
+  for (LmcovJob& J : jobs)   // the selections are host-written
+    if (J.sel) J.o_sel = P.A.alloc(sizeof(int32_t) * (size_t)std::max(1, J.n));
+  if (int rc = P.layout(jobs, [&](LmcovJob& J) {   // min_pivot | info | cov | flags | the taps asked for
+        J.o_cov = P.A.alloc(72 * (size_t)std::max(1, J.n));
+        J.o_flags = P.A.alloc((size_t)std::max(1, J.n));
+        P.alloc_taps(J);
+      }))
+    return rc;
   for (int i = 0; i < n; ++i) {
     const LmcovJob& J = jobs[i];
-    const okvis_ba_lmcov_result& R = results[i];
-    CovPoseArgs p;
-    std::memset(&p, 0, sizeof(p));
-    p.S = reinterpret_cast<const double*>(d + J.ex.o_S);
-    p.P = reinterpret_cast<double*>(d + J.o_P);
-    p.tail = reinterpret_cast<double*>(d + J.o_tail);
-    p.D = J.D, p.Dp = J.Dp;
-    std::memcpy(&hb[o_pargs + sizeof(CovPoseArgs) * (size_t)i], &p, sizeof(p));
     LmcovArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.P = p.P;
-    a.sel = J.sel ? reinterpret_cast<const int*>(d + J.o_sel) : nullptr;
-    a.cov = reinterpret_cast<double*>(d + J.o_cov);
-    a.flags = reinterpret_cast<uint8_t*>(d + J.o_flags);
-    a.tapV = R.V ? reinterpret_cast<double*>(d + J.o_V) : nullptr;
-    a.tapW = R.W ? reinterpret_cast<double*>(d + J.o_W) : nullptr;
-    a.n = J.n;
-    std::memcpy(&hb[o_largs + sizeof(LmcovArgs) * (size_t)i], &a, sizeof(a));
-    if (J.sel && J.n > 0) std::memcpy(&hb[J.o_sel], J.sel, sizeof(int32_t) * (size_t)J.n);
+    static_cast<CovWaveArgs&>(a) = P.wave_args(J);
+    a.sel = J.sel ? reinterpret_cast<const int*>(P.d + J.o_sel) : nullptr;
+    a.cov = reinterpret_cast<double*>(P.d + J.o_cov);
+    a.flags = reinterpret_cast<uint8_t*>(P.d + J.o_flags);
+    std::memcpy(P.item_args(i), &a, sizeof(a));
+    if (J.sel && J.n > 0) std::memcpy(&P.hb[J.o_sel], J.sel, sizeof(int32_t) * (size_t)J.n);
   }
-  for (auto& ev : s->ev_lmcov)
-    if (!ev) HIP_TRY(hipEventCreate(&ev));
-  int rc = cov_assemble_and_run(s, w0, n, d, hb, host_part, ca, s->ev_lmcov[0], s->ev_lmcov[1], [&](const WinPtrs* d_wins) {
-    const LmcovArgs* largs = reinterpret_cast<const LmcovArgs*>(d + o_largs);
-    hipLaunchKernelGGL(cov_pose_kernel, dim3((unsigned)n), dim3(COV_THREADS), cov_lds_bytes(Dmax), s->stream,
-                       reinterpret_cast<const CovPoseArgs*>(d + o_pargs));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(s->ev_lmcov[2], s->stream);
-    if (e == hipSuccess && nmax > 0) {
-      hipLaunchKernelGGL(lmcov_kernel, dim3((unsigned)((nmax + LMCOV_WAVES - 1) / LMCOV_WAVES), (unsigned)n), dim3(LMCOV_THREADS), 0, s->stream, d_wins, largs);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess && tap_vw) {
-      hipLaunchKernelGGL(lmcov_tap_kernel, dim3((unsigned)n), dim3(256), 0, s->stream, d_wins, largs);
-      e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipEventRecord(s->ev_lmcov[3], s->stream);
-    return e;
-  });
-  if (rc != OKVIS_BA_OK) return rc;
-  s->stage_dl.resize(out_total);
-  HIP_TRY(hipMemcpyAsync(s->stage_dl.data(), d + out_base, out_total, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  for (int i = 0; i < n; ++i) {
-    const LmcovJob& J = jobs[i];
+  if (int rc = P.run(s->ev_lmcov, [&](const WinPtrs* d_wins) {
+        hipLaunchKernelGGL(lmcov_kernel, dim3((unsigned)((P.nmax + LMCOV_WAVES - 1) / LMCOV_WAVES), (unsigned)n), dim3(LMCOV_THREADS), 0, s->stream, d_wins,
+                           reinterpret_cast<const LmcovArgs*>(P.d + P.o_iargs));
+      }))
+    return rc;
+  return P.finish(jobs, [&](const LmcovJob& J, int i) {
     okvis_ba_lmcov_result& R = results[i];
-    const unsigned char* o = s->stage_dl.data();
-    auto at = [&](size_t off) { return o + (off - out_base); };
-    std::memcpy(&R.min_pivot, at(J.o_tail), 8);
-    std::memcpy(&R.info, at(J.o_tail) + 8, sizeof(int32_t));
     R.n = J.n;
-    std::memcpy(R.cov, at(J.o_cov), 72 * (size_t)J.n);
-    std::memcpy(R.flags, at(J.o_flags), (size_t)J.n);
-    if (R.info != 0) {   // (a window whose S0 could not be inverted: P is NaN, so every row already is; every flag says so)
-      std::memset(R.flags, 1, (size_t)J.n);
-      rc = OKVIS_BA_ERR_NUMERIC;
-    }
-    if (R.S0) std::memcpy(R.S0, at(J.ex.o_S), 8 * (size_t)J.D * J.D);
-    if (R.Spp) std::memcpy(R.Spp, at(J.o_P), 8 * (size_t)J.Dp * J.Dp);
-    if (R.V) std::memcpy(R.V, at(J.o_V), 48 * (size_t)J.n_lm);
-    if (R.W) std::memcpy(R.W, at(J.o_W), 144 * (size_t)J.n_pair);
-  }
-  return rc;
+    std::memcpy(R.cov, P.at(J.o_cov), 72 * (size_t)J.n);
+    std::memcpy(R.flags, P.at(J.o_flags), (size_t)J.n);
+    // (a window whose S0 could not be inverted: P is NaN, so every row already is; every flag says so)
+    if (R.info != 0) std::memset(R.flags, 1, (size_t)J.n);
+  });
 }
 
 int okvis_ba_last_landmark_covariance_ms(okvis_ba_solver* s, float* assembly_ms, float* inverse_ms, float* landmark_ms) {
-  if (!s || !assembly_ms || !inverse_ms || !landmark_ms) return OKVIS_BA_ERR_ARG;
-  if (!s->ev_lmcov[3]) return OKVIS_BA_ERR_STATE;
-  HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(hipEventSynchronize(s->ev_lmcov[3]));
-  HIP_TRY(hipEventElapsedTime(assembly_ms, s->ev_lmcov[0], s->ev_lmcov[1]));
-  HIP_TRY(hipEventElapsedTime(inverse_ms, s->ev_lmcov[1], s->ev_lmcov[2]));
-  HIP_TRY(hipEventElapsedTime(landmark_ms, s->ev_lmcov[2], s->ev_lmcov[3]));
-  return OKVIS_BA_OK;
+  if (!s) return OKVIS_BA_ERR_ARG;
+  float* const ms[] = {assembly_ms, inverse_ms, landmark_ms};
+  return cov_last_ms(s, s->ev_lmcov, 3, ms);
 }

@@ -132,6 +132,10 @@ struct LaunchPlan : PlanFixed {
 
 }  // namespace
 
+// The stage events of a covariance entry's last call: in front of the assembly | behind it | behind cov_kernel (state covariance,
+// which uses three) or cov_pose_kernel | behind the item kernel and the taps (the two-stage entries).
+struct CovEvents { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; };
+
 struct okvis_ba_solver {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -206,13 +210,21 @@ struct okvis_ba_solver {
   float last_iterate_ms = 0.f;
   int last_hip_error = 0;
   unsigned char* marg_scratch = nullptr;  // grow-only device scratch of okvis_ba_marginalize
-  hipEvent_t ev_cov[3] = {nullptr, nullptr, nullptr};   // okvis_ba_state_covariance: in front of the assembly | of cov_kernel | behind it
-  hipEvent_t ev_lmcov[4] = {nullptr, nullptr, nullptr, nullptr};   // okvis_ba_landmark_covariance: in front of the assembly | of cov_pose_kernel | of lmcov_kernel | behind it
-  hipEvent_t ev_pred[4] = {nullptr, nullptr, nullptr, nullptr};    // okvis_ba_predicted_measurement: in front of the assembly | of cov_pose_kernel | of predcov_kernel | behind it
+  CovEvents ev_cov, ev_lmcov, ev_pred;   // okvis_ba_state_covariance, okvis_ba_landmark_covariance, okvis_ba_predicted_measurement
   size_t marg_scratch_bytes = 0;
 };
 
 namespace {
+
+int cov_events_create(okvis_ba_solver* s, CovEvents& ev) {   // (lazily, by the entry's first call)
+  for (auto& e : ev.e)
+    if (!e) HIP_TRY(hipEventCreate(&e));
+  return OKVIS_BA_OK;
+}
+void cov_events_destroy(CovEvents& ev) {
+  for (auto& e : ev.e)
+    if (e) (void)hipEventDestroy(e);
+}
 
 size_t solve_smem_chain(int chain_doubles, int Dpad);
 

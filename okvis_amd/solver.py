@@ -245,6 +245,37 @@ class WindowBatch:
             raise ValueError(f"window {w} has no IMU term: name the blocks")
         return [(BLOCK_POSE, int(np.asarray(W.imu_pose1).reshape(-1)[-1])), (BLOCK_SPEEDBIAS, int(np.asarray(W.imu_sb1).reshape(-1)[-1]))]
 
+    # ---- what state_covariance, landmark_covariance and predicted_measurement share ----
+    def _window_range(self, w0, n):
+        """(w0, n) of a call on windows w0 .. w0 + n - 1 (n = None: to the end of the batch)"""
+        w0 = int(w0)
+        n = len(self.windows) - w0 if n is None else int(n)
+        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
+            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        return w0, n
+
+    def _tap_dims(self, w0, n) -> list:
+        """(D, Dp, n_lm, n_pair) of windows w0 .. w0 + n - 1: the sizes of the referee's taps S0, Spp, V, W"""
+        dims = []
+        for w in range(w0, w0 + n):
+            W = self.windows[w]
+            np_ = C.c_int32()
+            _lib.check(self._L.okvis_ba_pair_count(self._h, w, C.byref(np_)))
+            dims.append((self.reduced_dim(w), 6 * int((np.asarray(W.pose_fixed).reshape(-1) == 0).sum()), int(W.n_lm), np_.value))
+        return dims
+
+    def _covariance_results(self, st, what, n, unpack) -> list:
+        """The end of a covariance call that returned status st: [unpack(i) for the n windows], raised inside BackendError (as its
+        ``results``) when st is OKVIS_BA_ERR_NUMERIC; any other failure has no results."""
+        if st not in (0, -5):
+            _lib.check(st, what)
+        res = [unpack(i) for i in range(n)]
+        if st != 0:
+            err = _lib.BackendError(st, what)
+            err.results = res
+            raise err
+        return res
+
     def state_covariance(self, blocks=None, w0: int = 0, n: int | None = None, want_S0: bool = False) -> list:
         """okvis_ba_state_covariance on windows w0 .. w0 + n - 1 (default: to the end of the batch): the marginal covariance of the
         listed free blocks at the state the solver holds, rows and columns of the inverse of the undamped reduced system, in the
@@ -256,10 +287,7 @@ class WindowBatch:
         (the matrix the kernel inverted).  A window with info = 1 has cov filled with NaN; the call then raises BackendError
         (OKVIS_BA_ERR_NUMERIC) whose ``results`` attribute holds the list."""
         from .window import cov_marshal_batch
-        w0 = int(w0)
-        n = len(self.windows) - w0 if n is None else int(n)
-        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
-            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        w0, n = self._window_range(w0, n)
         if blocks is None:
             sels = [self.newest_state_blocks(w0 + i) for i in range(n)]
         elif len(blocks) > 0 and isinstance(blocks[0], (list, tuple)) and len(blocks[0]) > 0 and isinstance(blocks[0][0], (list, tuple)):
@@ -272,20 +300,14 @@ class WindowBatch:
         specs, results, outs, keep = cov_marshal_batch(sels, dims, want_S0)
         st = self._L.okvis_ba_state_covariance(self._h, w0, n, specs, results)
         del keep
-        if st not in (0, -5):
-            _lib.check(st, "state_covariance")
-        res = []
-        for i in range(n):
+
+        def unpack(i):
             k = int(results[i].dim)
             r = dict(cov=outs[i]["cov"][:k * k].reshape(k, k).copy(), dim=k, info=int(results[i].info), min_pivot=float(results[i].min_pivot))
             if want_S0:
                 r["S0"] = outs[i]["S0"].reshape(dims[i], dims[i]).copy()
-            res.append(r)
-        if st != 0:
-            err = _lib.BackendError(st, "state_covariance")
-            err.results = res
-            raise err
-        return res
+            return r
+        return self._covariance_results(st, "state_covariance", n, unpack)
 
     def last_covariance_ms(self) -> dict:
         """okvis_ba_last_covariance_ms: HIP-event times of the last state_covariance call's assembly launches and of cov_kernel"""
@@ -306,10 +328,7 @@ class WindowBatch:
         info = 1 has every row NaN and every flag set; the call then raises BackendError (OKVIS_BA_ERR_NUMERIC) whose ``results``
         attribute holds the list."""
         from .window import lmcov_marshal_batch
-        w0 = int(w0)
-        n = len(self.windows) - w0 if n is None else int(n)
-        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
-            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        w0, n = self._window_range(w0, n)
         if landmarks is None:
             sels = [None] * n
         elif len(landmarks) > 0 and (landmarks[0] is None or isinstance(landmarks[0], (list, tuple, np.ndarray))):
@@ -319,32 +338,19 @@ class WindowBatch:
         else:
             sels = [landmarks] * n
         counts = [int(self.windows[w0 + i].n_lm) for i in range(n)]
-        taps = None
-        if want_taps:
-            taps = []
-            for i in range(n):
-                W = self.windows[w0 + i]
-                np_ = C.c_int32()
-                _lib.check(self._L.okvis_ba_pair_count(self._h, w0 + i, C.byref(np_)))
-                taps.append((self.reduced_dim(w0 + i), 6 * int((np.asarray(W.pose_fixed).reshape(-1) == 0).sum()), counts[i], np_.value))
+        taps = self._tap_dims(w0, n) if want_taps else None
         specs, results, outs, keep = lmcov_marshal_batch(sels, counts, taps)
         st = self._L.okvis_ba_landmark_covariance(self._h, w0, n, specs, results)
         del keep
-        if st not in (0, -5):
-            _lib.check(st, "landmark_covariance")
-        res = []
-        for i in range(n):
+
+        def unpack(i):
             m = int(results[i].n)
             r = dict(cov=outs[i]["cov"][:m].reshape(m, 3, 3).copy(), flags=outs[i]["flags"][:m].astype(bool), info=int(results[i].info),
                      min_pivot=float(results[i].min_pivot))
             if want_taps:
                 r.update({k: outs[i][k].copy() for k in ("S0", "Spp", "V", "W")})
-            res.append(r)
-        if st != 0:
-            err = _lib.BackendError(st, "landmark_covariance")
-            err.results = res
-            raise err
-        return res
+            return r
+        return self._covariance_results(st, "landmark_covariance", n, unpack)
 
     def last_landmark_covariance_ms(self) -> dict:
         """okvis_ba_last_landmark_covariance_ms: HIP-event times of the last landmark_covariance call's assembly launches, of the
@@ -381,10 +387,7 @@ class WindowBatch:
         info = 1 has every cov NaN and bit 1 set everywhere; the call then raises BackendError (OKVIS_BA_ERR_NUMERIC) whose
         ``results`` attribute holds the list."""
         from .window import predcov_marshal_batch
-        w0 = int(w0)
-        n = len(self.windows) - w0 if n is None else int(n)
-        if w0 < 0 or n < 1 or w0 + n > len(self.windows):
-            raise IndexError(f"windows {w0} .. {w0 + n - 1} of a batch of {len(self.windows)}")
+        w0, n = self._window_range(w0, n)
         if queries is None:
             qs = [None] * n
         elif isinstance(queries, np.ndarray) and queries.ndim == 2:
@@ -394,33 +397,20 @@ class WindowBatch:
             if len(qs) != n:
                 raise ValueError(f"{len(qs)} query lists for {n} windows")
         qs = [self.newest_state_queries(w0 + i) if q is None else np.asarray(q, np.int32).reshape(-1, 4) for i, q in enumerate(qs)]
-        taps = None
-        if want_taps:
-            taps = []
-            for i in range(n):
-                W = self.windows[w0 + i]
-                np_ = C.c_int32()
-                _lib.check(self._L.okvis_ba_pair_count(self._h, w0 + i, C.byref(np_)))
-                taps.append((self.reduced_dim(w0 + i), 6 * int((np.asarray(W.pose_fixed).reshape(-1) == 0).sum()), int(W.n_lm), np_.value))
+        taps = self._tap_dims(w0, n) if want_taps else None
         specs, results, outs, keep = predcov_marshal_batch(qs, taps)
         st = self._L.okvis_ba_predicted_measurement(self._h, w0, n, specs, results)
         del keep
-        if st not in (0, -5):
-            _lib.check(st, "predicted_measurement")
-        res = []
-        for i in range(n):
+
+        def unpack(i):
             m = int(results[i].n)
             r = dict(uv=outs[i]["uv"][:m].copy(), cov=outs[i]["cov"][:m].reshape(m, 2, 2).copy(), flags=outs[i]["flags"][:m].copy(),
                      info=int(results[i].info), min_pivot=float(results[i].min_pivot))
             if want_taps:
                 r.update({k: outs[i][k].copy() for k in ("S0", "Spp", "V", "W")})
                 r["jac"] = outs[i]["jac"][:m].copy()
-            res.append(r)
-        if st != 0:
-            err = _lib.BackendError(st, "predicted_measurement")
-            err.results = res
-            raise err
-        return res
+            return r
+        return self._covariance_results(st, "predicted_measurement", n, unpack)
 
     def last_predicted_measurement_ms(self) -> dict:
         """okvis_ba_last_predicted_measurement_ms: HIP-event times of the last predicted_measurement call's assembly launches, of the

@@ -190,14 +190,22 @@ def lmcov_marshal_batch(selections, counts, tap_dims=None):
         results[i].cov = out["cov"].ctypes.data_as(_dp)
         results[i].flags = out["flags"].ctypes.data_as(_bp)
         if tap_dims is not None:
-            D, Dp, n_lm, n_pair = (int(x) for x in tap_dims[i])
-            out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)))
-            for k in ("S0", "Spp", "V", "W"):
-                buf = out[k] if out[k].size else np.zeros(1)
-                keep.append(buf)
-                setattr(results[i], k, buf.ctypes.data_as(_dp))
+            _attach_taps(results[i], out, keep, tap_dims[i])
         outs.append(out)
     return specs, results, outs, keep
+
+
+def _attach_taps(result, out, keep, dims, jac_rows=None):
+    """The referee's tap buffers of one window, dims = (D, Dp, n_lm, n_pair): S0, Spp, V, W and, with jac_rows, jac [jac_rows][30]
+    into `out`, their addresses into `result` (an empty array is still an array: a non-NULL pointer, kept alive in `keep`)."""
+    D, Dp, n_lm, n_pair = (int(x) for x in dims)
+    out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)))
+    if jac_rows is not None:
+        out.update(jac=np.zeros((jac_rows, 30)))
+    for k in ("S0", "Spp", "V", "W") + (("jac",) if jac_rows is not None else ()):
+        buf = out[k] if out[k].size else np.zeros(1)
+        keep.append(buf)
+        setattr(result, k, buf.ctypes.data_as(_dp))
 
 
 def predcov_marshal_batch(queries, tap_dims=None):
@@ -221,12 +229,7 @@ def predcov_marshal_batch(queries, tap_dims=None):
         results[i].cov = out["cov"].ctypes.data_as(_dp)
         results[i].flags = out["flags"].ctypes.data_as(_bp)
         if tap_dims is not None:
-            D, Dp, n_lm, n_pair = (int(x) for x in tap_dims[i])
-            out.update(S0=np.zeros((D, D)), Spp=np.zeros((Dp, Dp)), V=np.zeros((n_lm, 6)), W=np.zeros((n_pair, 18)), jac=np.zeros((max(1, m), 30)))
-            for k in ("S0", "Spp", "V", "W", "jac"):
-                buf = out[k] if out[k].size else np.zeros(1)
-                keep.append(buf)
-                setattr(results[i], k, buf.ctypes.data_as(_dp))
+            _attach_taps(results[i], out, keep, tap_dims[i], jac_rows=max(1, m))
         outs.append(out)
     return specs, results, outs, keep
 
