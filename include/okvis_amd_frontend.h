@@ -32,8 +32,12 @@
  *                                (okvis_frontend/include/opengv/sac_problems/absolute_pose/FrameAbsolutePoseSacProblem.hpp:129-161,
  *                                 .../relative_pose/FrameRotationOnlySacProblem.hpp:122-144, .../relative_pose/FrameRelativePoseSacProblem.hpp:126-161)
  *
- * The minimal solvers (GP3P, five-point, two-point rotation), the sampler and the RANSAC loop are OpenGV's and are not here:
- * hypotheses come in from the caller.
+ *   okvis_fe_sac_solve           the two minimal solvers of runRansac2d2d (two-point rotation, five-point relative pose) for all samples
+ *                                of many problems per call, chained into the consensus kernel: sample indices in, inlier sets out.
+ *                                Stated from their published definitions, not pinned to OpenGV
+ *
+ * The generalised P3P of runRansac3d2d, the sampler and the RANSAC loop are OpenGV's and are not here: okvis_fe_sac_consensus takes
+ * its hypotheses from the caller, okvis_fe_sac_solve its samples.
  *
  * and the state propagation that every layer around the backend calls:
  *
@@ -268,6 +272,61 @@ typedef struct okvis_fe_sac_job { /* one sample-consensus problem with its hypot
  * correspondences); best and inliers are read off them on the host.  A cam_index entry outside 0..n_cams-1 is OKVIS_BA_ERR_ARG.
  * What is not here: the minimal solvers, the sampler, the loop (see INTEGRATION.md for the recipe). */
 int okvis_fe_sac_consensus(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_job* jobs);
+
+#define OKVIS_FE_SAC_SAMPLE_ROTATION_ONLY 2 /* correspondences per sample of a rotation-only job                        */
+#define OKVIS_FE_SAC_SAMPLE_RELATIVE 8      /* of a relative job: 5 that define E + 3 that pick the pose                */
+#define OKVIS_FE_SAC_MAX_ROOTS 10           /* real essential matrices of five correspondences                          */
+
+typedef struct okvis_fe_sac_solve_job { /* one 2D-2D sample-consensus problem with its samples: hypotheses are solved for, then scored */
+  int32_t kind;      /* OKVIS_FE_SAC_ROTATION_ONLY or _RELATIVE; _ABSOLUTE is OKVIS_BA_ERR_ARG */
+  int32_t n;         /* correspondences, 0..65536                                             */
+  int32_t n_models;  /* samples = hypotheses, 1..1024                                         */
+  int32_t reserved;  /* 0                                                                     */
+  double threshold;
+  const double *bearing1, *bearing2; /* [n][3]                                      */
+  const double *sigma1, *sigma2;     /* [n]; read only when something is scored     */
+  const int32_t* samples;            /* [n_models][2] or [n_models][8], indices into 0..n-1 */
+  /* out, hypotheses; each may be NULL */
+  double* models;     /* [n_models][9] rotation_t / [n_models][12] transformation_t, the layout okvis_fe_sac_job.models takes;
+                         every entry of an invalid hypothesis is a quiet NaN                                                    */
+  uint8_t* valid;     /* [n_models]                                                                                            */
+  int32_t* n_roots;   /* relative, referee: real essential matrices found, 0..10                                               */
+  double* essentials; /* relative, referee: [n_models][10][9] row-major, unit Frobenius norm, the first n_roots written (in no
+                         stated order, each up to sign)                                                                        */
+  /* out, consensus: exactly the five fields of okvis_fe_sac_job with the same meaning; all NULL = no scoring launch */
+  int32_t *counts, *best, *n_inliers, *inliers;
+  double* scores;
+} okvis_fe_sac_solve_job;
+
+/* The minimal solvers of Frontend::runRansac2d2d (okvis_frontend/src/Frontend.cpp:645-810) for all samples of many problems in one
+ * call, chained into the consensus kernel of okvis_fe_sac_consensus: sample indices in, hypotheses and inlier sets out.  The
+ * solvers are OpenGV's, and OpenGV's source is not part of the reference tree: like triangulate2 above, both solvers are stated
+ * from their published mathematical definitions and are NOT pinned to OpenGV.
+ * Convention (the consensus entry's): a point of frame 2 is R12 p2 + t12 in frame 1, so R f2 ~ f1 and f1^T E f2 = 0, E = [t12]x R12.
+ *   rotation only  sample (i, j).  a1 = f1_i, a2 = (f1_i x f1_j) / |.|, a3 = a1 x a2; b1, b2, b3 alike from frame 2;
+ *                  R(r,c) = (a1[r] b1[c] + a2[r] b2[c]) + a3[r] b3[c].  Cross products as u1 v2 - u2 v1 etc., the norm as
+ *                  sqrt((x x + y y) + z z), then three divisions; IEEE double without fused multiply-adds, so the nine doubles
+ *                  equal a float64 evaluation of these lines bit for bit.  Invalid when i == j or a cross product's norm is zero
+ *                  or not finite.
+ *   relative       sample (i0..i7); invalid up front when two of the eight indices are equal.  Candidates: all real E != 0, up to
+ *                  scale, in the null space of the 5x9 matrix with rows vec(f1_k f2_k^T), k = i0..i4, with det E = 0 and
+ *                  2 E E^T E - tr(E E^T) E = 0 (at most ten); for each the four (R, +-t) from its singular vectors (R = U W V^T,
+ *                  U W^T V^T with det R = +1; |t| = 1, t^T E = 0).  A candidate passes when both ray parameters of the two-view
+ *                  midpoint method are positive for all eight correspondences; the hypothesis is the passing candidate with the
+ *                  smallest sum of the eight relative-pose scores (sigma = 1 where sigma1 / sigma2 are NULL), invalid when none
+ *                  passes.  t12 has unit length (Frontend.cpp:782-787 rescales it by the motion prior).
+ *                  The route is Nister's polynomial of degree ten with a polish on the definition; every loop has a compile-time
+ *                  count and the result is deterministic.  tests/sac_solve_statement.py states the definition at 60 digits and
+ *                  tests/sac_solve_cases.py the bound the hypotheses are held to.
+ * One staging copy in, one solver launch for all jobs, one launch of the consensus kernel when any consensus output is asked for
+ * (it reads the hypotheses where the solver left them in device memory), one copy back.  A NaN hypothesis scores NaN in every
+ * cell; the consensus kernel counts `score < threshold`, which is false for NaN, so an invalid hypothesis has count 0 and never
+ * displaces a valid best under the "strictly larger count" rule (with every hypothesis invalid, best = 0 and n_inliers = 0).
+ * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or required pointer (bearing1, bearing2
+ * for n > 0, samples), a negative count, n or n_models out of range, an unknown kind or OKVIS_FE_SAC_ABSOLUTE, a sample index
+ * outside 0..n-1 (so n = 0 has no valid sample), NULL sigma1 or sigma2 while a consensus output is wanted.  n_jobs = 0 is valid.
+ * What is not here: the generalised P3P of runRansac3d2d, the sampler, the loop. */
+int okvis_fe_sac_solve(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_solve_job* jobs);
 
 #define OKVIS_FE_IMU_COV 1 /* the 15x15 covariance of the propagated state is wanted */
 #define OKVIS_FE_IMU_JAC 2 /* the 15x15 Jacobian of the propagated state is wanted   */

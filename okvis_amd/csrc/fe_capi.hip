@@ -16,6 +16,7 @@
 #include "fe_kernels.hpp"
 #include "fe_match.hpp"
 #include "fe_sac.hpp"
+#include "fe_sac_solve.hpp"
 #include "fe_vmatch.hpp"
 #include "fe_propagate.hpp"
 #include "fe_keyframe.hpp"
@@ -826,6 +827,139 @@ int okvis_fe_sac_consensus(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_s
         for (unsigned long long m = ballots[(size_t)best * words + w]; m; m &= m - 1) J.inliers[k++] = (int32_t)(64 * w) + __builtin_ctzll(m);
     }
     st.get(plan[j].scores, J.scores);
+  }
+  return OKVIS_BA_OK;
+}
+
+// The solvers in front of the consensus kernel: one staging copy in, sac_solve_kernel for all jobs, sac_consensus_kernel (as
+// okvis_fe_sac_consensus launches it) on the hypotheses where the solver left them, one copy back.
+int okvis_fe_sac_solve(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_sac_solve_job* jobs) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && !jobs)) return OKVIS_BA_ERR_ARG;
+  if (n_jobs == 0) return OKVIS_BA_OK;
+  size_t solve_blocks = 0, blocks = 0, n_scored = 0, n_counts = 0, n_words = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_solve_job& J = jobs[j];
+    if ((J.kind != OKVIS_FE_SAC_ROTATION_ONLY && J.kind != OKVIS_FE_SAC_RELATIVE) || J.n < 0 || J.n > fe::SAC_MAX_N || J.n_models < 1 ||
+        J.n_models > fe::SAC_MAX_MODELS || !J.samples || (J.n > 0 && (!J.bearing1 || !J.bearing2)))
+      return OKVIS_BA_ERR_ARG;
+    const bool scored = J.counts || J.best || J.n_inliers || J.inliers || J.scores;
+    if (scored && (!J.sigma1 || !J.sigma2)) return OKVIS_BA_ERR_ARG;
+    const bool relative = J.kind == OKVIS_FE_SAC_RELATIVE;
+    const size_t width = relative ? OKVIS_FE_SAC_SAMPLE_RELATIVE : OKVIS_FE_SAC_SAMPLE_ROTATION_ONLY;
+    for (size_t i = 0; i < width * (size_t)J.n_models; ++i)
+      if (J.samples[i] < 0 || J.samples[i] >= J.n) return OKVIS_BA_ERR_ARG;  // n = 0 ends here: every job past this line has n >= 1
+    solve_blocks += relative ? (size_t)J.n_models : ((size_t)J.n_models + 63) / 64;
+    if (!scored) continue;
+    const size_t tiles = ((size_t)J.n + fe::SAC_THREADS - 1) / fe::SAC_THREADS;
+    ++n_scored, blocks += tiles * (((size_t)J.n_models + fe::SAC_MODEL_TILE - 1) / fe::SAC_MODEL_TILE);
+    n_counts += (size_t)J.n_models, n_words += (size_t)J.n_models * (((size_t)J.n + 63) / 64);
+  }
+  if (solve_blocks > (size_t)INT32_MAX || blocks > (size_t)INT32_MAX || n_counts > (size_t)INT32_MAX) return OKVIS_BA_ERR_ARG;
+  FE_TRY(hipSetDevice(c->device));
+  Stage st{c};
+  struct Plan {
+    Staged<double> a, b, s1, s2, models, essentials, scores;
+    Staged<int32_t> samples, n_roots;
+    Staged<uint8_t> valid;
+    bool scored = false;
+  };
+  std::vector<Plan> plan((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_solve_job& J = jobs[j];
+    Plan& p = plan[j];
+    const size_t n = (size_t)J.n;
+    p.scored = J.counts || J.best || J.n_inliers || J.inliers || J.scores;
+    p.a = st.in<double>(3 * n), p.b = st.in<double>(3 * n);
+    p.s1 = st.in<double>(n, J.sigma1 != nullptr), p.s2 = st.in<double>(n, J.sigma2 != nullptr);
+    p.samples = st.in<int32_t>((size_t)J.n_models * (J.kind == OKVIS_FE_SAC_RELATIVE ? 8 : 2));
+  }
+  const auto s_solve = st.in<fe::SolveJob>((size_t)n_jobs);
+  const auto s_table = st.in<fe::SacJob>(n_scored, n_scored > 0);
+  const auto model_doubles = [&](int j) { return (size_t)jobs[j].n_models * (jobs[j].kind == OKVIS_FE_SAC_RELATIVE ? 12 : 9); };
+  for (int j = 0; j < n_jobs; ++j)  // hypotheses the caller does not take stay on the device
+    if (!jobs[j].models) plan[j].models = st.scratch<double>(model_doubles(j));
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_solve_job& J = jobs[j];
+    const bool relative = J.kind == OKVIS_FE_SAC_RELATIVE;
+    if (J.models) plan[j].models = st.out<double>(model_doubles(j));
+    plan[j].valid = st.out<uint8_t>((size_t)J.n_models, J.valid != nullptr);
+    plan[j].n_roots = st.out<int32_t>((size_t)J.n_models, relative && J.n_roots);
+    plan[j].essentials = st.out<double>(90 * (size_t)J.n_models, relative && J.essentials);
+  }
+  const auto s_counts = st.out<int32_t>(n_counts, n_scored > 0);
+  const auto s_ballots = st.out<unsigned long long>(n_words, n_scored > 0);
+  for (int j = 0; j < n_jobs; ++j) plan[j].scores = st.out<double>((size_t)jobs[j].n_models * (size_t)jobs[j].n, jobs[j].scores != nullptr);
+  if (int rc = st.reserve()) return rc;
+  fe::SolveJob* solve_table = st.host(s_solve);
+  fe::SacJob* table = st.host(s_table);
+  size_t solve_block0 = 0, block0 = 0, count0 = 0, word0 = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_solve_job& J = jobs[j];
+    const Plan& p = plan[j];
+    const size_t n = (size_t)J.n;
+    const bool relative = J.kind == OKVIS_FE_SAC_RELATIVE;
+    double *dst_a = st.host(p.a), *dst_b = st.host(p.b);  // [n][3] -> [3][n], as the consensus kernel reads them
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < 3; ++k) dst_a[k * n + i] = J.bearing1[3 * i + k], dst_b[k * n + i] = J.bearing2[3 * i + k];
+    st.put(p.s1, J.sigma1), st.put(p.s2, J.sigma2), st.put(p.samples, J.samples);
+    fe::SolveJob S;
+    S.a = st.dev(p.a), S.b = st.dev(p.b), S.sigma1 = st.dev(p.s1), S.sigma2 = st.dev(p.s2), S.samples = st.dev(p.samples);
+    S.models = st.dev(p.models), S.valid = st.dev(p.valid), S.n_roots = st.dev(p.n_roots), S.essentials = st.dev(p.essentials);
+    S.kind = J.kind, S.n = J.n, S.n_models = J.n_models, S.block0 = (int32_t)solve_block0;
+    solve_table[j] = S;
+    solve_block0 += relative ? (size_t)J.n_models : ((size_t)J.n_models + 63) / 64;
+    if (!p.scored) continue;
+    fe::SacJob D;
+    D.models = st.dev(p.models), D.a = st.dev(p.a), D.b = st.dev(p.b), D.sigma1 = st.dev(p.s1), D.sigma2 = st.dev(p.s2);
+    D.cam_index = nullptr, D.cams = nullptr, D.scores = st.dev(p.scores);
+    D.threshold = J.threshold, D.kind = J.kind, D.n = J.n, D.n_models = J.n_models;
+    D.block0 = (int32_t)block0, D.tiles = (int32_t)((n + fe::SAC_THREADS - 1) / fe::SAC_THREADS);
+    D.count0 = (int32_t)count0, D.word0 = (int64_t)word0;
+    *table++ = D;
+    block0 += (size_t)D.tiles * (((size_t)J.n_models + fe::SAC_MODEL_TILE - 1) / fe::SAC_MODEL_TILE);
+    count0 += (size_t)J.n_models, word0 += (size_t)J.n_models * ((n + 63) / 64);
+  }
+  if (int rc = st.upload()) return rc;
+  // essentials past n_roots are not written by the kernel: NaN, so that the copy back never hands out stale staging bytes
+  for (int j = 0; j < n_jobs; ++j)
+    if (plan[j].essentials.on) FE_TRY(hipMemsetAsync(st.dev(plan[j].essentials), 0xff, plan[j].essentials.bytes(), c->stream));
+  fe::SolveParams SP;
+  SP.jobs = st.dev(s_solve), SP.n_jobs = n_jobs;
+  hipLaunchKernelGGL(fe::sac_solve_kernel, dim3((unsigned)solve_blocks), dim3(64), 0, c->stream, SP);
+  FE_TRY(hipGetLastError());
+  if (n_scored > 0) {
+    FE_TRY(hipMemsetAsync(st.dev(s_counts), 0, s_counts.bytes(), c->stream));
+    fe::SacParams P;
+    P.jobs = st.dev(s_table), P.n_jobs = (int32_t)n_scored;
+    P.counts = st.dev(s_counts), P.ballots = st.dev(s_ballots);
+    hipLaunchKernelGGL(fe::sac_consensus_kernel, dim3((unsigned)blocks), dim3(fe::SAC_THREADS), 0, c->stream, P);
+    FE_TRY(hipGetLastError());
+  }
+  if (int rc = st.download()) return rc;
+  count0 = word0 = 0;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_solve_job& J = jobs[j];
+    const Plan& p = plan[j];
+    if (J.models) st.get(p.models, J.models);
+    st.get(p.valid, J.valid), st.get(p.n_roots, J.n_roots), st.get(p.essentials, J.essentials);
+    if (!p.scored) continue;
+    // Ransac::computeModel's book-keeping, as in okvis_fe_sac_consensus
+    const size_t words = ((size_t)J.n + 63) / 64;
+    const int32_t* counts = st.host(s_counts) + count0;
+    const unsigned long long* ballots = st.host(s_ballots) + word0;
+    count0 += (size_t)J.n_models, word0 += (size_t)J.n_models * words;
+    int best = 0;
+    for (int m = 1; m < J.n_models; ++m)
+      if (counts[m] > counts[best]) best = m;
+    if (J.counts) std::copy_n(counts, J.n_models, J.counts);
+    if (J.best) *J.best = best;
+    if (J.n_inliers) *J.n_inliers = counts[best];
+    if (J.inliers) {
+      int32_t k = 0;
+      for (size_t w = 0; w < words; ++w)
+        for (unsigned long long m = ballots[(size_t)best * words + w]; m; m &= m - 1) J.inliers[k++] = (int32_t)(64 * w) + __builtin_ctzll(m);
+    }
+    st.get(p.scores, J.scores);
   }
   return OKVIS_BA_OK;
 }

@@ -1,6 +1,7 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
 with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
-best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the IMU state
+best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the outlier rejection
+behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems), the IMU state
 propagation with covariance and Jacobian and the keyframe decision (exact hulls, areas and inside counts) on the MI355X.  No CPU
 path."""
 from __future__ import annotations
@@ -17,9 +18,11 @@ PROJ_SUCCESSFUL, PROJ_OUTSIDE_IMAGE, PROJ_MASKED, PROJ_BEHIND, PROJ_INVALID = ra
 GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
-           "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision"]
+           "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
+           "okvis_fe_sac_solve"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
+SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
 IMU_COV, IMU_JAC = 1, 2
 KF_FEW_POINTS, KF_FEW_MATCHES = 1, 2
 KF_MAX_KEYPOINTS, KF_MAX_CAMS = 8192, 8
@@ -53,6 +56,15 @@ class SacJobC(C.Structure):
                 ("models", C.c_void_p), ("points", C.c_void_p), ("bearing", C.c_void_p), ("sigma", C.c_void_p), ("cam_index", C.c_void_p),
                 ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("bearing1", C.c_void_p), ("bearing2", C.c_void_p),
                 ("sigma1", C.c_void_p), ("sigma2", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p),
+                ("inliers", C.c_void_p), ("scores", C.c_void_p)]
+
+
+class SacSolveJobC(C.Structure):
+    """okvis_fe_sac_solve_job"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("n_models", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double),
+                ("bearing1", C.c_void_p), ("bearing2", C.c_void_p), ("sigma1", C.c_void_p), ("sigma2", C.c_void_p),
+                ("samples", C.c_void_p), ("models", C.c_void_p), ("valid", C.c_void_p), ("n_roots", C.c_void_p),
+                ("essentials", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p),
                 ("inliers", C.c_void_p), ("scores", C.c_void_p)]
 
 
@@ -129,6 +141,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_match_descriptors.argtypes = [vp, i32, C.POINTER(MatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_bearing_vectors.argtypes = [vp, cam, i32, vp, vp, vp, vp]
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
+        L.okvis_fe_sac_solve.argtypes = [vp, i32, C.POINTER(SacSolveJobC)]
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
         L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
@@ -295,6 +308,28 @@ class Frontend:
             r = {"counts": counts, "best": int(scalars[0]), "n_inliers": int(scalars[1]), "inliers": inl[:int(scalars[1])].copy()}
             if want_scores:
                 r["scores"] = sc
+            res.append(r)
+        return res
+
+    def sac_solve(self, jobs, want_scores=False, want_essentials=False):
+        """The minimal solvers of the 2D-2D outlier rejection in front of sac_consensus, all jobs in one call.  jobs: dicts with
+        kind (SAC_ROTATION_ONLY or SAC_RELATIVE), bearing1, bearing2 [n][3], samples [K][2] (rotation only) or [K][8] (relative:
+        five that define E, three more that pick the pose), threshold (default 9), sigma1, sigma2 [n] (may be left out of a job
+        with consensus=False: the relative selection then weighs with 1), consensus (default True: score the hypotheses).
+        -> per job a dict: models [K][3][3] / [K][3][4] (NaN where invalid), valid [K] bool; with consensus counts, best,
+        n_inliers, inliers as sac_consensus returns them, and scores [K][n] under want_scores; relative jobs under
+        want_essentials also n_roots [K] and essentials [K][10][9] (unit norm, NaN past n_roots)."""
+        table, keep, out = sac_solve_job_table(jobs, want_scores, want_essentials)
+        self._call("sac_solve", len(jobs), table)
+        res = []
+        for o in out:
+            r = {"models": o["models"], "valid": o["valid"].astype(bool)}
+            if "counts" in o:
+                k = int(o["scalars"][1])
+                r.update(counts=o["counts"], best=int(o["scalars"][0]), n_inliers=k, inliers=o["inliers"][:k].copy())
+            for name in ("scores", "n_roots", "essentials"):
+                if name in o:
+                    r[name] = o[name]
             res.append(r)
         return res
 
@@ -471,6 +506,43 @@ def sac_job_table(jobs, want_scores=False):
         t.counts, t.best, t.n_inliers, t.inliers = counts.ctypes.data, scalars.ctypes.data, scalars.ctypes.data + 4, inl.ctypes.data
         t.scores = _ptr(sc)
         out.append((counts, scalars, inl, sc))
+    return table, keep, out
+
+
+def sac_solve_job_table(jobs, want_scores=False, want_essentials=False):
+    """-> (okvis_fe_sac_solve_job array, the input arrays it points into, per job the dict of output arrays); both lists have to
+    outlive the call"""
+    keep, out = [], []
+    table = (SacSolveJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        kind = int(job["kind"])
+        if kind not in (SAC_ROTATION_ONLY, SAC_RELATIVE):
+            raise ValueError("kind is SAC_ROTATION_ONLY or SAC_RELATIVE")
+        relative = kind == SAC_RELATIVE
+        a, b = _f64(job["bearing1"]).reshape(-1, 3), _f64(job["bearing2"]).reshape(-1, 3)
+        q = np.ascontiguousarray(job["samples"], np.int32).reshape(-1, SAC_SAMPLE_RELATIVE if relative else SAC_SAMPLE_ROTATION_ONLY)
+        s1 = None if job.get("sigma1") is None else _f64(job["sigma1"]).reshape(-1)
+        s2 = None if job.get("sigma2") is None else _f64(job["sigma2"]).reshape(-1)
+        if len(a) != len(b) or any(s is not None and len(s) != len(a) for s in (s1, s2)):
+            raise ValueError("arrays of different lengths")
+        n, K = len(a), len(q)
+        t = table[j]
+        t.kind, t.n, t.n_models, t.threshold = kind, n, K, float(job.get("threshold", 9.0))
+        t.bearing1, t.bearing2, t.sigma1, t.sigma2, t.samples = a.ctypes.data, b.ctypes.data, _ptr(s1), _ptr(s2), q.ctypes.data
+        keep.append((a, b, s1, s2, q))
+        o = {"models": np.zeros((K, 3, 4 if relative else 3)), "valid": np.zeros(K, np.uint8)}
+        t.models, t.valid = o["models"].ctypes.data, o["valid"].ctypes.data
+        if relative and want_essentials:
+            o["n_roots"], o["essentials"] = np.zeros(K, np.int32), np.zeros((K, SAC_MAX_ROOTS, 9))
+            t.n_roots, t.essentials = o["n_roots"].ctypes.data, o["essentials"].ctypes.data
+        if job.get("consensus", True):
+            o["counts"], o["scalars"], o["inliers"] = np.zeros(K, np.int32), np.zeros(2, np.int32), np.zeros(max(n, 1), np.int32)
+            t.counts, t.best, t.n_inliers = o["counts"].ctypes.data, o["scalars"].ctypes.data, o["scalars"].ctypes.data + 4
+            t.inliers = o["inliers"].ctypes.data
+            if want_scores:
+                o["scores"] = np.zeros((K, n))
+                t.scores = o["scores"].ctypes.data
+        out.append(o)
     return table, keep, out
 
 
