@@ -5,8 +5,9 @@
      staging block growing in between, equal the same calls made on a context of their own.
 
 Everything is compared byte for byte.  Scenes: tests/vmatch_scene.py at (65, 63) and (257, 513), which cross the 64-lane block and
-the 256-descriptor tile; the sample-consensus problems are recorded ones (tests/sac_cases.py).  Where okvis_amd/frontend.py always
-passes a pointer, the library is called through the tables and ctypes directly."""
+the 256-descriptor tile; the sample-consensus problems are recorded ones (tests/sac_cases.py); the solvers, the propagation and
+the keyframe decision take seeded cases of tests/sac_solve_cases.py, tests/imu_propagate_cases.py and tests/keyframe_cases.py.
+Where okvis_amd/frontend.py always passes a pointer, the library is called through the tables and ctypes directly."""
 import ctypes as C
 import functools
 import os
@@ -17,7 +18,10 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+import imu_propagate_cases as IC  # noqa: E402
+import keyframe_cases as KC  # noqa: E402
 import sac_cases  # noqa: E402
+import sac_solve_cases as SSC  # noqa: E402
 import vmatch_scene as SC  # noqa: E402
 from okvis_amd import frontend as F  # noqa: E402
 from okvis_amd.window import DIST_EQUIDISTANT, DIST_RADTAN  # noqa: E402
@@ -53,6 +57,20 @@ def vjob(kind, s):
 def sac_jobs():
     g = sac_cases.golden()
     return [sac_cases.golden_job(g, 0, name) for name in sac_cases.PROBLEMS]
+
+
+def solve_jobs():
+    """a relative job of 65 correspondences and 9 hypotheses (one ballot word and one model tile, each plus one) and a rotation-only
+    job of 257 and 65 (one 256-lane tile and one wave of samples, each plus one)"""
+    return [SSC.relative_job(SSC.case(365, 65, 9)), SSC.rotation_job(SSC.case(557, 257, 65))]
+
+
+def kf_arrays(res):
+    """what Frontend.keyframe_decision returns for some jobs, as flat arrays"""
+    ims = [im for r in res for im in r["images"]]
+    a = {k: np.array([r[k] for r in res]) for k in ("decision", "overlap", "ratio")}
+    a.update({k: np.concatenate([np.atleast_1d(im[k]) for im in ims]) for k in ims[0]})
+    return a
 
 
 def same(x, y):
@@ -164,6 +182,73 @@ def test_an_optional_output_left_out_changes_no_other_output():
             for x in f:
                 if x != name:
                     assert p[x].tobytes() == f[x].tobytes(), (name, x)
+    # the solvers: models / valid / n_roots / essentials / counts / best / n_inliers / inliers / scores, a relative and a
+    # rotation-only job in one call
+    sjobs = solve_jobs()
+
+    def solve(without=(), sigmas=True):
+        table, keep, out = F.sac_solve_job_table(sjobs, want_scores=True, want_essentials=True)
+        for j, o in enumerate(out):
+            o["best"], o["n_inliers"] = o["scalars"][:1], o["scalars"][1:]
+            del o["scalars"]
+            for a in o.values():
+                a.view(np.uint8)[...] = 0x5A
+            for name in without:
+                setattr(table[j], name, None)
+            if not sigmas:
+                table[j].sigma1 = table[j].sigma2 = None
+        check(L.okvis_fe_sac_solve(ctx, len(sjobs), table))
+        return out
+
+    def untouched_and_same(full, part, without):
+        for f, p in zip(full, part):
+            for x in f:
+                if x in without:
+                    assert (p[x].view(np.uint8) == 0x5A).all(), (without, x)
+                else:
+                    assert p[x].tobytes() == f[x].tobytes(), (without, x)
+
+    full = solve()
+    assert all(f["valid"].view(np.uint8).sum() > 0 and int(f["n_inliers"][0]) > 0 for f in full)
+    for name in ("models", "valid", "n_roots", "essentials", "counts", "best", "n_inliers", "inliers", "scores"):
+        untouched_and_same(full, solve((name,)), (name,))
+    # all five consensus outputs left out: no scoring, and then the sigmas may be left out too (the two-point solver reads none;
+    # the five-point selection weighs with 1 without them, so only what it does not select is compared)
+    five = ("counts", "best", "n_inliers", "inliers", "scores")
+    untouched_and_same(full, solve(five), five)
+    bare = solve(five, sigmas=False)
+    untouched_and_same(full[1:], bare[1:], five)
+    untouched_and_same([{x: full[0][x] for x in five + ("n_roots", "essentials")}], [{x: bare[0][x] for x in five + ("n_roots", "essentials")}], five)
+    # propagation: cov / jac, with flags to match
+    s_t, s_gyr, s_acc, ends, pjobs = IC.pool([IC.by_name(x) for x in ("steps11", "chain", "uncovered")])
+    prm, s_t, s_gyr, s_acc, ends = F.imu_pools(IC.PARAMS, s_t, s_gyr, s_acc, ends)
+    m = len(ends)
+
+    def propagate(p, drop=0):
+        table = F.imu_job_table([dict(j, flags=(F.IMU_COV | F.IMU_JAC) & ~drop) for j in pjobs])
+        check(L.okvis_fe_imu_propagate(ctx, len(prm), prm, len(s_t), s_t.ctypes.data, s_gyr.ctypes.data, s_acc.ctypes.data, m, ends.ctypes.data,
+                                       len(pjobs), table, p["T_WS"], p["sb"], p["cov"], p["jac"], p["count"]))
+
+    def run_propagate(without=None):
+        arrays = {"T_WS": np.empty((m, 7)), "sb": np.empty((m, 9)), "cov": np.empty((m, 15, 15)), "jac": np.empty((m, 15, 15)),
+                  "count": np.empty(m, np.int32)}
+        for a in arrays.values():
+            a.view(np.uint8)[...] = 0x5A
+        propagate({k: (None if k == without else a.ctypes.data) for k, a in arrays.items()}, {"cov": F.IMU_COV, "jac": F.IMU_JAC, None: 0}[without])
+        return arrays
+
+    full = run_propagate()
+    assert (full["count"] > 0).sum() >= 12 and (full["count"] == -1).sum() == 2
+    for name in ("cov", "jac"):
+        untouched_and_same([full], [run_propagate(name)], (name,))
+    # keyframe decision: its twelve outputs
+    kp, matched, images, table, counts = F.keyframe_job_table(KC.cases("degenerate") + KC.cases("on_edges"))
+    n_jobs = len(KC.cases("degenerate")) + len(KC.cases("on_edges"))
+    shapes = {k: (a.shape, a.dtype) for k, a in F.keyframe_outputs(n_jobs, len(counts), sum(counts), want_hulls=True).items()}
+    assert tuple(shapes) == F.KF_OUTPUTS and len(shapes) == 12
+    r = each_left_out(lambda p: check(L.okvis_fe_keyframe_decision(ctx, len(matched), kp.ctypes.data, matched.ctypes.data, len(counts), images,
+                                                                   n_jobs, table, *[p[k] for k in F.KF_OUTPUTS])), shapes)
+    assert r["hull_all_size"].sum() > 20 and r["n_inside"].sum() > 0
     fe.close()
     assert written > 100
 
@@ -190,14 +275,31 @@ def test_entries_mixed_on_one_context_equal_each_on_a_context_of_its_own():
         chi2, flags = fe.gate_3d2d(uv0, U0, s0["kp_b"], pairs0)
         return {"chi2": chi2, "flags": flags}
 
+    def solve(fe):
+        r, = fe.sac_solve(solve_jobs()[:1], want_scores=True, want_essentials=True)
+        return {k: np.asarray(v) for k, v in r.items()}
+
+    def propagate(fe):
+        s_t, s_gyr, s_acc, ends, pjobs = IC.pool([IC.by_name("chain_between")])
+        return dict(zip(("T_WS", "sb", "count", "cov", "jac"), fe.imu_propagate(IC.PARAMS, s_t, s_gyr, s_acc, pjobs, ends)))
+
+    def keyframe(fe):
+        return kf_arrays(fe.keyframe_decision(KC.cases("convex"), want_hulls=True))
+
     steps = [triangulate, match(s1, F.MATCH_2D2D), consensus, gate, match(s0, F.MATCH_3D2D), match(s1, F.MATCH_3D2D), triangulate]
+    between = {1: solve, 3: propagate, 5: keyframe}      # run in front of the step of that index
     fe = F.Frontend()                       # its staging block starts empty and moves at the second step
-    mixed = [step(fe) for step in steps]
+    mixed, mixed_between = [], {}
+    for i, step in enumerate(steps):
+        if i in between:
+            mixed_between[i] = between[i](fe)
+        mixed.append(step(fe))
     fe.close()
-    for step, got in zip(steps, mixed):
+    for step, got in list(zip(steps, mixed)) + [(between[i], mixed_between[i]) for i in between]:
         own = F.Frontend()
         want = step(own)
         own.close()
         assert same(got, want), step
+    assert int(mixed_between[1]["n_inliers"]) > 0 and (mixed_between[3]["count"] > 0).all() and mixed_between[5]["hull_all_size"].sum() > 600
     assert int(mixed[1]["accepted"].sum()) > 20 and int(mixed[4]["accepted"].sum()) > 0 and int(mixed[2]["n_inliers"]) > 0
     assert (mixed[0]["flags"] & F.TRI_VALID != 0).any() and (mixed[3]["flags"] & F.GATE_VERIFIED != 0).any()

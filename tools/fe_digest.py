@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry is called through okvis_amd.frontend; per case the SHA-256 of every output array goes to OUT.json.  Two trees
-whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.
+Every okvis_fe_* entry (the thirteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
+every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
+in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
+whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
+group differs, --cases FILE writes the hash of every array of every case (some 18 000 lines: to be compared, not to be kept).
 
-    python tools/fe_digest.py OUT.json [--root TREE]      (TREE: the checkout whose okvis_amd is used, default this one)
+    python tools/fe_digest.py OUT.json [--root TREE] [--cases FILE]   (TREE: the checkout whose okvis_amd is used, default this one)
 
-The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py, tests/golden/) are
-those of the checkout the tool itself is in; nothing outside it is read.
+The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py,
+tests/sac_solve_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
+itself is in; nothing outside it is read.
   verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
                       settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
   stand-alone pieces  the same scenes through project_landmarks (and the two camera models the scenes lack), gate_3d2d,
@@ -16,6 +20,13 @@ those of the checkout the tool itself is in; nothing outside it is read.
   descriptor matcher  widths 16 / 32 / 48 / 64 through both matchers, alone and as a batch; the recorded cases of dense_matcher.npz
   RANSAC              the recorded problems of sac_consensus.npz with and without scores, alone and as a batch; bearing_vectors for
                       the four camera models
+  RANSAC solvers      sac_solve over n in {1, 63, 64, 65, 257} correspondences x K in {1, 8, 9} (relative) / {1, 64, 65} (rotation
+                      only) hypotheses x solve only / with consensus / with scores / with essentials, every job alone, all of
+                      them (scored next to unscored, both kinds) as one batch per output setting, and two scored jobs whose
+                      hypotheses stay on the device (models null)
+  propagation         imu_propagate_cases.batch() as one call; every spec alone under flags 0, IMU_COV, IMU_JAC and both
+  keyframe            every family of keyframe_cases.NAMES with and without the hull lists, every job alone and the family as
+                      one call
 """
 import argparse
 import ctypes as C
@@ -27,6 +38,7 @@ import sys
 
 ap = argparse.ArgumentParser()
 ap.add_argument("out")
+ap.add_argument("--cases")
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 args = ap.parse_args()
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,7 +47,10 @@ sys.path.insert(0, os.path.abspath(args.root))
 
 import numpy as np  # noqa: E402
 
+import imu_propagate_cases as IC  # noqa: E402
+import keyframe_cases as KC  # noqa: E402
 import sac_cases  # noqa: E402
+import sac_solve_cases as SSC  # noqa: E402
 import test_gpu_descriptor_matcher as DM  # noqa: E402  (its scene generator and the golden cases)
 import vmatch_scene as SC  # noqa: E402
 from okvis_amd import frontend as F  # noqa: E402
@@ -171,7 +186,98 @@ for model, intr in sorted(BEARING_INTR.items()):
         kp = np.stack([rng.uniform(5, 747, n), rng.uniform(5, 475, n), rng.uniform(4, 30, n)], axis=1).astype(np.float32)
         b, s, ok = fe.bearing_vectors(F.camera(intr, model), kp)
         record(f"bearing_vectors/model{model}_n{n}", bearing=b, sigma=s, ok=ok)
+
+
+def arrays(r):
+    return {k: np.asarray(v) for k, v in r.items()}
+
+
+# sac_solve: n at the ballot-word edges and the edge of a 256-lane tile; K at the SAC_MODEL_TILE edge (relative) and at the 64
+# samples of a wave (rotation only).  sac_solve_cases.case draws samples without repetition, which needs n >= 8: the n = 1 scene
+# is sac_solve_cases.scene with every sample index 0 (hypotheses invalid by rule, the consensus stage still runs over them).
+def solve_case(n, k):
+    if n >= 8:
+        return SSC.case(300 + n, n, k)
+    rng = np.random.default_rng(300 + n)
+    _, _, b1, b2 = SSC.scene(rng, n)
+    return {"bearing1": b1, "bearing2": b2, "sigma1": rng.uniform(0.5e-6, 2e-6, n), "sigma2": rng.uniform(0.5e-6, 2e-6, n),
+            "samples5": np.zeros((k, 8), np.int32), "samples2": np.zeros((k, 2), np.int32), "n": n}
+
+
+SOLVE_N = (1, 63, 64, 65, 257)
+SOLVE_K = {F.SAC_RELATIVE: (1, 8, 9), F.SAC_ROTATION_ONLY: (1, 64, 65)}
+SOLVE_MODES = {"solve_only": (False, False, False), "consensus": (True, False, False), "scores": (True, True, False),
+               "essentials": (True, False, True)}       # (consensus, want_scores, want_essentials)
+
+
+def solve_job(kind, n, k, consensus):
+    make = SSC.relative_job if kind == F.SAC_RELATIVE else SSC.rotation_job
+    return make(solve_case(n, k), consensus=consensus)
+
+
+solve_shapes = [(kind, n, k) for kind in (F.SAC_RELATIVE, F.SAC_ROTATION_ONLY) for n in SOLVE_N for k in SOLVE_K[kind]]
+for mode, (consensus, want_scores, want_essentials) in SOLVE_MODES.items():
+    for kind, n, k in solve_shapes:
+        r, = fe.sac_solve([solve_job(kind, n, k, consensus)], want_scores, want_essentials)
+        record(f"sac_solve/kind{kind}_n{n}_k{k}_{mode}", **arrays(r))
+mixed = [(kind, n, k, consensus) for kind, n, k in solve_shapes for consensus in (False, True)]      # scored next to unscored
+for tag, want_scores, want_essentials in (("plain", False, False), ("scores", True, False), ("essentials", False, True)):
+    for (kind, n, k, consensus), r in zip(mixed, fe.sac_solve([solve_job(*m) for m in mixed], want_scores, want_essentials)):
+        record(f"sac_solve_batch/{tag}_kind{kind}_n{n}_k{k}_consensus{int(consensus)}", **arrays(r))
+for kind, n, k in ((F.SAC_RELATIVE, 65, 9), (F.SAC_ROTATION_ONLY, 257, 65)):     # models null on a scored job: they stay on the device
+    table, keep, (o,) = F.sac_solve_job_table([solve_job(kind, n, k, True)], want_scores=True, want_essentials=True)
+    models = o.pop("models")
+    table[0].models = None
+    fe._call("sac_solve", 1, table)
+    assert not models.any()
+    record(f"sac_solve/kind{kind}_n{n}_k{k}_device_only_models", **o)
+
+# ---------------------------------------------------------------- propagation
+PROP = ("T_WS", "sb", "count", "cov", "jac")
+
+
+def propagate(spec_list):
+    s_t, s_gyr, s_acc, ends, jobs = IC.pool(spec_list)
+    return dict(zip(PROP, fe.imu_propagate(IC.PARAMS, s_t, s_gyr, s_acc, jobs, ends)))
+
+
+record("imu_propagate/batch", **propagate(IC.batch()))
+for spec in IC.specs():
+    for flags in (0, F.IMU_COV, F.IMU_JAC, F.IMU_COV | F.IMU_JAC):
+        record(f"imu_propagate/{spec['name']}_flags{flags}", **propagate([dict(spec, flags=flags)]))
+
+
+# ---------------------------------------------------------------- keyframe decision
+def kf_arrays(r):
+    ims = r["images"]
+    a = {k: np.array([im[k] for im in ims]) for k in ("n_matched", "hull_all_size", "hull_matched_size", "area_all", "area_matched", "n_inside", "flags")}
+    for k in ("hull_all", "hull_matched"):
+        if k in ims[0]:
+            a[k] = np.concatenate([np.asarray(im[k], np.int32) for im in ims])
+    return dict(a, decision=np.uint8(r["decision"]), overlap=np.float64(r["overlap"]), ratio=np.float64(r["ratio"]))
+
+
+for name in KC.NAMES:
+    jobs = KC.cases(name)
+    for want_hulls in (False, True):
+        tag = f"{name}_hulls{int(want_hulls)}"
+        for j, job in enumerate(jobs):
+            r, = fe.keyframe_decision([job], want_hulls)
+            record(f"keyframe/{tag}_job{j}", **kf_arrays(r))
+        for j, r in enumerate(fe.keyframe_decision(jobs, want_hulls)):
+            record(f"keyframe_batch/{tag}_job{j}", **kf_arrays(r))
 fe.close()
 
-json.dump(out, open(args.out, "w"), indent=1, sort_keys=True)
-print(f"{len(out)} cases -> {args.out}: sha256 {hashlib.sha256(open(args.out, 'rb').read()).hexdigest()}")
+if args.cases:
+    json.dump(out, open(args.cases, "w"), indent=1, sort_keys=True)
+groups = {}
+for name in sorted(out):
+    g = groups.setdefault(name.split("/")[0], {"cases": 0, "arrays": 0, "sha256": hashlib.sha256()})
+    g["cases"] += 1
+    for k in sorted(out[name]):
+        g["arrays"] += 1
+        g["sha256"].update(f"{name} {k} {out[name][k]}\n".encode())
+for g in groups.values():
+    g["sha256"] = g["sha256"].hexdigest()
+json.dump(groups, open(args.out, "w"), indent=1, sort_keys=True)
+print(f"{len(out)} cases in {len(groups)} groups -> {args.out}: sha256 {hashlib.sha256(open(args.out, 'rb').read()).hexdigest()}")
