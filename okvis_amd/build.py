@@ -14,13 +14,13 @@ LIB = os.path.join(HERE, "lib", "libokvis_amd_ba.so")
 OBJ_DIR = os.path.join(HERE, "lib", "obj")
 # translation units of the HIP library and the headers each one is rebuilt for
 BA_HEADERS = ["ba_math.hpp", "ba_types.hpp", "ba_device.hpp", "ba_linearize.hpp", "ba_linearize2.hpp", "ba_schur.hpp", "ba_schur2.hpp", "ba_solve.hpp", "ba_chain.hpp", "ba_imu.hpp",
-              "ba_marg.hpp", "ba_marg_tiles.hpp", "ba_chol_tiles.hpp", "ba_cov.hpp", "ba_lmcov.hpp", "ba_predcov.hpp", "ba_ldl16.hpp", "ba_store.hpp", os.path.join("..", "..", "include", "okvis_amd_ba.h"),
+              "ba_marg.hpp", "ba_marg_tiles.hpp", "ba_chol_tiles.hpp", "ba_cov.hpp", "ba_lmcov.hpp", "ba_predcov.hpp", "ba_ldl16.hpp", "ba_store.hpp", "ba_results.hpp", os.path.join("..", "..", "include", "okvis_amd_ba.h"),
               # the parts of ba_capi.hip (one translation unit)
-              "ba_linearize2_lds.inc", "ba_linearize2_phases.inc", "capi_solver.inc", "capi_index_build.inc", "capi_launch.inc", "capi_standalone.inc", "capi_marginalize.inc", "capi_covariance.inc",
+              "ba_linearize2_lds.inc", "ba_linearize2_phases.inc", "capi_solver.inc", "capi_index_build.inc", "capi_launch.inc", "capi_queries.inc", "capi_upload.inc", "capi_standalone.inc", "capi_marginalize.inc", "capi_covariance.inc",
               "capi_landmark_covariance.inc", "capi_predicted_measurement.inc"]
 UNITS = {
     "ba_capi.hip": BA_HEADERS,                                     # the bundle-adjustment path (include/okvis_amd_ba.h)
-    "store_capi.hip": ["ba_store.hpp", os.path.join("..", "..", "include", "okvis_amd_ba.h")],   # host-side window container
+    "store_capi.hip": ["ba_store.hpp", "ba_results.hpp", os.path.join("..", "..", "include", "okvis_amd_ba.h")],   # host-side window container
     "dist_capi.hip": [os.path.join("..", "..", "include", "okvis_amd_ba.h")],   # record all-gather over RCCL (dlopen)
     "fe_capi.hip": ["fe_kernels.hpp", "fe_match.hpp", "fe_sac.hpp", "fe_sac_solve.hpp", "fe_vmatch.hpp", "fe_propagate.hpp", "fe_keyframe.hpp", "ba_math.hpp", os.path.join("..", "..", "include", "okvis_amd_frontend.h"),
                     os.path.join("..", "..", "include", "okvis_amd_ba.h"),

@@ -2010,8 +2010,8 @@ __global__ void imu_take_back_kernel(const WinPtrs* __restrict__ wins) {
   if (threadIdx.x == 0) cp->valid = 0;
 }
 
-// the results of one window in one contiguous record for okvis_ba_fetch_results: pose[7 n_pose] | sb[9 n_sb] | lm[4 n_lm] |
-// quality[n_lm] | reference bias of every IMU factor [9 n_imu]
+// the results of one window in one contiguous record, laid out as ResultsLayout (ba_results.hpp) states it: pose[7 n_pose] | sb[9 n_sb] |
+// lm[4 n_lm] | quality[n_lm] | reference bias of every IMU factor [9 n_imu] | its preintegration record [OKVIS_BA_IMU_CACHE_DOUBLES n_imu]
 __global__ void pack_results_kernel(const WinPtrs* __restrict__ win, int acc) {
   const WinPtrs& W = *win;
   if (acc < 0) acc = W.ctrl->acc;   // (okvis_ba_finish: the host has not read the control record yet)

@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/okvis_amd_ba.h"
+#include "ba_results.hpp"
 
 namespace ba {
 
@@ -492,15 +493,15 @@ struct WindowStore {
     return OKVIS_BA_OK;
   }
 
-  // values of an optimisation written back (packed record of okvis_ba_fetch_results: pose | sb | lm | quality | IMU reference biases)
+  // values of an optimisation written back (the packed results record, ResultsLayout)
   // take_refs: the device has evaluated the IMU terms since the upload (their caches carry the bias they were built at)
   void take_results(const unsigned char* rec, bool take_refs) {
-    const size_t b_pose = 56 * (size_t)n_pose(), b_sb = 72 * (size_t)n_sb(), b_lm = 32 * (size_t)n_lm(), b_q = 8 * (size_t)n_lm();
-    if (b_pose) std::memcpy(pose.data(), rec, b_pose);
-    if (b_sb) std::memcpy(sb.data(), rec + b_pose, b_sb);
-    if (b_lm) std::memcpy(lm.data(), rec + b_pose + b_sb, b_lm);
-    const unsigned char* r = rec + b_pose + b_sb + b_lm + b_q;
-    const unsigned char* rc = r + 72 * imu.size();   // the preintegration records behind the reference biases
+    const ResultsLayout R(n_pose(), n_sb(), n_lm(), (int)imu.size());
+    if (R.pose.bytes) std::memcpy(pose.data(), rec + R.pose.off, R.pose.bytes);
+    if (R.sb.bytes) std::memcpy(sb.data(), rec + R.sb.off, R.sb.bytes);
+    if (R.lm.bytes) std::memcpy(lm.data(), rec + R.lm.off, R.lm.bytes);
+    const unsigned char* r = rec + R.sb_ref.off;
+    const unsigned char* rc = rec + R.caches.off;   // the preintegration records behind the reference biases
     for (size_t f = 0; take_refs && f < imu.size(); ++f) {
       std::memcpy(imu[f].sb_ref, r + 72 * f, 72);
       imu[f].ref_valid = 1;

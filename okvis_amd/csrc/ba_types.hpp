@@ -6,6 +6,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "ba_results.hpp"
+
 namespace ba {
 
 constexpr int GROUP_OBS = 256;       // observations handled by one linearise workgroup (= block size)
@@ -102,9 +104,9 @@ struct ImuCacheD {
 };
 
 static_assert(sizeof(ImuCacheD) == 8 * OKVIS_BA_IMU_CACHE_DOUBLES, "the record okvis_ba_fetch_imu_caches hands out");
-// bytes of the packed results record (pack_results_kernel): pose | speed/bias | landmarks | quality | IMU reference biases | IMU caches
+// bytes of the packed results record (pack_results_kernel; ResultsLayout, ba_results.hpp, is the statement of its layout)
 __host__ __device__ inline size_t results_bytes(int n_pose, int n_sb, int n_lm, int n_imu) {
-  return 56 * (size_t)n_pose + 72 * (size_t)n_sb + 40 * (size_t)n_lm + (72 + sizeof(ImuCacheD)) * (size_t)(n_imu > 0 ? n_imu : 0);
+  return ResultsLayout(n_pose, n_sb, n_lm, n_imu).total;
 }
 
 // layout of WinPtrs::dec (doubles)
@@ -296,7 +298,7 @@ struct alignas(64) WinPtrs {
   BA_G double* Dp2;            // [D]
   BA_G double* Hpp;            // [D][D] undamped U (debug/parity), optional
   BA_G double* quality;        // [n_lm]
-  BA_G double* results;        // [7 n_pose + 9 n_sb + 4 n_lm + n_lm + 9 n_imu] packed by pack_results_kernel for okvis_ba_fetch_results
+  BA_G double* results;        // [ResultsLayout::total bytes, ba_results.hpp: pose | sb | lm | quality | IMU reference biases | preintegration records] packed by pack_results_kernel
   BA_G double* prof;           // [64] clock64() phase stamps of workgroup 0 (diagnostics)
   BA_G Ctrl* ctrl;
 

@@ -22,11 +22,11 @@ struct CovAssembly {
 
 // (okvis_ba_begin starts from the accepted buffers as the host knows them)
 int cov_refresh_acc(okvis_ba_solver* s) {
-  if (s->acc_fresh) return OKVIS_BA_OK;
+  if (s->host.acc_fresh) return OKVIS_BA_OK;
   std::vector<Ctrl> cs;
   if (int rc = fetch_ctrl(s, cs)) return rc;
   for (size_t i = 0; i < s->wins.size(); ++i) s->wins[i].acc = cs[i].acc & 1;
-  s->acc_fresh = true;
+  s->host.acc_read();
   return OKVIS_BA_OK;
 }
 
@@ -62,15 +62,14 @@ int cov_assemble_and_run(okvis_ba_solver* s, int w0, int n, unsigned char* d, co
   HIP_TRY(hipEventRecord(ev_begin, s->stream));
   hipLaunchKernelGGL(cov_keep_kernel, dim3((unsigned)nw), dim3(256), 0, s->stream, s->d_wins, d_keep, ca.keep_stride, ca.max_imu, 0);
   HIP_TRY(hipGetLastError());
-  struct HostFlags {
+  struct KeepHostView {   // (okvis_ba_begin tramples the host's view; the call leaves it as it found it, not begun)
     okvis_ba_solver* s;
-    bool evaluated, res_staged, acc_fresh, mirror_fresh;
-    long long slots;
-    ~HostFlags() {
-      s->begun = false;
-      s->evaluated = evaluated, s->res_staged = res_staged, s->acc_fresh = acc_fresh, s->mirror_fresh = mirror_fresh, s->slots = slots;
+    HostView kept;
+    ~KeepHostView() {
+      s->host = kept;
+      s->host.not_begun();
     }
-  } host_flags{s, s->evaluated, s->res_staged, s->acc_fresh, s->mirror_fresh, s->slots};
+  } keep_host_view{s, s->host};
   int rc;
   {
     MargSwapOptions swap_options{s, s->d_opt};
@@ -126,7 +125,7 @@ int cov_win_init(const HostWin& H, const CovTaps& out, CovWin& J) {
 template <class Spec, class Result, class Job, class Check>
 int cov_enter(okvis_ba_solver* s, int w0, int n, const Spec* specs, Result* results, std::vector<Job>& jobs, Check check) {
   if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
-  if (!s->uploaded || s->begun || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+  if (!s->host.uploaded || s->host.begun || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
   if (n <= 0 || w0 < 0 || (int64_t)w0 + n > (int64_t)s->wins.size()) return OKVIS_BA_ERR_ARG;
   jobs.resize((size_t)n);
   for (int i = 0; i < n; ++i)

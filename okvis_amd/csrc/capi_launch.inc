@@ -373,7 +373,7 @@ hipError_t launch_iterations_forked(okvis_ba_solver* s, int n, int budget, bool 
 
 // the accepted-buffer index lives on the device while iterations are in flight: read it back
 int refresh_acc(okvis_ba_solver* s, int w) {
-  if (s->acc_fresh) return OKVIS_BA_OK;   // read by okvis_ba_finish / set at upload, nothing launched since
+  if (s->host.acc_fresh) return OKVIS_BA_OK;   // read by okvis_ba_finish / set at upload, nothing launched since
   int acc = 0;
   HIP_TRY(hipMemcpyAsync(&acc, &s->wins[w].ptrs.ctrl->acc, sizeof(int), hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
@@ -437,7 +437,7 @@ int resume_paused(okvis_ba_solver* s, const std::vector<Ctrl>& cs, int* n_paused
     *n_paused += b.nw;
     w0 = w1;
   }
-  s->slots += most;
+  s->host.slots_add(most);
   return OKVIS_BA_OK;
 }
 

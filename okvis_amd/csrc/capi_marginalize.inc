@@ -319,9 +319,9 @@ int marg_hand_over(okvis_ba_solver* s, const okvis_ba_solver::MargPending::Item&
 // The first half of a call for windows w0 .. w0 + n - 1: everything is enqueued, the kept blocks are reported.  `batch`: which of
 // the two _end entries ends it.
 int marg_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* specs, okvis_ba_marg_result* results, bool batch) {
-  if (s) s->acc_fresh = false;
+  if (s) s->host.work_enqueued();
   if (!s || !specs || !results) return OKVIS_BA_ERR_ARG;
-  if (!s->uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
+  if (!s->host.uploaded || s->marg_pending.active) return OKVIS_BA_ERR_STATE;
   if (n <= 0 || w0 < 0 || (int64_t)w0 + n > (int64_t)s->wins.size()) return OKVIS_BA_ERR_ARG;
   // every window's arguments before anything is enqueued
   std::vector<MargJob> jobs((size_t)n);
@@ -373,7 +373,7 @@ int marg_begin(okvis_ba_solver* s, int w0, int n, const okvis_ba_marg_spec* spec
   // ---- linearise + landmark elimination + export: one launch each for the range ----
   int rc = okvis_ba_begin(s);
   if (rc != OKVIS_BA_OK) return rc;
-  s->begun = false;
+  s->host.not_begun();
   HIP_TRY(schur_and_export(s, w0, n, d_wins, any_small));
   // ---- the dense tail: a workgroup per window, one launch per run of consecutive windows on the LDS route (a range of the
   //      pipeline's sizes is one run) ----
@@ -446,7 +446,7 @@ int marg_end(okvis_ba_solver* s, okvis_ba_marg_result* results, bool batch) {
     if (rc == OKVIS_BA_OK) rc = r;
   }
   if (rc != OKVIS_BA_OK) return rc;
-  s->acc_fresh = true;
+  s->host.acc_read();
   return OKVIS_BA_OK;
 }
 

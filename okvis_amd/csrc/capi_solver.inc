@@ -1,6 +1,8 @@
 // Part of ba_capi.hip (one translation unit; included there, in this order: capi_solver.inc, capi_index_build.inc, capi_launch.inc,
-// then the entry points, capi_standalone.inc and capi_marginalize.inc inside its extern "C" block).
-// The solver record: host copies of what queries need, the staging allocator, the arena, okvis_ba_solver, the diagnostics word.
+// then the entry points with capi_queries.inc and capi_upload.inc, capi_standalone.inc, capi_marginalize.inc and the covariance parts
+// inside its extern "C" block).
+// The solver record: host copies of what queries need, the staging allocator, the arena, the host view (HostView), okvis_ba_solver,
+// the entry guard (enter), the diagnostics word.
 namespace {
 
 #define HIP_TRY(expr)                                              \
@@ -136,6 +138,34 @@ struct LaunchPlan : PlanFixed {
 // which uses three) or cov_pose_kernel | behind the item kernel and the taps (the two-stage entries).
 struct CovEvents { hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr}; };
 
+// What the host believes about the device.  The members are read everywhere and written HERE only: every entry that changes one
+// calls a transition, and DESIGN.md (section 4c) tabulates which entry calls which.  A stale res_staged or acc_fresh does not
+// crash, it hands out the previous frame's values, so a new member belongs in this record (okvis_ba_state_covariance and its
+// siblings keep and restore the record as a whole).
+struct HostView {
+  bool uploaded = false, begun = false;
+  bool evaluated = false;      // okvis_ba_begin ran since the last upload: every IMU term's cache has been (re)built
+  bool acc_fresh = false;      // HostWin::acc mirrors the device's accepted-buffer index (no kernel launched since it was read)
+  bool res_staged = false;     // stage_res holds window 0's packed results as of the last okvis_ba_finish (single-window solvers)
+  bool mirror_fresh = false;   // the containers hold the values the device holds (nothing optimised / set since)
+  long long slots = 0;         // launch slots (schur + solve + linearise triples) since okvis_ba_begin: diagnostics (ARR_DIAG_SLOTS)
+
+  void upload_started() { uploaded = false, begun = false; }
+  void upload_done() { uploaded = true, evaluated = false, res_staged = false, acc_fresh = true; }   // Ctrl starts zeroed: accepted buffer 0, like HostWin::acc
+  void containers_match(bool yes) { mirror_fresh = yes; }    // taken from the caller / refreshed from the device / lost
+  void values_set() { begun = false, res_staged = mirror_fresh = false; }                // okvis_ba_set_state
+  void prior_values_replaced() { begun = false, evaluated = false, res_staged = false; } // okvis_ba_set_marg_prior_values
+  void work_enqueued() { acc_fresh = false; }                                            // a kernel may move the accepted buffer
+  void begin_entered() { acc_fresh = res_staged = mirror_fresh = false; }                // okvis_ba_begin, before its own checks
+  void slots_restart() { slots = 0; }
+  void slots_add(long long n) { slots += n; }
+  void begin_done() { begun = true, evaluated = true; }
+  void not_begun() { begun = false; }   // okvis_ba_begin was called for its linearisation alone (marginalisation, covariance)
+  void iterations_enqueued() { mirror_fresh = false; }   // (a container refreshed between begin and finish is behind again)
+  void finish_done(bool staged) { res_staged = staged, begun = false, acc_fresh = true, mirror_fresh = false; }
+  void acc_read() { acc_fresh = true; }   // every window's accepted-buffer index was just read back
+};
+
 struct okvis_ba_solver {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -155,7 +185,7 @@ struct okvis_ba_solver {
   StageVec stage_dl;             // pinned staging of result downloads (okvis_ba_marginalize[_batch]: every window's numbers, one copy)
   StageVec stage, stage_small;   // pinned staging of the arena's data part / of the WinPtrs + OptD records (kept across uploads)
   std::vector<HostWin> wins;
-  bool uploaded = false, begun = false;
+  HostView host;       // what the host believes about the device: written through its transitions only
   BatchLayout layout;   // of the uploaded batch
   BatchMax max;
   LaunchPlan plan;      // (upload, set_options)
@@ -169,10 +199,7 @@ struct okvis_ba_solver {
   std::vector<WindowStore> mirrors;
   WindowStore mirror_edit;   // okvis_ba_patch_window edits a copy: this one
   long marg_tiles_fallbacks = 0;   // windows of okvis_ba_marginalize[_batch] calls whose tiled tail gave way to the single workgroup (diagnostics)
-  bool evaluated = false;      // okvis_ba_begin ran since the last upload: every IMU term's cache has been (re)built
-  bool mirror_fresh = false;   // the containers hold the values the device holds (nothing optimised / set since)
-  bool res_staged = false;  // stage_res holds window 0's packed results as of the last okvis_ba_finish (single-window solvers)
-  StageVec stage_res;
+  StageVec stage_res;   // window 0's packed results as of the last okvis_ba_finish (HostView::res_staged)
   StageVec stage_marg;           // host-written part of okvis_ba_marginalize's scratch block
   StageVec stage_marg_vals;      // okvis_ba_set_marg_prior_values: the staged J | H0 | e0 span ...
   hipEvent_t ev_marg_vals = nullptr;   // ... and the event behind its copy
@@ -191,10 +218,8 @@ struct okvis_ba_solver {
   } marg_pending;
   StageVec stage_pre;            // first preintegrations started at upload (imu_pre_kernel): the staged block and its device copy
   unsigned char* d_pre = nullptr;   // (PRE_MAX_TERMS records)
-  bool acc_fresh = false;   // HostWin::acc mirrors the device's accepted-buffer index (no kernel launched since it was read)
   long long stagger_ticks = 0;   // start offset between consecutive sub-batch streams (wall_clock64 ticks, 100 MHz); okvis_ba_tuning::stagger_us
   bool skip_topup = false;   // okvis_ba_optimize_timed ran out of time: finish() must not grant the slots mis-speculated steps still owe
-  long long slots = 0;   // launch slots (schur + solve + linearise triples) since okvis_ba_begin: diagnostics (array 96)
   // captured graphs, keyed on the call length and the route (graph_key, capi_launch.inc); per sub-batch: (key, sub) -> its chain's graph
   std::map<int, hipGraphExec_t> graphs;
   std::map<std::pair<int, int>, hipGraphExec_t> sub_graphs;
@@ -215,6 +240,49 @@ struct okvis_ba_solver {
 };
 
 namespace {
+
+// okvis_ba_marginalize_end / _batch_end first: between the two halves of a marginalisation the solver takes no edits and hands out
+// no results
+#define REFUSE_BETWEEN_MARG_HALVES(s) do { if ((s) && (s)->marg_pending.active) return OKVIS_BA_ERR_STATE; } while (0)
+
+// The entry guard: what an entry requires of the solver before it does anything, as a word of these.  The statuses and their
+// precedence are part of the ABI (tests/test_gpu_entry_status.py pins them), so an entry's oddity is a bit here and not a second
+// copy of the checks.  In this order:
+//   ENTER_MARG_FIRST   between the halves of a marginalisation: ERR_STATE, even for arguments that are ERR_ARG otherwise
+//   (always)           a null solver, or `ptrs_ok` false (the entry's required pointers and counts): ERR_ARG
+//   ENTER_UPLOADED     no upload: ERR_STATE - ERR_ARG with ENTER_UPLOAD_IS_ARG (okvis_ba_array_size, okvis_ba_download, ...)
+//   ENTER_NO_MARG      between the halves: ERR_STATE, behind the pointers (okvis_ba_set_marg_prior_values)
+//   ENTER_BEGUN        not between okvis_ba_begin and okvis_ba_finish: ERR_STATE;  `state_ok` false (the entry's own): ERR_STATE
+//   ENTER_WINDOW       w outside the uploaded windows: ERR_ARG
+//   ENTER_PTRS_LAST    `ptrs_ok` is looked at here and not with the null solver (okvis_ba_fetch_imu_caches)
+//   ENTER_DEVICE       hipSetDevice
+enum : unsigned {
+  ENTER_MARG_FIRST = 1, ENTER_UPLOADED = 2, ENTER_UPLOAD_IS_ARG = 4, ENTER_NO_MARG = 8, ENTER_BEGUN = 16, ENTER_WINDOW = 32,
+  ENTER_PTRS_LAST = 64, ENTER_DEVICE = 128,
+  ENTER_RESULTS = ENTER_MARG_FIRST | ENTER_UPLOADED | ENTER_WINDOW | ENTER_DEVICE   // state get / set and the fetches
+};
+int enter(okvis_ba_solver* s, unsigned need, int w = 0, bool ptrs_ok = true, bool state_ok = true) {
+  if (need & ENTER_MARG_FIRST) REFUSE_BETWEEN_MARG_HALVES(s);
+  if (!s || (!ptrs_ok && !(need & ENTER_PTRS_LAST))) return OKVIS_BA_ERR_ARG;
+  const bool no_upload = (need & ENTER_UPLOADED) && !s->host.uploaded;
+  if (no_upload && (need & ENTER_UPLOAD_IS_ARG)) return OKVIS_BA_ERR_ARG;
+  if (no_upload || ((need & ENTER_NO_MARG) && s->marg_pending.active) || ((need & ENTER_BEGUN) && !s->host.begun) || !state_ok)
+    return OKVIS_BA_ERR_STATE;
+  if ((need & ENTER_WINDOW) && (w < 0 || w >= (int)s->wins.size())) return OKVIS_BA_ERR_ARG;
+  if (!ptrs_ok) return OKVIS_BA_ERR_ARG;
+  if (need & ENTER_DEVICE) HIP_TRY(hipSetDevice(s->device));
+  return OKVIS_BA_OK;
+}
+
+// staging bytes lent to a call go back to their keeper whatever happens (on = false: the call keeps its own)
+struct GiveBack {
+  StageVec& a;
+  StageVec& b;
+  bool on = true;
+  ~GiveBack() {
+    if (on) a.swap(b);
+  }
+};
 
 int cov_events_create(okvis_ba_solver* s, CovEvents& ev) {   // (lazily, by the entry's first call)
   for (auto& e : ev.e)
