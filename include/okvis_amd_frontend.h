@@ -36,8 +36,12 @@
  *                                of many problems per call, chained into the consensus kernel: sample indices in, inlier sets out.
  *                                Stated from their published definitions, not pinned to OpenGV
  *
- * The generalised P3P of runRansac3d2d, the sampler and the RANSAC loop are OpenGV's and are not here: okvis_fe_sac_consensus takes
- * its hypotheses from the caller, okvis_fe_sac_solve its samples.
+ *   okvis_fe_sac_solve_absolute  the minimal solver of runRansac3d2d (generalised three-point absolute pose over several cameras) for all
+ *                                samples of many problems per call, chained into the consensus kernel in the same way.  Stated from
+ *                                its mathematical definition, not pinned to OpenGV
+ *
+ * The sampler, the RANSAC loop and optimizeModelCoefficients are OpenGV's and are not here: okvis_fe_sac_consensus takes its
+ * hypotheses from the caller, okvis_fe_sac_solve and okvis_fe_sac_solve_absolute their samples.
  *
  * and the state propagation that every layer around the backend calls:
  *
@@ -325,8 +329,69 @@ typedef struct okvis_fe_sac_solve_job { /* one 2D-2D sample-consensus problem wi
  * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or required pointer (bearing1, bearing2
  * for n > 0, samples), a negative count, n or n_models out of range, an unknown kind or OKVIS_FE_SAC_ABSOLUTE, a sample index
  * outside 0..n-1 (so n = 0 has no valid sample), NULL sigma1 or sigma2 while a consensus output is wanted.  n_jobs = 0 is valid.
- * What is not here: the generalised P3P of runRansac3d2d, the sampler, the loop. */
+ * What is not here: the sampler, the loop.  The generalised P3P of runRansac3d2d is okvis_fe_sac_solve_absolute. */
 int okvis_fe_sac_solve(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_solve_job* jobs);
+
+#define OKVIS_FE_SAC_SAMPLE_ABSOLUTE 4    /* correspondences per sample: 3 that define the candidates + 1 that picks the pose */
+#define OKVIS_FE_SAC_MAX_ROOTS_ABSOLUTE 8 /* real solutions of three quadrics in three depths                                 */
+
+typedef struct okvis_fe_sac_absolute_job { /* one 3D-2D sample-consensus problem with its samples: hypotheses are solved for, then scored */
+  int32_t n;         /* correspondences, 0..65536     */
+  int32_t n_models;  /* samples = hypotheses, 1..1024 */
+  int32_t n_cams;    /* 1..8                          */
+  int32_t reserved;  /* 0                             */
+  double threshold;
+  /* exactly the absolute inputs of okvis_fe_sac_job, same meaning and layout */
+  const double* points;        /* [n][3]                                     */
+  const double* bearing;       /* [n][3]                                     */
+  const double* sigma;         /* [n]; read only when something is scored    */
+  const int32_t* cam_index;    /* [n]         0..n_cams-1                    */
+  const double* cam_offsets;   /* [n_cams][3]                                */
+  const double* cam_rotations; /* [n_cams][9] row-major                      */
+  const int32_t* samples;      /* [n_models][4], indices into 0..n-1         */
+  /* out, hypotheses; each may be NULL */
+  double* models;     /* [n_models][12] row-major 3x4 transformation_t, the layout okvis_fe_sac_job.models takes; every entry of an
+                         invalid hypothesis is a quiet NaN                                                                      */
+  uint8_t* valid;     /* [n_models]                                                                                            */
+  int32_t* n_roots;   /* referee: candidates found, 0..8                                                                       */
+  double* candidates; /* referee: [n_models][8][12], the first n_roots written (in no stated order), the rest quiet NaNs       */
+  /* out, consensus: exactly the five fields of okvis_fe_sac_job with the same meaning; all NULL = no scoring launch */
+  int32_t *counts, *best, *n_inliers, *inliers;
+  double* scores;
+} okvis_fe_sac_absolute_job;
+
+/* The minimal solver of Frontend::runRansac3d2d (okvis_frontend/src/Frontend.cpp:575-642: FrameAbsolutePoseSacProblem with
+ * Algorithm::GP3P) for all samples of many problems in one call, chained into the consensus kernel of okvis_fe_sac_consensus:
+ * sample indices in, hypotheses and inlier sets out.  OpenGV's gp3p is generated Groebner-basis code and OpenGV's source is not
+ * part of the reference tree: the solver is stated from its mathematical definition and is NOT pinned to OpenGV.
+ * Convention (the consensus entry's): a hypothesis (R, t) takes a body point to the world, X = R p + t.
+ *   inputs       sample (i0, i1, i2, i3); for k = 0..2: c_k = cam_offsets[cam_index[i_k]], d_k = cam_rotations[cam_index[i_k]]
+ *                bearing[i_k], X_k = points[i_k].
+ *   invalid      up front when two of the four indices are equal, or (X_1 - X_0) x (X_2 - X_0) has a zero or non-finite norm.
+ *   candidates   all real (l0, l1, l2), every l_k > 0, with |(c_a + l_a d_a) - (c_b + l_b d_b)|^2 = |X_a - X_b|^2 for the pairs
+ *                (0,1), (0,2), (1,2): three quadrics in three unknowns, at most eight.  With p_k = c_k + l_k d_k the candidate is the
+ *                proper rigid transformation that takes the p_k to the X_k: a1 = (X_1 - X_0) / |.|, a2 = (a1 x (X_2 - X_0)) / |.|,
+ *                a3 = a1 x a2; b1, b2, b3 alike from the p_k (the frames of the rotation-only solver above);
+ *                R(r,c) = (a1[r] b1[c] + a2[r] b2[c]) + a3[r] b3[c], t = X_0 - R p_0.
+ *   hypothesis   the candidate with the smallest |reprojection - bearing|^2 of correspondence i3 (the absolute score of
+ *                okvis_fe_sac_consensus without the division by sigma); invalid when there is no candidate.  Positive depths are
+ *                the rule of the relative solver above on its ray parameters.
+ *   central      all three correspondences from one camera, or n_cams = 1: the same definition through the same code.
+ *                The route: the resultant of the two quadrics that share l0, reduced modulo the third to one polynomial of degree
+ *                eight in l1; its roots over all of l1 > 0 (on [0, 1] in l1 and on [0, 1] in 1 / l1: no bound on the scene is
+ *                assumed) by the derivative chain of the relative solver; l0 and l2 from their quadratics; Newton on the three
+ *                quadrics themselves; the frames.  Every loop has a compile-time count and the result is deterministic.
+ *                tests/sac_abs_statement.py states the definition at 60 digits and tests/sac_abs_cases.py the bound the
+ *                hypotheses are held to.
+ * One staging copy in, one solver launch for all jobs, one launch of the consensus kernel when any consensus output is asked for
+ * (it reads the hypotheses where the solver left them in device memory, and the points, bearings and cameras as staged once), one
+ * copy back.  An invalid hypothesis scores NaN and counts 0, as for okvis_fe_sac_solve.
+ * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or table, a negative count, n, n_models or
+ * n_cams out of range, a NULL required input (samples always; points, bearing, cam_index, cam_offsets, cam_rotations for n > 0), a
+ * cam_index outside 0..n_cams-1, a sample index outside 0..n-1 (so n = 0 has no valid sample), NULL sigma while a consensus
+ * output is wanted.  n_jobs = 0 is valid.
+ * What is not here: the sampler, the loop, optimizeModelCoefficients. */
+int okvis_fe_sac_solve_absolute(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_absolute_job* jobs);
 
 #define OKVIS_FE_IMU_COV 1 /* the 15x15 covariance of the propagated state is wanted */
 #define OKVIS_FE_IMU_JAC 2 /* the 15x15 Jacobian of the propagated state is wanted   */

@@ -19,6 +19,7 @@
 #include "fe_match.hpp"
 #include "fe_sac.hpp"
 #include "fe_sac_solve.hpp"
+#include "fe_sac_gp3p.hpp"
 #include "fe_vmatch.hpp"
 #include "fe_propagate.hpp"
 #include "fe_keyframe.hpp"

@@ -1,7 +1,7 @@
 // Part of fe_capi.hip (one translation unit).  Bearing vectors, consensus scoring and the minimal solvers in front of it.  The
 // consensus stage (what a scored job adds to the launch, its device record, the launch, Ransac::computeModel's book-keeping) is
-// written once and serves okvis_fe_sac_consensus and okvis_fe_sac_solve, templated on the job type where the fields carry the
-// same names.
+// written once and serves okvis_fe_sac_consensus, okvis_fe_sac_solve and okvis_fe_sac_solve_absolute, templated on the job type
+// where the fields carry the same names.
 namespace {
 
 // What the scored jobs of a call take of sac_consensus_kernel's grid and of its two result arrays, summed job by job: the sums
@@ -271,6 +271,107 @@ int okvis_fe_sac_solve(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_sac_s
     const Plan& p = plan[j];
     if (J.models) st.get(p.models, J.models);
     st.get(p.valid, J.valid), st.get(p.n_roots, J.n_roots), st.get(p.essentials, J.essentials);
+    if (p.scored) sac_book_keeping(st, at, s_counts, s_ballots, J, p.scores);
+  }
+  return OKVIS_BA_OK;
+}
+
+// The 3D-2D solver in front of the consensus kernel, as okvis_fe_sac_solve: one staging copy in, sac_gp3p_kernel for all jobs, the
+// consensus stage on the hypotheses where the solver left them and on the points, bearings and cameras as the solver read them,
+// one copy back.
+int okvis_fe_sac_solve_absolute(okvis_fe_context* c, int32_t n_jobs, const okvis_fe_sac_absolute_job* jobs) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && !jobs)) return OKVIS_BA_ERR_ARG;
+  if (n_jobs == 0) return OKVIS_BA_OK;
+  struct Plan {
+    Staged<double> a, b, s1, s2, cams, models, candidates, scores;  // a: points, b: bearings, s1: sigma, s2: never on
+    Staged<int32_t> ci, samples, n_roots;
+    Staged<uint8_t> valid;
+    bool scored = false;  // a consensus output is asked for
+  };
+  struct Head {  // what push_sac_job reads of a job
+    double threshold;
+    int32_t kind, n, n_models;
+  };
+  std::vector<Plan> plan((size_t)n_jobs);
+  size_t solve_blocks = 0;
+  SacSum total;  // of the scored jobs
+  const auto job_solve_blocks = [](const okvis_fe_sac_absolute_job& J) { return ((size_t)J.n_models + fe::GP3_PER_WAVE - 1) / fe::GP3_PER_WAVE; };
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_absolute_job& J = jobs[j];
+    if (J.n < 0 || J.n > fe::SAC_MAX_N || J.n_models < 1 || J.n_models > fe::SAC_MAX_MODELS || J.n_cams < 1 || J.n_cams > fe::SAC_MAX_CAMS ||
+        !J.samples || (J.n > 0 && (!J.points || !J.bearing || !J.cam_index || !J.cam_offsets || !J.cam_rotations)))
+      return OKVIS_BA_ERR_ARG;
+    plan[j].scored = J.counts || J.best || J.n_inliers || J.inliers || J.scores;
+    if (plan[j].scored && !J.sigma) return OKVIS_BA_ERR_ARG;
+    for (int i = 0; i < J.n; ++i)
+      if (J.cam_index[i] < 0 || J.cam_index[i] >= J.n_cams) return OKVIS_BA_ERR_ARG;
+    for (size_t i = 0; i < (size_t)OKVIS_FE_SAC_SAMPLE_ABSOLUTE * (size_t)J.n_models; ++i)
+      if (J.samples[i] < 0 || J.samples[i] >= J.n) return OKVIS_BA_ERR_ARG;  // n = 0 ends here: every job past this line has n >= 1
+    solve_blocks += job_solve_blocks(J);
+    if (plan[j].scored) total.add(J.n, J.n_models);
+  }
+  if (solve_blocks > (size_t)INT32_MAX || !total.launchable()) return OKVIS_BA_ERR_ARG;
+  FE_TRY(hipSetDevice(c->device));
+  Stage st{c};
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_absolute_job& J = jobs[j];
+    Plan& p = plan[j];
+    const size_t n = (size_t)J.n;
+    p.a = st.in<double>(3 * n), p.b = st.in<double>(3 * n), p.s1 = st.in<double>(n, J.sigma != nullptr);
+    p.ci = st.in<int32_t>(n), p.cams = st.in<double>(12 * (size_t)J.n_cams);
+    p.samples = st.in<int32_t>((size_t)J.n_models * OKVIS_FE_SAC_SAMPLE_ABSOLUTE);
+  }
+  const auto s_solve = st.in<fe::Gp3Job>((size_t)n_jobs);
+  const auto s_table = st.in<fe::SacJob>(total.jobs, total.jobs > 0);
+  for (int j = 0; j < n_jobs; ++j)  // hypotheses the caller does not take stay on the device
+    if (!jobs[j].models) plan[j].models = st.scratch<double>(12 * (size_t)jobs[j].n_models);
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_absolute_job& J = jobs[j];
+    if (J.models) plan[j].models = st.out<double>(12 * (size_t)J.n_models);
+    plan[j].valid = st.out<uint8_t>((size_t)J.n_models, J.valid != nullptr);
+    plan[j].n_roots = st.out<int32_t>((size_t)J.n_models, J.n_roots != nullptr);
+    plan[j].candidates = st.out<double>(12 * (size_t)fe::GP3_MAX_ROOTS * (size_t)J.n_models, J.candidates != nullptr);
+  }
+  const auto s_counts = st.out<int32_t>(total.counts, total.jobs > 0);
+  const auto s_ballots = st.out<unsigned long long>(total.words, total.jobs > 0);
+  for (int j = 0; j < n_jobs; ++j) plan[j].scores = st.out<double>((size_t)jobs[j].n_models * (size_t)jobs[j].n, jobs[j].scores != nullptr);
+  if (int rc = st.reserve()) return rc;
+  fe::Gp3Job* solve_table = st.host(s_solve);
+  fe::SacJob* table = st.host(s_table);
+  size_t solve_block0 = 0;
+  SacSum at;
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_absolute_job& J = jobs[j];
+    const Plan& p = plan[j];
+    put_transposed(st, p.a, J.points), put_transposed(st, p.b, J.bearing);  // as the consensus kernel reads them
+    st.put(p.s1, J.sigma), st.put(p.ci, J.cam_index), st.put(p.samples, J.samples);
+    double* cams = st.host(p.cams);
+    for (int k = 0; k < J.n_cams; ++k) {
+      std::copy_n(J.cam_offsets + 3 * k, 3, cams + 12 * k);
+      std::copy_n(J.cam_rotations + 9 * k, 9, cams + 12 * k + 3);
+    }
+    fe::Gp3Job S;
+    S.points = st.dev(p.a), S.bearing = st.dev(p.b), S.cam_index = st.dev(p.ci), S.cams = st.dev(p.cams), S.samples = st.dev(p.samples);
+    S.models = st.dev(p.models), S.valid = st.dev(p.valid), S.n_roots = st.dev(p.n_roots), S.candidates = st.dev(p.candidates);
+    S.n = J.n, S.n_models = J.n_models, S.block0 = (int32_t)solve_block0;
+    solve_table[j] = S;
+    solve_block0 += job_solve_blocks(J);
+    if (p.scored) push_sac_job(st, table, at, Head{J.threshold, OKVIS_FE_SAC_ABSOLUTE, J.n, J.n_models}, p, st.dev(p.ci), st.dev(p.cams));
+  }
+  if (int rc = st.upload()) return rc;
+  fe::Gp3Params GP;
+  GP.jobs = st.dev(s_solve), GP.n_jobs = n_jobs;
+  hipLaunchKernelGGL(fe::sac_gp3p_kernel, dim3((unsigned)solve_blocks), dim3(64), 0, c->stream, GP);  // writes every candidate slot: NaN past n_roots
+  FE_TRY(hipGetLastError());
+  if (total.jobs > 0)
+    if (int rc = launch_consensus(st, s_table, total, s_counts, s_ballots)) return rc;
+  if (int rc = st.download()) return rc;
+  at = SacSum();
+  for (int j = 0; j < n_jobs; ++j) {
+    const okvis_fe_sac_absolute_job& J = jobs[j];
+    const Plan& p = plan[j];
+    if (J.models) st.get(p.models, J.models);
+    st.get(p.valid, J.valid), st.get(p.n_roots, J.n_roots), st.get(p.candidates, J.candidates);
     if (p.scored) sac_book_keeping(st, at, s_counts, s_ballots, J, p.scores);
   }
   return OKVIS_BA_OK;

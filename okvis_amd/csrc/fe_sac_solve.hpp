@@ -243,6 +243,33 @@ BA_HD double sac5_horner(const double* q, double x) {
   return s;
 }
 
+// The root of the polynomial qs of degree D (ascending) on [a, b] when its sign changes there: SAC5_BISECT bisection steps, then
+// SAC5_NEWTON guarded Newton steps.  *found = the sign changes; without one the result is not meant to be used.
+template <int D>
+BA_HD double sac_interval_root(const double* qs, double a, double b, bool* found) {
+  BA_NO_CONTRACT
+  double q[D + 1], dq[D];
+#pragma unroll
+  for (int j = 0; j <= D; ++j) q[j] = qs[j];
+#pragma unroll
+  for (int j = 0; j < D; ++j) dq[j] = (double)(j + 1) * q[j + 1];
+  const bool fa = sac5_horner<D>(q, a) > 0.0, fb = sac5_horner<D>(q, b) > 0.0;
+  double lo = a, hi = b;
+  for (int it = 0; it < SAC5_BISECT; ++it) {
+    const double mid = 0.5 * (lo + hi);
+    const bool fm = sac5_horner<D>(q, mid) > 0.0;
+    if (fm == fa) lo = mid;
+    else hi = mid;
+  }
+  double x = 0.5 * (lo + hi);
+  for (int it = 0; it < SAC5_NEWTON; ++it) {
+    const double xn = x - sac5_horner<D>(q, x) / sac5_horner<D - 1>(dq, x);
+    if (xn > lo && xn < hi) x = xn;
+  }
+  *found = fa != fb;
+  return x;
+}
+
 // One level of the root isolation: the polynomial of degree D of each team's chain on the intervals between the D + 1 points of
 // the level below (pin), one interval per lane.  An interval without a sign change hands its left end on (an interval of width
 // zero one level up: harmless).  Writes D + 2 points (pout) and the flags.
@@ -255,26 +282,9 @@ BA_HD void sac5_level(double* slab, int lane, int stride) {
     const double* qs = slab + SV_POLY + 66 * team + SV_OFF(D);
     const double* pin = slab + SV_PTS + 24 * team + 12 * (D & 1);
     double* pout = slab + SV_PTS + 24 * team + 12 * ((D + 1) & 1);
-    double q[D + 1], dq[D];
-#pragma unroll
-    for (int j = 0; j <= D; ++j) q[j] = qs[j];
-#pragma unroll
-    for (int j = 0; j < D; ++j) dq[j] = (double)(j + 1) * q[j + 1];
-    const double a = pin[i], b = pin[i + 1];
-    const bool fa = sac5_horner<D>(q, a) > 0.0, fb = sac5_horner<D>(q, b) > 0.0;
-    double lo = a, hi = b;
-    for (int it = 0; it < SAC5_BISECT; ++it) {
-      const double mid = 0.5 * (lo + hi);
-      const bool fm = sac5_horner<D>(q, mid) > 0.0;
-      if (fm == fa) lo = mid;
-      else hi = mid;
-    }
-    double x = 0.5 * (lo + hi);
-    for (int it = 0; it < SAC5_NEWTON; ++it) {
-      const double xn = x - sac5_horner<D>(q, x) / sac5_horner<D - 1>(dq, x);
-      if (xn > lo && xn < hi) x = xn;
-    }
-    const bool found = fa != fb;
+    const double a = pin[i];
+    bool found;
+    const double x = sac_interval_root<D>(qs, a, pin[i + 1], &found);
     pout[i + 1] = found ? x : a;
     slab[SV_FLAG + 12 * team + i] = found ? 1.0 : 0.0;
     if (i == 0) pout[0] = -1.0, pout[D + 1] = 1.0;

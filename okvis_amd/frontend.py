@@ -1,7 +1,8 @@
 """ctypes view of include/okvis_amd_frontend.h: the batched reprojection pieces of the OKVIS frontend (stereo triangulation
 with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
 best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the outlier rejection
-behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems), the IMU state
+behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems, the generalised
+three-point solver of the 3D-2D problem), the IMU state
 propagation with covariance and Jacobian and the keyframe decision (exact hulls, areas and inside counts) on the MI355X.  No CPU
 path."""
 from __future__ import annotations
@@ -19,10 +20,11 @@ GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
            "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
-           "okvis_fe_sac_solve"]
+           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
+SAC_SAMPLE_ABSOLUTE, SAC_MAX_ROOTS_ABSOLUTE = 4, 8
 IMU_COV, IMU_JAC = 1, 2
 KF_FEW_POINTS, KF_FEW_MATCHES = 1, 2
 KF_MAX_KEYPOINTS, KF_MAX_CAMS = 8192, 8
@@ -66,6 +68,15 @@ class SacSolveJobC(C.Structure):
                 ("samples", C.c_void_p), ("models", C.c_void_p), ("valid", C.c_void_p), ("n_roots", C.c_void_p),
                 ("essentials", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p),
                 ("inliers", C.c_void_p), ("scores", C.c_void_p)]
+
+
+class SacAbsoluteJobC(C.Structure):
+    """okvis_fe_sac_absolute_job"""
+    _fields_ = [("n", C.c_int32), ("n_models", C.c_int32), ("n_cams", C.c_int32), ("reserved", C.c_int32), ("threshold", C.c_double),
+                ("points", C.c_void_p), ("bearing", C.c_void_p), ("sigma", C.c_void_p), ("cam_index", C.c_void_p),
+                ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("samples", C.c_void_p), ("models", C.c_void_p),
+                ("valid", C.c_void_p), ("n_roots", C.c_void_p), ("candidates", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p),
+                ("n_inliers", C.c_void_p), ("inliers", C.c_void_p), ("scores", C.c_void_p)]
 
 
 class ImuJobC(C.Structure):
@@ -142,6 +153,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_bearing_vectors.argtypes = [vp, cam, i32, vp, vp, vp, vp]
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
         L.okvis_fe_sac_solve.argtypes = [vp, i32, C.POINTER(SacSolveJobC)]
+        L.okvis_fe_sac_solve_absolute.argtypes = [vp, i32, C.POINTER(SacAbsoluteJobC)]
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
         L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
@@ -328,6 +340,28 @@ class Frontend:
                 k = int(o["scalars"][1])
                 r.update(counts=o["counts"], best=int(o["scalars"][0]), n_inliers=k, inliers=o["inliers"][:k].copy())
             for name in ("scores", "n_roots", "essentials"):
+                if name in o:
+                    r[name] = o[name]
+            res.append(r)
+        return res
+
+    def sac_solve_absolute(self, jobs, want_scores=False, want_candidates=False):
+        """The minimal solver of the 3D-2D outlier rejection (generalised three-point absolute pose) in front of sac_consensus, all
+        jobs in one call.  jobs: dicts with points, bearing [n][3], cam_index [n], cam_offsets [c][3], cam_rotations [c][3][3] as
+        sac_consensus takes them, samples [K][4] (three that define the candidates, one more that picks the pose), threshold
+        (default 9), sigma [n] (may be left out of a job with consensus=False), consensus (default True: score the hypotheses).
+        -> per job a dict: models [K][3][4] (body to world; NaN where invalid), valid [K] bool; with consensus counts, best,
+        n_inliers, inliers as sac_consensus returns them, and scores [K][n] under want_scores; under want_candidates also n_roots
+        [K] and candidates [K][8][3][4] (NaN past n_roots)."""
+        table, keep, out = sac_absolute_job_table(jobs, want_scores, want_candidates)
+        self._call("sac_solve_absolute", len(jobs), table)
+        res = []
+        for o in out:
+            r = {"models": o["models"], "valid": o["valid"].astype(bool)}
+            if "counts" in o:
+                k = int(o["scalars"][1])
+                r.update(counts=o["counts"], best=int(o["scalars"][0]), n_inliers=k, inliers=o["inliers"][:k].copy())
+            for name in ("scores", "n_roots", "candidates"):
                 if name in o:
                     r[name] = o[name]
             res.append(r)
@@ -535,6 +569,41 @@ def sac_solve_job_table(jobs, want_scores=False, want_essentials=False):
         if relative and want_essentials:
             o["n_roots"], o["essentials"] = np.zeros(K, np.int32), np.zeros((K, SAC_MAX_ROOTS, 9))
             t.n_roots, t.essentials = o["n_roots"].ctypes.data, o["essentials"].ctypes.data
+        if job.get("consensus", True):
+            o["counts"], o["scalars"], o["inliers"] = np.zeros(K, np.int32), np.zeros(2, np.int32), np.zeros(max(n, 1), np.int32)
+            t.counts, t.best, t.n_inliers = o["counts"].ctypes.data, o["scalars"].ctypes.data, o["scalars"].ctypes.data + 4
+            t.inliers = o["inliers"].ctypes.data
+            if want_scores:
+                o["scores"] = np.zeros((K, n))
+                t.scores = o["scores"].ctypes.data
+        out.append(o)
+    return table, keep, out
+
+
+def sac_absolute_job_table(jobs, want_scores=False, want_candidates=False):
+    """-> (okvis_fe_sac_absolute_job array, the input arrays it points into, per job the dict of output arrays); both lists have to
+    outlive the call"""
+    keep, out = [], []
+    table = (SacAbsoluteJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        a, b = _f64(job["points"]).reshape(-1, 3), _f64(job["bearing"]).reshape(-1, 3)
+        ci = np.ascontiguousarray(job["cam_index"], np.int32).reshape(-1)
+        off, rot = _f64(job["cam_offsets"]).reshape(-1, 3), _f64(job["cam_rotations"]).reshape(-1, 9)
+        q = np.ascontiguousarray(job["samples"], np.int32).reshape(-1, SAC_SAMPLE_ABSOLUTE)
+        s = None if job.get("sigma") is None else _f64(job["sigma"]).reshape(-1)
+        if not (len(a) == len(b) == len(ci)) or len(off) != len(rot) or (s is not None and len(s) != len(a)):
+            raise ValueError("arrays of different lengths")
+        n, K = len(a), len(q)
+        t = table[j]
+        t.n, t.n_models, t.n_cams, t.threshold = n, K, len(off), float(job.get("threshold", 9.0))
+        t.points, t.bearing, t.sigma, t.cam_index = a.ctypes.data, b.ctypes.data, _ptr(s), ci.ctypes.data
+        t.cam_offsets, t.cam_rotations, t.samples = off.ctypes.data, rot.ctypes.data, q.ctypes.data
+        keep.append((a, b, s, ci, off, rot, q))
+        o = {"models": np.zeros((K, 3, 4)), "valid": np.zeros(K, np.uint8)}
+        t.models, t.valid = o["models"].ctypes.data, o["valid"].ctypes.data
+        if want_candidates:
+            o["n_roots"], o["candidates"] = np.zeros(K, np.int32), np.zeros((K, SAC_MAX_ROOTS_ABSOLUTE, 3, 4))
+            t.n_roots, t.candidates = o["n_roots"].ctypes.data, o["candidates"].ctypes.data
         if job.get("consensus", True):
             o["counts"], o["scalars"], o["inliers"] = np.zeros(K, np.int32), np.zeros(2, np.int32), np.zeros(max(n, 1), np.int32)
             t.counts, t.best, t.n_inliers = o["counts"].ctypes.data, o["scalars"].ctypes.data, o["scalars"].ctypes.data + 4

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry (the thirteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
+Every okvis_fe_* entry (the fourteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
 every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
 in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
 whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
@@ -10,7 +10,7 @@ group differs, --cases FILE writes the hash of every array of every case (some 1
     python tools/fe_digest.py OUT.json [--root TREE] [--cases FILE]   (TREE: the checkout whose okvis_amd is used, default this one)
 
 The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py,
-tests/sac_solve_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
+tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
 itself is in; nothing outside it is read.
   verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
                       settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
@@ -24,6 +24,10 @@ itself is in; nothing outside it is read.
                       only) hypotheses x solve only / with consensus / with scores / with essentials, every job alone, all of
                       them (scored next to unscored, both kinds) as one batch per output setting, and two scored jobs whose
                       hypotheses stay on the device (models null)
+  RANSAC absolute solver  sac_solve_absolute over n in {4, 63, 64, 65, 257} correspondences x K in {1, 3, 4, 5, 9} samples (the four
+                      samples of a wave, the eight hypotheses of a consensus tile) x 1, 2 and 8 cameras x solve only / with consensus /
+                      with scores / with candidates, every job alone, all of them (scored next to unscored) as one batch per output
+                      setting, and a scored job whose hypotheses stay on the device (models null)
   propagation         imu_propagate_cases.batch() as one call; every spec alone under flags 0, IMU_COV, IMU_JAC and both
   keyframe            every family of keyframe_cases.NAMES with and without the hull lists, every job alone and the family as
                       one call
@@ -49,6 +53,7 @@ import numpy as np  # noqa: E402
 
 import imu_propagate_cases as IC  # noqa: E402
 import keyframe_cases as KC  # noqa: E402
+import sac_abs_cases as SAC  # noqa: E402
 import sac_cases  # noqa: E402
 import sac_solve_cases as SSC  # noqa: E402
 import test_gpu_descriptor_matcher as DM  # noqa: E402  (its scene generator and the golden cases)
@@ -231,6 +236,38 @@ for kind, n, k in ((F.SAC_RELATIVE, 65, 9), (F.SAC_ROTATION_ONLY, 257, 65)):    
     fe._call("sac_solve", 1, table)
     assert not models.any()
     record(f"sac_solve/kind{kind}_n{n}_k{k}_device_only_models", **o)
+
+# ---------------------------------------------------------------- RANSAC absolute solver
+# sac_solve_absolute: n at the ballot-word edges and the edge of a 256-lane tile (4: the least a sample needs); K at the four
+# samples of a wave and at the SAC_MODEL_TILE edge; the central problem, two cameras, and eight with the outer two in use
+ABS_N = (4, 63, 64, 65, 257)
+ABS_K = (1, 3, 4, 5, 9)
+ABS_CAMS = ((1, None), (2, None), (8, (0, 7)))
+ABS_MODES = {"solve_only": (False, False, False), "consensus": (True, False, False), "scores": (True, True, False),
+             "candidates": (True, False, True)}       # (consensus, want_scores, want_candidates)
+
+
+def abs_job(n, k, cams, consensus):
+    c = SAC.case(500 + n, n, 130, cams[0], False, cams[1])
+    q = c["samples"][:k] if n > 4 else np.repeat(c["samples"], k, axis=0)
+    return SAC.job(c, q, consensus=consensus)
+
+
+abs_shapes = [(n, k, cams) for n in ABS_N for k in ABS_K for cams in ABS_CAMS]
+for mode, (consensus, want_scores, want_candidates) in ABS_MODES.items():
+    for n, k, cams in abs_shapes:
+        r, = fe.sac_solve_absolute([abs_job(n, k, cams, consensus)], want_scores, want_candidates)
+        record(f"sac_solve_absolute/cams{cams[0]}_n{n}_k{k}_{mode}", **arrays(r))
+mixed = [(n, k, cams, consensus) for n, k, cams in abs_shapes for consensus in (False, True)]      # scored next to unscored
+for tag, want_scores, want_candidates in (("plain", False, False), ("scores", True, False), ("candidates", False, True)):
+    for (n, k, cams, consensus), r in zip(mixed, fe.sac_solve_absolute([abs_job(*m) for m in mixed], want_scores, want_candidates)):
+        record(f"sac_solve_absolute_batch/{tag}_cams{cams[0]}_n{n}_k{k}_consensus{int(consensus)}", **arrays(r))
+table, keep, (o,) = F.sac_absolute_job_table([abs_job(257, 9, ABS_CAMS[1], True)], want_scores=True, want_candidates=True)
+models = o.pop("models")      # models null on a scored job: they stay on the device
+table[0].models = None
+fe._call("sac_solve_absolute", 1, table)
+assert not models.any()
+record("sac_solve_absolute/cams2_n257_k9_device_only_models", **o)
 
 # ---------------------------------------------------------------- propagation
 PROP = ("T_WS", "sb", "count", "cov", "jac")
