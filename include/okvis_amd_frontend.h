@@ -40,8 +40,13 @@
  *                                samples of many problems per call, chained into the consensus kernel in the same way.  Stated from
  *                                its mathematical definition, not pinned to OpenGV
  *
- * The sampler, the RANSAC loop and optimizeModelCoefficients are OpenGV's and are not here: okvis_fe_sac_consensus takes its
- * hypotheses from the caller, okvis_fe_sac_solve and okvis_fe_sac_solve_absolute their samples.
+ *   okvis_fe_ransac              whole sample-consensus runs (opengv::sac::Ransac<P>::computeModel as runRansac3d2d / runRansac2d2d call
+ *                                it): the sampler and the adaptive loop on the device around the three solvers and the consensus kernel,
+ *                                all runs of a frame in one call, correspondences in, inlier set and model out.  Stated in this header,
+ *                                not pinned to OpenGV
+ *
+ * optimizeModelCoefficients is OpenGV's and is not here (the reference's frontend never calls it).  okvis_fe_sac_consensus takes its
+ * hypotheses from the caller, okvis_fe_sac_solve and okvis_fe_sac_solve_absolute their samples; okvis_fe_ransac draws its own.
  *
  * and the state propagation that every layer around the backend calls:
  *
@@ -274,7 +279,8 @@ typedef struct okvis_fe_sac_job { /* one sample-consensus problem with its hypot
  *                  pinned to reference lines; everything around it is.
  * One launch and one copy back per call: the device returns the counts and one 64-bit inlier ballot per (hypothesis, 64
  * correspondences); best and inliers are read off them on the host.  A cam_index entry outside 0..n_cams-1 is OKVIS_BA_ERR_ARG.
- * What is not here: the minimal solvers, the sampler, the loop (see INTEGRATION.md for the recipe). */
+ * What is not here: the minimal solvers (okvis_fe_sac_solve, okvis_fe_sac_solve_absolute) and the sampler and the loop around them
+ * (okvis_fe_ransac); see INTEGRATION.md for the recipe. */
 int okvis_fe_sac_consensus(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_job* jobs);
 
 #define OKVIS_FE_SAC_SAMPLE_ROTATION_ONLY 2 /* correspondences per sample of a rotation-only job                        */
@@ -329,7 +335,8 @@ typedef struct okvis_fe_sac_solve_job { /* one 2D-2D sample-consensus problem wi
  * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or required pointer (bearing1, bearing2
  * for n > 0, samples), a negative count, n or n_models out of range, an unknown kind or OKVIS_FE_SAC_ABSOLUTE, a sample index
  * outside 0..n-1 (so n = 0 has no valid sample), NULL sigma1 or sigma2 while a consensus output is wanted.  n_jobs = 0 is valid.
- * What is not here: the sampler, the loop.  The generalised P3P of runRansac3d2d is okvis_fe_sac_solve_absolute. */
+ * The sampler and the loop around this entry are okvis_fe_ransac; the generalised P3P of runRansac3d2d is okvis_fe_sac_solve_absolute.
+ * What is not here: optimizeModelCoefficients. */
 int okvis_fe_sac_solve(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_solve_job* jobs);
 
 #define OKVIS_FE_SAC_SAMPLE_ABSOLUTE 4    /* correspondences per sample: 3 that define the candidates + 1 that picks the pose */
@@ -390,8 +397,90 @@ typedef struct okvis_fe_sac_absolute_job { /* one 3D-2D sample-consensus problem
  * n_cams out of range, a NULL required input (samples always; points, bearing, cam_index, cam_offsets, cam_rotations for n > 0), a
  * cam_index outside 0..n_cams-1, a sample index outside 0..n-1 (so n = 0 has no valid sample), NULL sigma while a consensus
  * output is wanted.  n_jobs = 0 is valid.
- * What is not here: the sampler, the loop, optimizeModelCoefficients. */
+ * The sampler and the loop around this entry are okvis_fe_ransac.  What is not here: optimizeModelCoefficients. */
 int okvis_fe_sac_solve_absolute(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_sac_absolute_job* jobs);
+
+#define OKVIS_FE_RANSAC_STOP_CONVERGED 0      /* the adaptive bound was met                                                  */
+#define OKVIS_FE_RANSAC_STOP_MAX_ITERATIONS 1 /* iterations went past max_iterations                                         */
+#define OKVIS_FE_RANSAC_STOP_EXHAUSTED 2      /* the n_slots sample slots ran out before the loop stopped                    */
+#define OKVIS_FE_RANSAC_STOP_SKIPS 3          /* 10 * max_iterations samples without a hypothesis                            */
+#define OKVIS_FE_RANSAC_STOP_NO_SAMPLE 4      /* n is below the sample size: nothing was drawn                               */
+
+typedef struct okvis_fe_ransac_job { /* one whole sample-consensus run: correspondences in, inlier set and model out */
+  int32_t kind;           /* OKVIS_FE_SAC_*, mixed freely within a call                                       */
+  int32_t n;              /* correspondences, 0..65536                                                        */
+  int32_t n_slots;        /* sample slots solved speculatively, 1..1024                                       */
+  int32_t n_cams;         /* absolute: 1..8                                                                   */
+  int32_t max_iterations; /* >= 1; the reference uses 50                                                      */
+  int32_t reserved;       /* 0                                                                                */
+  double threshold;       /* the reference uses 9                                                             */
+  double probability;     /* strictly inside (0, 1); the reference uses 0.99                                  */
+  uint64_t seed;
+  /* the input arrays of okvis_fe_sac_job for the kind, same meaning and layout */
+  const double* points;
+  const double* bearing;
+  const double* sigma;
+  const int32_t* cam_index;
+  const double* cam_offsets;
+  const double* cam_rotations;
+  const double *bearing1, *bearing2;
+  const double *sigma1, *sigma2;
+  /* out, each may be NULL */
+  int32_t* best;       /* the slot of the returned hypothesis, or -1                                                        */
+  int32_t* n_inliers;  /* its count, 0 when best = -1                                                                       */
+  int32_t* inliers;    /* [n], the first n_inliers written, ascending                                                       */
+  double* model;       /* [12] row-major 3x4, or the first 9 (row-major 3x3) of a rotation-only job; quiet NaNs when best = -1 */
+  int32_t* iterations; /* valid slots the loop consumed                                                                     */
+  int32_t* skipped;    /* invalid slots the loop consumed                                                                   */
+  int32_t* stop;       /* OKVIS_FE_RANSAC_STOP_*                                                                            */
+  /* out, for referees; each may be NULL; not written when n is below the sample size */
+  int32_t* samples; /* [n_slots][s]                                                                                         */
+  uint8_t* valid;   /* [n_slots]                                                                                            */
+  int32_t* counts;  /* [n_slots]                                                                                            */
+  double* models;   /* [n_slots][9] rotation only / [n_slots][12]                                                            */
+} okvis_fe_ransac_job;
+
+/* opengv::sac::Ransac<P>::computeModel as Frontend::runRansac3d2d / runRansac2d2d call it (okvis_frontend/src/Frontend.cpp:599-611,
+ * 677-703), for all sample-consensus runs of a frame in one call: many sequences, the three problem kinds mixed.  OpenGV's source is
+ * not part of the reference tree (oracle/shim/callers/opengv/sac/Ransac.hpp is declarations only): like the solvers, the sampler
+ * and the loop are stated here and are NOT pinned to OpenGV.  s is the kind's OKVIS_FE_SAC_SAMPLE_* constant: 2, 8 or 4.
+ *   sampler   slot m of a job with seed S: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57, Weyl constants 0x9E3779B9,
+ *             0xBB67AE85) under the key (S mod 2^32, S >> 32); u_0..u_3 = the output for counter (m, 0, 0, 0), u_4..u_7 for
+ *             (m, 1, 0, 0).  With the virtual array A[i] = i, for k = 0..s-1: j = k + ((uint64)u_k * (uint64)(n - k) >> 32); swap
+ *             A[k] and A[j]; sample[k] = A[k] (a sparse Fisher-Yates).  The indices are distinct and in range by construction, the
+ *             draw is uniform up to n / 2^32, and it depends on (S, m, n, s) only, never on the batch around the job.
+ *   slots     slot m's hypothesis is the solver of okvis_fe_sac_solve / okvis_fe_sac_solve_absolute on sample m, its count that of
+ *             okvis_fe_sac_consensus under `threshold`: the same kernels, unchanged.  All n_slots slots are solved and scored
+ *             speculatively; the loop decides which of them the sequential loop would have reached.
+ *   loop      it = 0; skipped = 0; best = -1; best_count = -1; stop = EXHAUSTED
+ *             for m = 0 .. n_slots-1:
+ *                 if !valid[m]: skipped += 1
+ *                               if skipped >= 10 * max_iterations: stop = SKIPS; break
+ *                               continue
+ *                 if counts[m] > best_count: best = m; best_count = counts[m]
+ *                 it += 1
+ *                 if done(it, best_count): stop = CONVERGED; break
+ *                 if it > max_iterations:  stop = MAX_ITERATIONS; break
+ *   done      the adaptive bound it >= log(1 - p) / log(1 - w^s) without transcendental functions, in IEEE double, every
+ *             operation rounded on its own: w = (double)c / (double)n; ws = w multiplied by w a further s-1 times; q = 1.0 - ws,
+ *             clamped to [2^-52, 1 - 2^-52]; r = q^it by binary powering from the least significant bit of it (r = 1, b = q; per
+ *             bit: if (e & 1) r = r * b; b = b * b; e >>= 1); done = r <= 1.0 - p.  A hypothesis with count 0 never satisfies
+ *             done, so the loop may run max_iterations + 1 iterations (it stops on it > max_iterations, after the iteration).
+ *   result    iterations = it; n_inliers = best_count (0 when best = -1); inliers = the correspondences with score < threshold
+ *             under hypothesis best, ascending; model = hypothesis best.
+ * n below s is not an error: nothing is launched for the job, best = -1, n_inliers = 0, iterations = 0, skipped = 0,
+ * stop = NO_SAMPLE, model = quiet NaNs.
+ * One staging copy in; sac_sample_kernel for all jobs; sac_solve_kernel for the 2D-2D jobs; sac_gp3p_kernel for the absolute jobs;
+ * one sac_consensus_kernel launch over all jobs; sac_loop_kernel (one wave per job); one copy back.  No sample index crosses the
+ * bus unless `samples` asks for it; counts, valid, ballots and hypotheses stay on the device unless a referee output asks for
+ * them: without referee outputs the copy back holds the per-job record, the model and the inlier lists only.
+ * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or table, a negative job count, an unknown
+ * kind, n outside 0..65536, n_slots outside 1..1024, max_iterations < 1, probability not strictly inside (0, 1), for n > 0 a NULL
+ * input of the kind (absolute: points, bearing, sigma, cam_index, cam_offsets, cam_rotations; the others: bearing1, bearing2,
+ * sigma1, sigma2), for an absolute job n_cams outside 1..8 or a cam_index outside 0..n_cams-1.  n_jobs = 0 is valid.
+ * What is not here: optimizeModelCoefficients (the reference's frontend never calls it); the bearing vectors are a call of their
+ * own (okvis_fe_bearing_vectors). */
+int okvis_fe_ransac(okvis_fe_context* ctx, int32_t n_jobs, const okvis_fe_ransac_job* jobs);
 
 #define OKVIS_FE_IMU_COV 1 /* the 15x15 covariance of the propagated state is wanted */
 #define OKVIS_FE_IMU_JAC 2 /* the 15x15 Jacobian of the propagated state is wanted   */

@@ -23,6 +23,7 @@
 #include "fe_vmatch.hpp"
 #include "fe_propagate.hpp"
 #include "fe_keyframe.hpp"
+#include "fe_sac_loop.hpp"
 
 struct okvis_fe_context {
   int device = 0;
@@ -168,3 +169,4 @@ void okvis_fe_destroy(okvis_fe_context* c) {
 #include "fe_capi_ransac.inc"         // bearing vectors, the consensus stage, consensus scoring, the minimal solvers
 #include "fe_capi_propagation.inc"    // IMU state propagation
 #include "fe_capi_keyframe.inc"       // the keyframe decision
+#include "fe_capi_ransac_loop.inc"    // whole RANSAC runs: the sampler and the loop around the solvers and the consensus stage

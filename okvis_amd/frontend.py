@@ -2,7 +2,7 @@
 with uncertainty, 3D-2D projection and chi-square gating), its descriptor matching (Hamming candidates, the dense matcher's
 best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the outlier rejection
 behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems, the generalised
-three-point solver of the 3D-2D problem), the IMU state
+three-point solver of the 3D-2D problem, and whole RANSAC runs with the sampler and the adaptive loop on the device), the IMU state
 propagation with covariance and Jacobian and the keyframe decision (exact hulls, areas and inside counts) on the MI355X.  No CPU
 path."""
 from __future__ import annotations
@@ -20,11 +20,13 @@ GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
            "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
-           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute"]
+           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
 SAC_SAMPLE_ABSOLUTE, SAC_MAX_ROOTS_ABSOLUTE = 4, 8
+SAC_SAMPLE_SIZE = {SAC_ABSOLUTE: SAC_SAMPLE_ABSOLUTE, SAC_ROTATION_ONLY: SAC_SAMPLE_ROTATION_ONLY, SAC_RELATIVE: SAC_SAMPLE_RELATIVE}
+RANSAC_STOP_CONVERGED, RANSAC_STOP_MAX_ITERATIONS, RANSAC_STOP_EXHAUSTED, RANSAC_STOP_SKIPS, RANSAC_STOP_NO_SAMPLE = range(5)
 IMU_COV, IMU_JAC = 1, 2
 KF_FEW_POINTS, KF_FEW_MATCHES = 1, 2
 KF_MAX_KEYPOINTS, KF_MAX_CAMS = 8192, 8
@@ -77,6 +79,17 @@ class SacAbsoluteJobC(C.Structure):
                 ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("samples", C.c_void_p), ("models", C.c_void_p),
                 ("valid", C.c_void_p), ("n_roots", C.c_void_p), ("candidates", C.c_void_p), ("counts", C.c_void_p), ("best", C.c_void_p),
                 ("n_inliers", C.c_void_p), ("inliers", C.c_void_p), ("scores", C.c_void_p)]
+
+
+class RansacJobC(C.Structure):
+    """okvis_fe_ransac_job"""
+    _fields_ = [("kind", C.c_int32), ("n", C.c_int32), ("n_slots", C.c_int32), ("n_cams", C.c_int32), ("max_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("threshold", C.c_double), ("probability", C.c_double), ("seed", C.c_uint64),
+                ("points", C.c_void_p), ("bearing", C.c_void_p), ("sigma", C.c_void_p), ("cam_index", C.c_void_p),
+                ("cam_offsets", C.c_void_p), ("cam_rotations", C.c_void_p), ("bearing1", C.c_void_p), ("bearing2", C.c_void_p),
+                ("sigma1", C.c_void_p), ("sigma2", C.c_void_p), ("best", C.c_void_p), ("n_inliers", C.c_void_p), ("inliers", C.c_void_p),
+                ("model", C.c_void_p), ("iterations", C.c_void_p), ("skipped", C.c_void_p), ("stop", C.c_void_p), ("samples", C.c_void_p),
+                ("valid", C.c_void_p), ("counts", C.c_void_p), ("models", C.c_void_p)]
 
 
 class ImuJobC(C.Structure):
@@ -154,6 +167,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_sac_consensus.argtypes = [vp, i32, C.POINTER(SacJobC)]
         L.okvis_fe_sac_solve.argtypes = [vp, i32, C.POINTER(SacSolveJobC)]
         L.okvis_fe_sac_solve_absolute.argtypes = [vp, i32, C.POINTER(SacAbsoluteJobC)]
+        L.okvis_fe_ransac.argtypes = [vp, i32, C.POINTER(RansacJobC)]
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
         L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
@@ -367,6 +381,17 @@ class Frontend:
             res.append(r)
         return res
 
+    def ransac(self, jobs, want_referee=False):
+        """Whole sample-consensus runs, all jobs in one call: the device draws the samples, solves and scores every slot and
+        applies the loop's rule.  jobs: dicts with kind (SAC_*), the input arrays sac_consensus takes for the kind, and optionally
+        n_slots (default 64), max_iterations (50), threshold (9), probability (0.99), seed (0).
+        -> per job a dict: best (slot, or -1), n_inliers, inliers [n_inliers] int32 (ascending), model [3][4] / [3][3] (NaN when
+        best = -1), iterations, skipped, stop (RANSAC_STOP_*); under want_referee also samples [n_slots][s], valid [n_slots] bool,
+        counts [n_slots], models [n_slots][3][4] / [n_slots][3][3] (left as zeros where n is below the sample size)."""
+        table, keep, out = ransac_job_table(jobs, want_referee)
+        self._call("ransac", len(jobs), table)
+        return [ransac_result(o) for o in out]
+
     def imu_propagate(self, params, s_t, s_gyr, s_acc, jobs, ends, fill=np.nan):
         """ImuError::propagation for the chains of calls of many sequences, in one call.  params: a list of ImuParams (or
         ImuParamsC); s_t [n] int64 ns, s_gyr / s_acc [n][3]: the pool of samples; ends [m] int64 ns: the pool of end times; jobs:
@@ -541,6 +566,80 @@ def sac_job_table(jobs, want_scores=False):
         t.scores = _ptr(sc)
         out.append((counts, scalars, inl, sc))
     return table, keep, out
+
+
+RANSAC_SCALARS = ("best", "n_inliers", "iterations", "skipped", "stop")
+
+
+def ransac_job_table(jobs, want_referee=False):
+    """-> (okvis_fe_ransac_job array, the input arrays it points into, per job the dict of output arrays); both lists have to
+    outlive the call"""
+    keep, out = [], []
+    table = (RansacJobC * max(1, len(jobs)))()
+    for j, job in enumerate(jobs):
+        kind = int(job["kind"])
+        if kind not in (SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE):
+            raise ValueError("kind is one of SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE")
+        t = table[j]
+        t.kind, t.n_slots, t.max_iterations = kind, int(job.get("n_slots", 64)), int(job.get("max_iterations", 50))
+        t.threshold, t.probability, t.seed = float(job.get("threshold", 9.0)), float(job.get("probability", 0.99)), int(job.get("seed", 0))
+        if kind == SAC_ABSOLUTE:
+            a, b = _f64(job["points"]).reshape(-1, 3), _f64(job["bearing"]).reshape(-1, 3)
+            s1, ci = _f64(job["sigma"]).reshape(-1), np.ascontiguousarray(job["cam_index"], np.int32).reshape(-1)
+            off, rot = _f64(job["cam_offsets"]).reshape(-1, 3), _f64(job["cam_rotations"]).reshape(-1, 9)
+            if not (len(a) == len(b) == len(s1) == len(ci)) or len(off) != len(rot):
+                raise ValueError("arrays of different lengths")
+            t.n, t.n_cams = len(a), len(off)
+            t.points, t.bearing, t.sigma, t.cam_index = a.ctypes.data, b.ctypes.data, s1.ctypes.data, ci.ctypes.data
+            t.cam_offsets, t.cam_rotations = off.ctypes.data, rot.ctypes.data
+            keep.append((a, b, s1, ci, off, rot))
+        else:
+            a, b = _f64(job["bearing1"]).reshape(-1, 3), _f64(job["bearing2"]).reshape(-1, 3)
+            s1, s2 = _f64(job["sigma1"]).reshape(-1), _f64(job["sigma2"]).reshape(-1)
+            if not (len(a) == len(b) == len(s1) == len(s2)):
+                raise ValueError("arrays of different lengths")
+            t.n = len(a)
+            t.bearing1, t.bearing2, t.sigma1, t.sigma2 = a.ctypes.data, b.ctypes.data, s1.ctypes.data, s2.ctypes.data
+            keep.append((a, b, s1, s2))
+        n, K, cols = t.n, t.n_slots, 3 if kind == SAC_ROTATION_ONLY else 4
+        o = {"scalars": np.zeros(len(RANSAC_SCALARS), np.int32), "inliers": np.zeros(max(n, 1), np.int32), "model": np.zeros((3, cols))}
+        for i, name in enumerate(RANSAC_SCALARS):
+            setattr(t, name, o["scalars"].ctypes.data + 4 * i)
+        t.inliers, t.model = o["inliers"].ctypes.data, o["model"].ctypes.data
+        if want_referee:
+            o.update(samples=np.zeros((max(K, 0), SAC_SAMPLE_SIZE[kind]), np.int32), valid=np.zeros(max(K, 0), np.uint8),
+                     counts=np.zeros(max(K, 0), np.int32), models=np.zeros((max(K, 0), 3, cols)))
+            for name in ("samples", "valid", "counts", "models"):
+                setattr(t, name, o[name].ctypes.data)
+        out.append(o)
+    return table, keep, out
+
+
+def ransac_result(o):
+    """the filled arrays of one job of ransac_job_table as the dict Frontend.ransac returns"""
+    r = {name: int(o["scalars"][i]) for i, name in enumerate(RANSAC_SCALARS)}
+    r.update(inliers=o["inliers"][:r["n_inliers"]].copy(), model=o["model"])
+    for name in ("samples", "counts", "models"):
+        if name in o:
+            r[name] = o[name]
+    if "valid" in o:
+        r["valid"] = o["valid"].astype(bool)
+    return r
+
+
+def ransac_2d2d_outcome(n, rotation_only_inliers, rel_pose_inliers):
+    """What Frontend::runRansac2d2d makes of its two runs (okvis_frontend/src/Frontend.cpp:688-733), with its `float` ratios.
+    n: the number of correspondences (n >= 1); the two arguments: the inlier counts of the rotation-only and of the relative-pose
+    run.  -> dict: rotation_only_ratio, rel_pose_ratio (float32), rotation_only (the rotation-only ratio is larger than the
+    relative-pose ratio or above 0.8), rotation_only_success, rel_pose_success (more than 10 inliers, and the respective choice),
+    inliers_from ("rotation_only", "rel_pose" or None: whose inlier set decides which observations are removed)."""
+    n, k_rot, k_rel = int(n), int(rotation_only_inliers), int(rel_pose_inliers)
+    r_rot, r_rel = np.float32(k_rot) / np.float32(n), np.float32(k_rel) / np.float32(n)
+    rotation_only = bool(r_rot > r_rel or float(r_rot) > 0.8)     # :711 compares the float with the double literal: 4 / 5 passes
+    rot_success = bool(rotation_only and k_rot > 10)
+    rel_success = bool(not rotation_only and k_rel > 10)
+    return {"rotation_only_ratio": r_rot, "rel_pose_ratio": r_rel, "rotation_only": rotation_only, "rotation_only_success": rot_success,
+            "rel_pose_success": rel_success, "inliers_from": "rotation_only" if rot_success else "rel_pose" if rel_success else None}
 
 
 def sac_solve_job_table(jobs, want_scores=False, want_essentials=False):

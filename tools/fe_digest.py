@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry (the fourteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
+Every okvis_fe_* entry (the fifteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
 every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
 in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
 whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
@@ -10,7 +10,7 @@ group differs, --cases FILE writes the hash of every array of every case (some 1
     python tools/fe_digest.py OUT.json [--root TREE] [--cases FILE]   (TREE: the checkout whose okvis_amd is used, default this one)
 
 The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py,
-tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
+tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/ransac_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
 itself is in; nothing outside it is read.
   verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
                       settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
@@ -28,6 +28,10 @@ itself is in; nothing outside it is read.
                       samples of a wave, the eight hypotheses of a consensus tile) x 1, 2 and 8 cameras x solve only / with consensus /
                       with scores / with candidates, every job alone, all of them (scored next to unscored) as one batch per output
                       setting, and a scored job whose hypotheses stay on the device (models null)
+  RANSAC loop         ransac over n in {s-1, s, 63, 64, 65, 257} correspondences x {1, 5, 8, 9, 64, 65} sample slots x the three
+                      kinds on scenes with a third of the second bearings swapped, with and without the referee outputs, every
+                      job alone and all of them as one mixed batch; the three end-to-end scenes.  Left out where the tree under
+                      --root is from before the entry
   propagation         imu_propagate_cases.batch() as one call; every spec alone under flags 0, IMU_COV, IMU_JAC and both
   keyframe            every family of keyframe_cases.NAMES with and without the hull lists, every job alone and the family as
                       one call
@@ -53,6 +57,7 @@ import numpy as np  # noqa: E402
 
 import imu_propagate_cases as IC  # noqa: E402
 import keyframe_cases as KC  # noqa: E402
+import ransac_cases as RC  # noqa: E402
 import sac_abs_cases as SAC  # noqa: E402
 import sac_cases  # noqa: E402
 import sac_solve_cases as SSC  # noqa: E402
@@ -268,6 +273,29 @@ table[0].models = None
 fe._call("sac_solve_absolute", 1, table)
 assert not models.any()
 record("sac_solve_absolute/cams2_n257_k9_device_only_models", **o)
+
+# ---------------------------------------------------------------- RANSAC loop
+# ransac: n below the sample size, at it, at the ballot-word edges and the edge of a 256-lane tile; slots at the consensus tile,
+# the four samples of a three-point wave and the 64 lanes of the loop's wave; scenes with a third of the second bearings swapped
+RANSAC_N = (-1, 0, 63, 64, 65, 257)          # offsets from the sample size below 63
+RANSAC_SLOTS = (1, 5, 8, 9, 64, 65)
+if hasattr(fe, "ransac"):          # a tree from before the entry has every other group
+    def ransac_digest_job(kind, dn, slots):
+        n = F.SAC_SAMPLE_SIZE[kind] + dn if dn <= 0 else dn
+        return RC.ransac_job(kind, RC.exact_fields(kind, n, 700 + 10 * n + kind, outliers=0.34), n_slots=slots, max_iterations=50,
+                             probability=0.99, threshold=9.0, seed=0x9E3779B97F4A7C15 ^ (n * 1024 + slots))
+
+    ransac_shapes = [(kind, dn, slots) for kind in RC.KINDS for dn in RANSAC_N for slots in RANSAC_SLOTS]
+    for referee in (False, True):
+        tag = f"referee{int(referee)}"
+        for kind, dn, slots in ransac_shapes:
+            r, = fe.ransac([ransac_digest_job(kind, dn, slots)], referee)
+            record(f"ransac/kind{kind}_n{dn}_slots{slots}_{tag}", **arrays(r))
+        for (kind, dn, slots), r in zip(ransac_shapes, fe.ransac([ransac_digest_job(*s) for s in ransac_shapes], referee)):
+            record(f"ransac_batch/kind{kind}_n{dn}_slots{slots}_{tag}", **arrays(r))
+        for kind in RC.KINDS:
+            r, = fe.ransac([RC.end_to_end(kind)[0]], referee)
+            record(f"ransac/end_to_end_kind{kind}_{tag}", **arrays(r))
 
 # ---------------------------------------------------------------- propagation
 PROP = ("T_WS", "sb", "count", "cov", "jac")
