@@ -63,8 +63,15 @@
  *                                the decision per multiframe, many multiframes per call; exact (hull, area and inside test are stated
  *                                from their definitions, see the entry)
  *
- * What stays with the caller is what needs the estimator's book-keeping or image data: which keypoints carry a landmark,
- * addLandmark / addObservation.  G = PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
+ * and the first thing the pipeline does with a frame:
+ *
+ *   okvis_fe_detect_keypoints    the detector of Frontend::detectAndDescribe (okvis_frontend/src/Frontend.cpp:92-114) under the shipped
+ *                                configuration (octaves 0): Harris scores on the full-resolution 8-bit image, 3 x 3 maxima above an
+ *                                absolute threshold, greedy selection of the strongest that keeps them min_dist apart, many images
+ *                                per call; exact integer arithmetic.  Stated in this header, not pinned to BRISK
+ *
+ * What stays with the caller is what needs the estimator's book-keeping or the descriptor extractor: which keypoints carry a
+ * landmark, addLandmark / addObservation, BRISK's descriptors (and scale space, octaves > 0).  G =PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
  * Plain pointers and sizes, int status codes (okvis_amd_ba.h), host buffers in and out; no CPU path.
  */
@@ -578,6 +585,72 @@ int okvis_fe_keyframe_decision(okvis_fe_context* ctx, int32_t n_kp, const float*
                                double* overlap, double* ratio, int32_t* n_matched, int32_t* hull_all_size, int32_t* hull_matched_size,
                                double* area_all, double* area_matched, int32_t* n_inside, uint8_t* flags, int32_t* hull_all,
                                int32_t* hull_matched);
+
+#define OKVIS_FE_DETECT_OVERFLOW 1u /* more candidates than cand_capacity: nothing was selected, raise the threshold           */
+#define OKVIS_FE_DETECT_FULL 2u     /* max_keypoints were accepted and one more would have been: the list is cut short       */
+#define OKVIS_FE_DETECT_MAX_DIM 8192        /* width and height: 5 .. 8192                                                   */
+#define OKVIS_FE_DETECT_MAX_KEYPOINTS 2048  /* the reference asks for 400 to 450                                             */
+#define OKVIS_FE_DETECT_MAX_CANDIDATES 8192 /* the keyframe entry's limit per image; the selection kernel holds a candidate
+                                               list in the registers of one workgroup, 1024 lanes x 8                        */
+
+typedef struct okvis_fe_detect_job { /* one grey image */
+  const uint8_t* image;  /* row-major, row y starts at image + y * pitch                                  */
+  int64_t threshold;     /* >= 1, on the scale of S below                                                 */
+  int32_t width, height; /* 5 .. OKVIS_FE_DETECT_MAX_DIM each; below 5 there is no pixel with a score     */
+  int32_t pitch;         /* bytes, >= width                                                               */
+  int32_t min_dist;      /* >= 0: the uniformity radius in pixels, the reference's `threshold` option (40) */
+  int32_t max_keypoints; /* 1 .. OKVIS_FE_DETECT_MAX_KEYPOINTS                                            */
+  int32_t cand_capacity; /* 1 .. OKVIS_FE_DETECT_MAX_CANDIDATES                                           */
+  float kp_size;         /* copied into the third column of kp: BRISK's size for octave 0 is the caller's to supply */
+  /* out */
+  int32_t n_keypoints;
+  int32_t n_candidates; /* the true count, past cand_capacity too */
+  int32_t flags;        /* OKVIS_FE_DETECT_*                       */
+  float* kp;            /* [max_keypoints][3] x, y, size: the first n_keypoints rows are written, in selection order, strongest
+                           first; what every other okvis_fe_* entry takes as keypoints                                        */
+  double* response;     /* [max_keypoints] or NULL: (double)S, exact                                                        */
+  int32_t* pixel;       /* [max_keypoints][2] or NULL: x, y of the integer maximum                                          */
+  int64_t* score;       /* [height][width] or NULL: the whole score image, 0 outside its domain.  A referee's output: without
+                           it no score leaves the tile it was computed in                                                    */
+} okvis_fe_detect_job;
+
+/* What Frontend::detectAndDescribe (okvis_frontend/src/Frontend.cpp:92-114) asks of its detector under the shipped configuration,
+ * for many images per call: brisk::ScaleSpaceFeatureDetector<brisk::HarrisScoreCalculator>(threshold, octaves, absoluteThreshold,
+ * maxNoKeypoints) (:828-831) with octaves = 0 — a Harris score on the full-resolution image, a 3 x 3 maximum search above an absolute
+ * threshold, a selection of the strongest maxima that keeps them apart.  BRISK's source is not part of the reference tree (it is
+ * fetched at build time): the detector is stated here and is NOT pinned to BRISK.  Scale space (octaves > 0), descriptors and masks
+ * are not here.  Images are 8-bit: the statement is integer arithmetic (int64 unless said otherwise) and every output is exact.
+ * With I the image, w = width, h = height:
+ *   derivatives  for 1 <= x <= w-2, 1 <= y <= h-2 (Sobel):
+ *                Ix = (I[y-1][x+1] + 2 I[y][x+1] + I[y+1][x+1]) - (I[y-1][x-1] + 2 I[y][x-1] + I[y+1][x-1]),
+ *                Iy = (I[y+1][x-1] + 2 I[y+1][x] + I[y+1][x+1]) - (I[y-1][x-1] + 2 I[y-1][x] + I[y-1][x+1]);  |Ix|, |Iy| <= 4 * 255 = 1020.
+ *   tensor       for 2 <= x <= w-3, 2 <= y <= h-3 (the score domain): A = sum k Ix^2, B = sum k Ix Iy, C = sum k Iy^2 over the 3 x 3
+ *                neighbourhood under the binomial weights k = [1 2 1]^T [1 2 1] (sum 16).
+ *   score        S = 16 (A C - B^2) - (A + C)^2: the Harris measure det - k trace^2 with k = 1/16, scaled by 16.
+ *                Bounds: 0 <= A, C <= 16 * 1020^2 = 16 646 400 and |B| <= the same, so A C <= 2.78e14, 0 <= A C - B^2 <= 2.78e14
+ *                (Cauchy-Schwarz), (A + C)^2 <= 1.11e15, and -1.11e15 <= S <= 4.44e15: |S| < 5.6e15 < 2^53 = 9.007e15.  No int64
+ *                intermediate overflows, and every score is exact in a double.
+ *   candidates   pixel p BEATS pixel q when S_p > S_q, or S_p == S_q and y_p w + x_p < y_q w + x_q: a total order.  A pixel of the
+ *                score domain is a candidate when S >= threshold and it beats all of its eight neighbours; neighbours outside the
+ *                score domain count as beaten.  A plateau yields exactly one candidate.  n_candidates is their number.
+ *   sub-pixel    along x: num = S(x-1,y) - S(x+1,y), den = 2 (S(x-1,y) - 2 S(x,y) + S(x+1,y)) in int64, a neighbour outside the domain
+ *                counting as S(x,y); both converted to double (round to nearest); d = num / den if den != 0, else 0, clamped to
+ *                [-0.5, 0.5]; kp.x = (float)((double)x + d).  The same along y.  One IEEE division and one addition per axis.
+ *   selection    n_candidates > cand_capacity: flags = OVERFLOW, n_keypoints = 0, no partial result.  Otherwise the candidates are
+ *                gone through in beat order, strongest first; one is ACCEPTABLE when every keypoint accepted before it lies at integer
+ *                squared distance >= min_dist^2 from it, measured on the integer maxima (min_dist = 0: all are); acceptable
+ *                candidates are accepted until max_keypoints have been; when a further one is acceptable after that, flags |= FULL
+ *                (candidates running out right at max_keypoints is not FULL).  This is plain greedy disc suppression.  BRISK weights
+ *                its uniformity mask by score: this rule is NOT BRISK's.
+ * One staging copy in (the images, rows packed without their pitch, in front of everything else in the block); detect_score_kernel,
+ * one workgroup per 64 x 16 tile of any image: bytes, gradients and scores in LDS, only candidates leave the tile (24 bytes each,
+ * appended through one counter per image; the list's order in memory reaches no output); detect_select_kernel, one workgroup per
+ * image: the strongest candidate still in play by a workgroup-wide reduction per accepted keypoint, its disc struck out in
+ * parallel; one copy back.  The results do not depend on the batch around a job or on the run.
+ * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or table, a negative job count, a NULL
+ * image or kp, width or height outside 5..OKVIS_FE_DETECT_MAX_DIM, pitch < width, threshold < 1, min_dist < 0, max_keypoints or
+ * cand_capacity outside their limits.  n_jobs = 0 is valid and touches nothing. */
+int okvis_fe_detect_keypoints(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_job* jobs);
 
 #ifdef __cplusplus
 }

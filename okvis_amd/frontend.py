@@ -3,8 +3,8 @@ with uncertainty, 3D-2D projection and chi-square gating), its descriptor matchi
 best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the outlier rejection
 behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems, the generalised
 three-point solver of the 3D-2D problem, and whole RANSAC runs with the sampler and the adaptive loop on the device), the IMU state
-propagation with covariance and Jacobian and the keyframe decision (exact hulls, areas and inside counts) on the MI355X.  No CPU
-path."""
+propagation with covariance and Jacobian, the keyframe decision (exact hulls, areas and inside counts) and keypoint detection
+(Harris scores, 3 x 3 maxima and greedy uniformity selection, exact) on the MI355X.  No CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +20,7 @@ GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
            "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
-           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac"]
+           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac", "okvis_fe_detect_keypoints"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
@@ -30,6 +30,11 @@ RANSAC_STOP_CONVERGED, RANSAC_STOP_MAX_ITERATIONS, RANSAC_STOP_EXHAUSTED, RANSAC
 IMU_COV, IMU_JAC = 1, 2
 KF_FEW_POINTS, KF_FEW_MATCHES = 1, 2
 KF_MAX_KEYPOINTS, KF_MAX_CAMS = 8192, 8
+DETECT_OVERFLOW, DETECT_FULL = 1, 2
+DETECT_MAX_DIM, DETECT_MAX_KEYPOINTS, DETECT_MAX_CANDIDATES = 8192, 2048, 8192
+DETECT_TILE_X, DETECT_TILE_Y = 64, 16            # the score kernel's tile (fe_detect.hpp: DET_TILE_X, DET_TILE_Y)
+DETECT_WAVE, DETECT_SELECT_THREADS = 64, 1024    # the selection kernel's widths (DET_SEL_THREADS)
+DETECT_KP_SIZE = 12.0                            # BRISK's basic size at scale 1; okvis takes sigma = 0.8 size / 12
 
 
 class CameraC(C.Structure):
@@ -109,6 +114,14 @@ class KfJobC(C.Structure):
                 ("overlap_threshold", C.c_float), ("ratio_threshold", C.c_float)]
 
 
+class DetectJobC(C.Structure):
+    """okvis_fe_detect_job"""
+    _fields_ = [("image", C.c_void_p), ("threshold", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32),
+                ("min_dist", C.c_int32), ("max_keypoints", C.c_int32), ("cand_capacity", C.c_int32), ("kp_size", C.c_float),
+                ("n_keypoints", C.c_int32), ("n_candidates", C.c_int32), ("flags", C.c_int32), ("kp", C.c_void_p),
+                ("response", C.c_void_p), ("pixel", C.c_void_p), ("score", C.c_void_p)]
+
+
 def camera(intr, model, width=752, height=480) -> CameraC:
     c = CameraC()
     k = np.zeros(12)
@@ -171,6 +184,7 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_match_verified.argtypes = [vp, i32, C.POINTER(VMatchJobC), i32, C.c_float, i32, i32, C.c_float]
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
         L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
+        L.okvis_fe_detect_keypoints.argtypes = [vp, i32, C.POINTER(DetectJobC)]
 
 
 class Frontend:
@@ -422,6 +436,18 @@ class Frontend:
                    *[_ptr(out[k]) for k in KF_OUTPUTS])
         return keyframe_results(table, counts, out, want_hulls)
 
+    def detect_keypoints(self, images, threshold, min_dist=40, max_keypoints=400, cand_capacity=DETECT_MAX_CANDIDATES,
+                         kp_size=DETECT_KP_SIZE, want_score=False):
+        """Harris corners with uniformity selection for many images in one call (okvis_fe_detect_keypoints; the statement is in
+        the header and is not BRISK's).  images: a list of 2-D uint8 arrays whose columns are contiguous (rows may have any pitch
+        >= width; sizes may differ); threshold, min_dist, max_keypoints, cand_capacity, kp_size: one value for all, or one per image.
+        -> per image a dict: kp [n][3] float32 (x, y, size; strongest first: what every other entry takes as keypoints), response
+        [n] float64 (the score S, exact), pixel [n][2] int32 (the integer maximum), n_candidates, flags (DETECT_OVERFLOW |
+        DETECT_FULL) and, under want_score, score [h][w] int64 (0 outside the score domain)."""
+        table, keep, out = detect_job_table(images, threshold, min_dist, max_keypoints, cand_capacity, kp_size, want_score)
+        self._call("detect_keypoints", len(out), table)
+        return detect_results(table, out)
+
 
 def landmark_covariance_in_camera(Sigma, T_CW):
     """A landmark's covariance rotated into a camera frame: ``R Sigma R^T``, R the rotation of T_CW (world to camera).  Sigma
@@ -514,6 +540,46 @@ def keyframe_results(table, counts, out, want_hulls=False):
                 r["hull_matched"] = out["hull_matched"][starts[i]:starts[i] + r["hull_matched_size"]].copy()
             ims.append(r)
         res.append({"decision": bool(out["decision"][j]), "overlap": float(out["overlap"][j]), "ratio": float(out["ratio"][j]), "images": ims})
+    return res
+
+
+DETECT_OUTPUTS = ("kp", "response", "pixel", "score")
+
+
+def detect_job_table(images, threshold, min_dist=40, max_keypoints=400, cand_capacity=DETECT_MAX_CANDIDATES, kp_size=DETECT_KP_SIZE,
+                     want_score=False, leave_out=()):
+    """-> (okvis_fe_detect_job array, what has to outlive the call, the output arrays per job by name (DETECT_OUTPUTS; None where
+    not asked for or named in leave_out)).  An image is passed as it lies in memory: no copy is made of a view with a pitch."""
+    n = len(images)
+    per = lambda v: list(v) if np.ndim(v) else [v] * n
+    thr, md, mk, cc, ks = per(threshold), per(min_dist), per(max_keypoints), per(cand_capacity), per(kp_size)
+    table, keep, out = (DetectJobC * max(1, n))(), [], []
+    for j, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1) or im.strides[0] < im.shape[1]:
+            raise ValueError("an image is a 2-D uint8 array with contiguous columns and a pitch of at least its width")
+        t = table[j]
+        t.image, t.height, t.width, t.pitch = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        t.threshold, t.min_dist, t.max_keypoints, t.cand_capacity, t.kp_size = int(thr[j]), int(md[j]), int(mk[j]), int(cc[j]), float(ks[j])
+        rows = max(0, int(mk[j]))
+        o = {"kp": np.zeros((rows, 3), np.float32), "response": np.zeros(rows), "pixel": np.zeros((rows, 2), np.int32),
+             "score": np.zeros(im.shape, np.int64) if want_score else None}
+        for k in leave_out:
+            o[k] = None
+        t.kp, t.response, t.pixel, t.score = (_ptr(o[k]) for k in DETECT_OUTPUTS)
+        keep.append(im), out.append(o)
+    return table, keep, out
+
+
+def detect_results(table, out):
+    """the filled arrays of detect_job_table as one dict per image, cut to n_keypoints rows"""
+    res = []
+    for j, o in enumerate(out):
+        n = table[j].n_keypoints
+        r = {k: o[k][:n].copy() for k in ("kp", "response", "pixel") if o[k] is not None}
+        if o["score"] is not None:
+            r["score"] = o["score"]
+        r.update(n_candidates=int(table[j].n_candidates), flags=int(table[j].flags))
+        res.append(r)
     return res
 
 

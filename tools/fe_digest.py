@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry (the fifteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
+Every okvis_fe_* entry (the sixteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
 every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
 in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
 whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
@@ -10,7 +10,7 @@ group differs, --cases FILE writes the hash of every array of every case (some 1
     python tools/fe_digest.py OUT.json [--root TREE] [--cases FILE]   (TREE: the checkout whose okvis_amd is used, default this one)
 
 The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py,
-tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/ransac_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/golden/) are those of the checkout the tool
+tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/ransac_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/detect_cases.py, tests/golden/) are those of the checkout the tool
 itself is in; nothing outside it is read.
   verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
                       settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
@@ -35,6 +35,9 @@ itself is in; nothing outside it is read.
   propagation         imu_propagate_cases.batch() as one call; every spec alone under flags 0, IMU_COV, IMU_JAC and both
   keyframe            every family of keyframe_cases.NAMES with and without the hull lists, every job alone and the family as
                       one call
+  detect              every family of detect_cases.NAMES with and without the score image, every job alone and the family as one
+                      call; the end-to-end scenes and the shifted images.  Left out where the tree under --root is from before
+                      the entry
 """
 import argparse
 import ctypes as C
@@ -331,6 +334,29 @@ for name in KC.NAMES:
             record(f"keyframe/{tag}_job{j}", **kf_arrays(r))
         for j, r in enumerate(fe.keyframe_decision(jobs, want_hulls)):
             record(f"keyframe_batch/{tag}_job{j}", **kf_arrays(r))
+
+# ---------------------------------------------------------------- keypoint detection
+if hasattr(fe, "detect_keypoints"):          # a tree from before the entry has every other group
+    import detect_cases as DC  # noqa: E402  (it reads the tile shape from the tree's okvis_amd.frontend)
+
+    def detect(jobs, want_score):
+        return fe.detect_keypoints([j["image"] for j in jobs], *[[j[k] for j in jobs] for k in ("threshold", "min_dist", "max_keypoints",
+                                                                                               "cand_capacity", "kp_size")], want_score=want_score)
+
+    def det_arrays(r):
+        return {k: np.asarray(v) for k, v in r.items()}
+
+    families = {name: DC.cases(name) for name in DC.NAMES}
+    families["scenes"] = [DC.scene(seed, noise)[0] for seed in DC.SCENE_SEEDS for noise in (False, True)]
+    families["shifts"] = [DC.translated(dx, dy) for dx, dy in DC.SHIFTS]
+    for name, jobs in families.items():
+        for want_score in (False, True):
+            tag = f"{name}_score{int(want_score)}"
+            for j, job in enumerate(jobs):
+                r, = detect([job], want_score)
+                record(f"detect/{tag}_job{j}", **det_arrays(r))
+            for j, r in enumerate(detect(jobs, want_score)):
+                record(f"detect_batch/{tag}_job{j}", **det_arrays(r))
 fe.close()
 
 if args.cases:
