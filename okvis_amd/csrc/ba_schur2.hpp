@@ -22,6 +22,13 @@
 //     and 16 consecutive rows at stride 13 doubles write 32 distinct LDS banks.  The ring is zeroed once; a set is zeroed again, two
 //     barriers ahead of its fill, only in front of a stage that does not overwrite it (a pair missing, or the ragged last stage).
 //     The chunk's J^T J / J^T r lists are requested in front of V^-1 and summed behind the first fill.
+//     The iterations of a decision-free launch (SCH2_FREE: schur_mfma_kernel<3, false, true>, schur_ride_kernel<3, false, true>) form
+//     V^-1 in front of the FIRST barrier: lambda comes from the control words of the head, so the landmark blocks and their Jacobi
+//     scales leave first, the stages and the list values behind them in the same trip, and work-item i waits for its own twelve values
+//     only.  The list requests are straight-line code there; written with the choice at the request, each entry's first addition was
+//     pulled up to its load and a wait for every outstanding load with it.  Two dependent trips and two barriers between launch and
+//     first product instead of five and three (head + V^-1 5.3 -> 3.2 us); inv3sym and the damping are spelled with fma in the order
+//     the other instantiations give them: the same bits (tests/test_gpu_schur_prologue.py).  profiles/schur_prologue_notes.md.
 //     A workgroup's static structure — chunk descriptor, list ranges and list heads — is ONE launch record of whole lines whose address
 //     comes from the kernel arguments and the workgroup's indices (SCHUR_REC_INTS, ba_types.hpp; build_chunk_records): it is requested
 //     with the window record and the control words, so the first data loads leave one round trip behind the launch (head 3.5 -> 1.9 us).
@@ -33,8 +40,8 @@
 //     Both loops feed the matrix core the same groups of four indices in the same order into the same accumulators: the same sums
 //     bit for bit (tests/test_gpu_schur_pipeline.py); only the exact zeros of a ragged last batch are no longer added.
 //
-// 49 KB of LDS and 166 registers, no scratch in the Schur workgroups: three workgroups per CU (schur_kernel: two, at 222
-// registers), and the block products of a 48-landmark chunk take 1.5 k matrix-core cycles per wave instead of 3 x 3 us of
+// 49 KB of LDS and 166 registers (SCH2_FREE: 139), no scratch in the Schur workgroups: three workgroups per CU (schur_kernel: two,
+// at 222 registers), and the block products of a 48-landmark chunk take 1.5 k matrix-core cycles per wave instead of 3 x 3 us of
 // LDS-bound 6x6 block products.  Phase stamps and launch times: profiles/schur_pipeline_notes.md.
 #pragma once
 #include "ba_imu.hpp"
@@ -61,10 +68,15 @@ __host__ __device__ constexpr int sch2_ring_doubles(int trows) { return SCH2_RIN
 
 // SCH2_SERIAL: the batch loop of rounds 4-6 (nlb landmarks per batch, three barriers per batch) — the large tiles, and the referee of
 // the pipelined loop (OKVIS_BA_TUNE_SCHUR_SERIAL_BATCHES)
-template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
+// SCH2_FREE: the pipelined loop of a decision-free launch in a damped mode — every iteration of a DOGLEG, Gauss-Newton or fixed-radius
+// run (launch_schur, capi_launch.inc); V^-1 in front of the first barrier.  The deciding launch and the eliminations of the
+// marginalisation and covariance entries (OptD::marg_mode) keep the instantiation without it, whose text is what it was.
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3), bool SCH2_FREE = false>
 __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows, int final_call, int nlb,
-                                                const CtrlSlot* __restrict__ ctrls, int nodec, const int bx, const int* __restrict__ recs,
+                                                const CtrlSlot* __restrict__ ctrls, int nodec_arg, const int bx, const int* __restrict__ recs,
                                                 int rec_stride) {
+  static_assert(!SCH2_FREE || !SCH2_SERIAL, "the decision-free instantiation is a ring instantiation");
+  const int nodec = SCH2_FREE ? 1 : nodec_arg;
   const WinPtrs& W = wins[blockIdx.y];
   // The control record's address comes from the kernel arguments (CtrlSlot, ba_types.hpp; == W.ctrl): its first words — accepted
   // buffer, pending, first, done — arrive together with the window record, and with them the index of the linearisation buffer
@@ -284,6 +296,9 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
   };
   static_assert(SCHUR_CHUNK_LM_MAX <= SCHUR_THREADS, "one landmark per work-item");
   double lv[6] = {1, 0, 0, 1, 0, 1}, lb3[3] = {0, 0, 0};
+  // SCH2_FREE: the Jacobi scales of the landmark's columns leave with its blocks (clamped, no branch around the request: the
+  // work-items behind the chunk's last landmark re-read its scales and drop them; a chunk has at least one landmark)
+  double lsc[3] = {1.0, 1.0, 1.0};
   auto load_landmark = [&](int buf) {
     if (tid < nl) {
       const double* Vl = W.V[buf] + 6 * (size_t)(lm_begin + tid);
@@ -292,29 +307,96 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
       for (int e = 0; e < 6; ++e) lv[e] = Vl[e];
       lb3[0] = bl[0], lb3[1] = bl[1], lb3[2] = bl[2];
     }
+    if constexpr (SCH2_FREE) {
+      const double* sl = W.lm_scale + 3 * (size_t)max(min(lm_begin + min(tid, nl - 1), W.n_lm - 1), 0);
+      lsc[0] = sl[0], lsc[1] = sl[1], lsc[2] = sl[2];
+    }
   };
-  load_first();
-  load_landmark(spec);
-  if (!nodec) schur_decision_finish(W, opt, dl, final_call, bx, tid, s_ctrl, s_dec, s_lambda);
+  // The chunk's J^T J / J^T r lists, summed in list order.  Serial loop: requested and summed behind the decision.  Pipelined loop:
+  // requested with the first data (SCH2_FREE) or behind the decision, summed behind the first fill, where the workgroup would
+  // otherwise wait for nothing (they do not depend on the product); a pose part within 64 rows has at most SCH2_DIP x SCHUR_THREADS
+  // diagonal entries.
+  double d_u[SCH2_DI], r_g = 0.0, r_du = 0.0;
+  constexpr int SCH2_DIP = SCH2_SERIAL ? 1 : (SCH2_MAXT_SMALL_ROWS / 6 * 36 + SCHUR_THREADS - 1) / SCHUR_THREADS;
+  double d_v[SCH2_DIP][SCH2_LL], r_vg[SCH2_LL], r_vd[SCH2_LL];
+  // SCH2_FREE: requests that are straight-line code — a slot without a list entry re-reads the first value of the buffer (a window
+  // with a chunk has a task output there) and lists_sum adds an exact zero in its place.  With the choice at the request (the other
+  // instantiations, below) the compiler pulls the first addition of every entry up to its load, and a wait for ALL outstanding
+  // loads with it: two memory round trips of their own.
+  double e_v[SCH2_DIP][SCH2_LL], e_vg[SCH2_LL], e_vd[SCH2_LL];
+  auto early_request_entries = [&](const double* gp) {   // (U_pp of the diagonal blocks)
+#pragma unroll
+    for (int it = 0; it < SCH2_DIP; ++it) {
+      const int e = tid + it * SCHUR_THREADS;
+      const int k = e % 36, ii = k / 6, jj = k - 6 * ii;
+      const int uk = jj * 6 - (jj * (jj - 1)) / 2 + (ii - jj);
+      const bool on = diag && e < nrow * 36 && jj <= ii;   // U_pp: lower triangle
+#pragma unroll
+      for (int q = 0; q < SCH2_LL; ++q) e_v[it][q] = gp[on && q < d_n[it] ? d_out[it][q] + uk : 0];
+    }
+  };
+  auto early_request_rows = [&](const double* gp) {   // (g | diag U of the rows)
+    const int a = tid % 6, dk = a * 6 - (a * (a - 1)) / 2;
+#pragma unroll
+    for (int q = 0; q < SCH2_LL; ++q) {
+      const bool on = diag && tid < 6 * nrow && q < r_n;
+      e_vg[q] = gp[on ? r_out[q] + 21 + a : 0];
+      e_vd[q] = gp[on ? r_out[q] + dk : 0];
+    }
+  };
+  // (nodec: the rule of the fused linearise launch, ba_linearize2.hpp — the damping of the solve that follows an accepted trial)
+  auto lam_free = [&]() {
+    const double lam_next = opt.dogleg ? ((chead.z || opt.gauss_newton) ? c_mu : fmax(DL_MIN_MU, 2.0 * c_mu / DL_MU_INCREASE)) : 1.0 / c_radius;
+    return chead.y ? lam_next : (opt.dogleg ? c_mu : 1.0 / c_radius);
+  };
+  // SCH2_FREE: nothing V^-1 needs lies behind the first trip — lambda comes from the control words of the head, the reduced buffer
+  // is the speculated one — so the landmark blocks and scales leave FIRST, the stage rows and the list values behind them in the
+  // same trip, and work-item i < nl forms (V_i + lambda D_i^2)^-1 and V_i^-1 b as soon as its own twelve values are there (vector
+  // loads return in order: the wait is a counted one that leaves the rows and the lists in flight).  s_vinv / s_vb are published
+  // by the barrier that publishes the zeroed ring: two trips and two barriers between launch and first product instead of five and
+  // three.  The deciding launch has lambda only behind schur_decision_finish, the marginalisation modes take no scales: both keep
+  // their path below.  Without the decision and the pseudo-inverse the instantiation holds 139 registers.
+  constexpr bool early = SCH2_FREE;
+  if (early) {
+    if (chead.w != 0) return;   // (finished earlier: uniform, nothing requested)
+    load_landmark(spec);
+    load_first();
+    early_request_entries(W.gpart[spec]);
+    early_request_rows(W.gpart[spec]);
+    if (tid < nl) {
+      // inv3sym and the damping with the contraction the compiler gives them in the block below, spelled out (see s_vb)
+      double sc0 = 1.0, sc1 = 1.0, sc2 = 1.0;
+      if (opt.dogleg) sc0 = lsc[0], sc1 = lsc[1], sc2 = lsc[2];
+      const double lam = lam_free();
+      const double a = __builtin_fma(lam, damp_diag(lv[0], sc0, opt), lv[0]), b = lv[1], c = lv[2];
+      const double d = __builtin_fma(lam, damp_diag(lv[3], sc1, opt), lv[3]), e = lv[4];
+      const double f = __builtin_fma(lam, damp_diag(lv[5], sc2, opt), lv[5]);
+      const double c00 = __builtin_fma(d, f, -(e * e)), c01 = __builtin_fma(c, e, -(b * f)), c02 = __builtin_fma(b, e, -(c * d));
+      const double id = 1.0 / __builtin_fma(c, c02, __builtin_fma(a, c00, b * c01));
+      const double vi[6] = {c00 * id, c01 * id, c02 * id, __builtin_fma(a, f, -(c * c)) * id, __builtin_fma(b, c, -(a * e)) * id,
+                            __builtin_fma(a, d, -(b * b)) * id};
+#pragma unroll
+      for (int q = 0; q < 6; ++q) s_vinv[tid][q] = vi[q];
+      s_vb[tid][0] = __builtin_fma(vi[2], lb3[2], __builtin_fma(vi[1], lb3[1], vi[0] * lb3[0]));
+      s_vb[tid][1] = __builtin_fma(vi[4], lb3[2], __builtin_fma(vi[3], lb3[1], vi[1] * lb3[0]));
+      s_vb[tid][2] = __builtin_fma(vi[5], lb3[2], __builtin_fma(vi[4], lb3[1], vi[2] * lb3[0]));
+    }
+  } else {
+    load_first();
+    load_landmark(spec);
+    if (!nodec) schur_decision_finish(W, opt, dl, final_call, bx, tid, s_ctrl, s_dec, s_lambda);
+  }
   __syncthreads();
   SSTAMP(17);
   if (nodec ? chead.w != 0 : (s_ctrl.done || s_dec[1])) return;   // finished earlier / terminated by the decision (the solve kernel records it)
   const int acc = nodec ? spec : __builtin_amdgcn_readfirstlane(s_dec[0]);
-  // (nodec: the rule of the fused linearise launch, ba_linearize2.hpp — the damping of the solve that follows an accepted trial)
-  const double lam_next = opt.dogleg ? ((chead.z || opt.gauss_newton) ? c_mu : fmax(DL_MIN_MU, 2.0 * c_mu / DL_MU_INCREASE)) : 1.0 / c_radius;
-  const double lambda = nodec ? (chead.y ? lam_next : (opt.dogleg ? c_mu : 1.0 / c_radius)) : s_lambda;
+  const double lambda = nodec ? lam_free() : s_lambda;
   if (acc != spec) {   // (a rejected trial: the other buffer is the one to reduce — requested again)
     Wb = W.W[acc];
     load_first();
     load_landmark(acc);
   }
   const double* gp = W.gpart[acc];
-  // The chunk's J^T J / J^T r lists, summed in list order.  Serial loop: requested and summed here.  Pipelined loop: requested here,
-  // summed behind the first fill, where the workgroup would otherwise wait for nothing (they do not depend on the product); a
-  // pose part within 64 rows has at most SCH2_DIP x SCHUR_THREADS diagonal entries.
-  double d_u[SCH2_DI], r_g = 0.0, r_du = 0.0;
-  constexpr int SCH2_DIP = SCH2_SERIAL ? 1 : (SCH2_MAXT_SMALL_ROWS / 6 * 36 + SCHUR_THREADS - 1) / SCHUR_THREADS;
-  double d_v[SCH2_DIP][SCH2_LL], r_vg[SCH2_LL], r_vd[SCH2_LL];
 #pragma unroll
   for (int it = 0; it < SCH2_DI; ++it) d_u[it] = 0.0;
   if constexpr (SCH2_SERIAL) {
@@ -353,7 +435,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
         }
       }
     }
-  } else {
+  } else if (!early) {
 #pragma unroll
     for (int it = 0; it < SCH2_DIP; ++it) {
       const int e = tid + it * SCHUR_THREADS;
@@ -372,7 +454,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
       r_vd[q] = diag && tid < 6 * nrow && q < r_n ? gp[r_out[q] + dk] : 0.0;
     }
   };
-  auto lists_sum = [&]() {   // (pipelined loop)
+  auto lists_sum = [&]() {   // (pipelined loop; SCH2_FREE: e_v | e_vg | e_vd, the exact zeros chosen here)
     if (!diag) return;
 #pragma unroll
     for (int it = 0; it < SCH2_DIP; ++it) {
@@ -382,7 +464,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
         if (jj <= ii) {
           const int uk = jj * 6 - (jj * (jj - 1)) / 2 + (ii - jj);
 #pragma unroll
-          for (int q = 0; q < SCH2_LL; ++q) d_u[it] += d_v[it][q];
+          for (int q = 0; q < SCH2_LL; ++q) d_u[it] += early ? (q < d_n[it] ? e_v[it][q] : 0.0) : d_v[it][q];
           for (int q = SCH2_LL; q < d_n[it]; ++q) d_u[it] += gp[W.chunk_diag_out[d_q0[it] + q] + uk];
         }
       }
@@ -390,7 +472,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     if (tid < 6 * nrow) {
       const int a = tid % 6, dk = a * 6 - (a * (a - 1)) / 2;
 #pragma unroll
-      for (int q = 0; q < SCH2_LL; ++q) r_g += r_vg[q], r_du += r_vd[q];
+      for (int q = 0; q < SCH2_LL; ++q) r_g += early ? (q < r_n ? e_vg[q] : 0.0) : r_vg[q], r_du += early ? (q < r_n ? e_vd[q] : 0.0) : r_vd[q];
       for (int q = SCH2_LL; q < r_n; ++q) {
         const double* o = gp + W.chunk_diag_out[r_q0 + q];
         r_g += o[21 + a];
@@ -399,7 +481,7 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     }
   };
   // (V_l + lambda D_l^2)^-1 and V^-1 b of every landmark of the chunk (work-item i: landmark i, its blocks are in registers)
-  if (tid < nl) {
+  if (!early && tid < nl) {
     const int i = tid;
     const int l = lm_begin + i;
     double v[6] = {lv[0], lv[1], lv[2], lv[3], lv[4], lv[5]};
@@ -561,8 +643,10 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
     //        runs the products of stage st on set st % 3.
     //      Set (st + 2) % 3 was last read by the products of stage st - 1, in front of the previous barrier; the fill of stage
     //      st + 2 comes behind the next one.  Nothing here waits for anything but the workgroup's own barrier. ----
-    lists_request_rows();
-    __syncthreads();   // s_vinv / s_vb
+    if (!early) {   // (SCH2_FREE: requested with the first data, published by the barrier of the head)
+      lists_request_rows();
+      __syncthreads();   // s_vinv / s_vb
+    }
     SSTAMP(18);
     const bool vb_item = diag && tid >= SCHUR_THREADS - SCH2_STAGE_LM;   // the V^-1 b row: the last work-items, idle in the fill
     auto write_stage = [&](int u, int st) {   // (u static: register set and ring set)
@@ -775,11 +859,11 @@ __device__ __forceinline__ void schur_mfma_body(const WinPtrs* __restrict__ wins
 }
 
 
-template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3), bool SCH2_FREE = false>
 __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_mfma_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp,
                                                                       int tile_rows, int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec,
                                                                       const int* __restrict__ recs, int rec_stride) {
-  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x, recs, rec_stride);
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL, SCH2_FREE>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x, recs, rec_stride);
 }
 
 // The decision-free Schur launch with the EVALUATION of the IMU / prior factors of the same trial riding along (round 6): workgroups
@@ -788,7 +872,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, SCH2_MAXT <= 3 ? 3 : 2) void schur_m
 // Schur workgroups.  Neither kind waits for the other — the reduction does not need the factors' costs when it takes no decision —
 // and both only have to be through before the next solve launch.  (Round 5 let the WHOLE factor workgroups ride: 255 registers and
 // 62 KB of LDS of the re-preintegration path put the launch at two workgroups per CU and cost the line 6 %; this half keeps three.)
-template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3)>
+template <int SCH2_MAXT, bool SCH2_SERIAL = (SCH2_MAXT > 3), bool SCH2_FREE = false>
 __global__ __launch_bounds__(SCHUR_THREADS, 3) void schur_ride_kernel(const WinPtrs* __restrict__ wins, const OptD* __restrict__ optp, int tile_rows,
                                                                       int final_call, int nlb, const CtrlSlot* __restrict__ ctrls, int nodec, int n_small,
                                                                       const int* __restrict__ recs, int rec_stride) {
@@ -798,7 +882,7 @@ __global__ __launch_bounds__(SCHUR_THREADS, 3) void schur_ride_kernel(const WinP
     small_body<2>(wins[blockIdx.y], 0, (int)blockIdx.x, sch_smem);
     return;
   }
-  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small, recs, rec_stride);
+  schur_mfma_body<SCH2_MAXT, SCH2_SERIAL, SCH2_FREE>(wins, optp, tile_rows, final_call, nlb, ctrls, nodec, (int)blockIdx.x - n_small, recs, rec_stride);
 }
 
 }  // namespace ba

@@ -66,7 +66,9 @@ std::vector<std::pair<const void*, size_t>> plan_kernels() {
           {f(&schur_ride_kernel<3, true>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3, true>), wide},
           // (the record instantiations of the piece path, behind everything that was there before them)
           {f(&linearize2_rec_kernel<double, 3>), d}, {f(&linearize2_rec_kernel<double, 4, 14>), d},
-          {f(&linearize2_rec_kernel<float, 3>), s}, {f(&linearize2_rec_kernel<float, 4, 14>), s}};
+          {f(&linearize2_rec_kernel<float, 3>), s}, {f(&linearize2_rec_kernel<float, 4, 14>), s},
+          // (the ring loop's instantiations for the decision-free launch of an iteration: V^-1 in front of the first barrier)
+          {f(&schur_ride_kernel<3, false, true>), std::max(wide, small_eval_smem())}, {f(&schur_mfma_kernel<3, false, true>), wide}};
 }
 
 // ---- The instantiations a launch plan names (Launch::k is the index in the table of its kind) ----
@@ -263,8 +265,11 @@ Sub sub(hipStream_t st, const Extent& e) { return Sub{st, e.w0, e.nw, e.helpers}
 Sub whole(okvis_ba_solver* s) { return sub(s->stream, s->plan.whole); }
 
 // ---- The launches, each as the plan has it ----
-hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
+// damped: the launch of an iteration (lambda from the control words).  The eliminations of the marginalisation and of the covariance
+// entries (OptD::marg_mode, schur_and_export) take no damping and keep the instantiations that hold their inverses.
+hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0, bool damped = true) {
   const LaunchPlan& p = s->plan;
+  const bool free_ring = p.nodec && damped;   // (ring instantiations: the decision-free prologue, ba_schur2.hpp)
   const dim3 grid((unsigned)p.schur.gx, (unsigned)b.nw), blk(SCHUR_THREADS);
   const WinPtrs* wins = s->d_wins + b.w0;
   const CtrlSlot* ctrls = s->d_ctrl + b.w0;
@@ -273,9 +278,13 @@ hipError_t launch_schur(okvis_ba_solver* s, Sub b, int final_call = 0) {
   switch (p.schur.k) {
     case SCHUR_NONE: return hipSuccess;
     case SCHUR_VALU: hipLaunchKernelGGL(schur_kernel, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call); break;
-    case SCHUR_MFMA3: hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
+    case SCHUR_MFMA3:
+      if (free_ring) hipLaunchKernelGGL((schur_mfma_kernel<3, false, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride);
+      else hipLaunchKernelGGL(schur_mfma_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
     case SCHUR_MFMA9: hipLaunchKernelGGL(schur_mfma_kernel<9>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
-    case SCHUR_RIDE3: hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride); break;
+    case SCHUR_RIDE3:
+      if (free_ring) hipLaunchKernelGGL((schur_ride_kernel<3, false, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride);
+      else hipLaunchKernelGGL(schur_ride_kernel<3>, grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride); break;
     case SCHUR_MFMA3_SERIAL: hipLaunchKernelGGL((schur_mfma_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, recs, p.rec_stride); break;
     case SCHUR_RIDE3_SERIAL: hipLaunchKernelGGL((schur_ride_kernel<3, true>), grid, blk, p.schur.lds, b.st, wins, s->d_opt, p.trows, final_call, p.nlb, ctrls, p.nodec, p.n_small, recs, p.rec_stride); break;
   }

@@ -53,7 +53,7 @@ WinPtrs win_with_export(const HostWin& H, unsigned char* d, const ExportAt& ex) 
 // (such windows leave the solve launch at once; marg_export_large exports them one by one).
 hipError_t schur_and_export(okvis_ba_solver* s, int w0, int n, const WinPtrs* d_wins, bool lds_windows = true) {
   const int helpers = n <= SOLVE_HELPED_MAX_WINDOWS ? s->plan.one_helpers : 0;
-  const hipError_t e = launch_schur(s, sub(s->stream, Extent{w0, n, helpers}));
+  const hipError_t e = launch_schur(s, sub(s->stream, Extent{w0, n, helpers}), 0, false);
   if (e != hipSuccess) return e;
   if (lds_windows && s->plan.solve.k) launch_solve_kernel(s, s->plan.solve, dim3((unsigned)n, 1 + helpers), s->stream, d_wins, 2, s->d_ctrl + w0);
   return hipGetLastError();
