@@ -845,7 +845,10 @@ int okvis_ba_dense_solve(int device, int32_t n, const double* S, const double* r
  * two solvers; D <= the LDS solver's limit, (D - Dp) a multiple of 9).  S: D x D symmetric, row-major; Dp: rows of the pose part
  * (pose-type blocks first, then 9-row speed/bias blocks).  mode: OKVIS_BA_SOLVE_DENSE = blocked LDL^T of the whole system,
  * OKVIS_BA_SOLVE_CHAIN = speed/bias blocks eliminated along the chain first — S must then have the chain structure (a speed/bias
- * block couples only to its two neighbours and to poses).  comp_mask: diagonal 16-blocks eliminated with compensated products (of
+ * block couples only to its two neighbours and to poses).  In chain mode OKVIS_BA_ERR_ARG is returned before any device call
+ * when a speed/bias block of S couples beyond its neighbours (a non-zero entry of such a block, in either triangle), and when the
+ * shape (D, Dp) is one okvis_ba_upload would not lay out for the chain solver (more than three 64-column chunks of pose columns,
+ * or more LDS than the chain solve launch may ask for, e.g. (174, 120)); the dense mode takes every D up to the limit.  comp_mask: diagonal 16-blocks eliminated with compensated products (of
  * the whole system / of the pose system).  ticks: device clock ticks of one solve (mean over `repeats`); info: 1 = a pivot was not
  * positive.  lds_dump (NULL or lds_capacity doubles, at most 20 000 are needed): the solver's LDS image after the solve. */
 int okvis_ba_reduced_solve(int device, int32_t D, int32_t Dp, int32_t mode, uint32_t comp_mask, const double* S, const double* rhs,

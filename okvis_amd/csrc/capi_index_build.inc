@@ -1190,6 +1190,25 @@ int build_batch(const okvis_ba_window* w, int n, const okvis_ba_options& o, Batc
       i = -1;
     } else if (rc != OKVIS_BA_OK)
       return rc;
+    // The chain solve launch is sized from the batch's largest LChain::total and its largest padded dimension (batch_max,
+    // make_plan), which may come from different windows: every window fits alone (BuildCtx::layout) and the pair does not.
+    // Such a batch is answered like one with an unfit window: the dense layout for every window.  (Reached under a forced
+    // SOLVE_CHAIN only: every pair that overflows contains the shape (156, 120), whose four speed/bias blocks are fewer than
+    // CHAIN_AUTO_MIN_BLOCKS, so that under AUTO the per-window rule has sent the batch to the dense layout already.)
+    if (i == n - 1 && L.chain) {
+      int chain_doubles = 0, Dpad = 0;
+      for (int k = 0; k < n; ++k) {
+        const WinPtrs& Pk = H[k].ptrs;
+        if (Pk.D > MAX_D_LDS) continue;
+        Dpad = std::max(Dpad, ((Pk.D + 5) / 6) * 6);
+        if (Pk.chain) chain_doubles = std::max(chain_doubles, LChain::make(Pk.D, Pk.Dp).total);
+      }
+      if (chain_doubles > 0 && (int)solve_smem_chain(chain_doubles, Dpad) > SOLVE_LDS_LIMIT_CHAIN) {
+        L.chain = false;
+        A.size = A.zsize = 0;
+        i = -1;
+      }
+    }
   }
   L.split_small = L.split_small && L.lin2;
   return OKVIS_BA_OK;

@@ -102,6 +102,18 @@ int okvis_ba_reduced_solve(int device, int32_t D, int32_t Dp, int32_t mode, uint
   if (D <= 0 || D > MAX_D_LDS || Dp < 0 || Dp > D || (D - Dp) % 9 != 0 || !S || !rhs || !x || !info) return OKVIS_BA_ERR_ARG;
   const bool chain = mode == OKVIS_BA_SOLVE_CHAIN;
   if (chain && (Dp < 6 || D == Dp || !LChain::tiles_fit(Dp))) return OKVIS_BA_ERR_ARG;
+  if (chain) {
+    // the fit rule of the index build (BuildCtx::layout): what the upload refuses for LDS is not launched here either
+    if ((D - Dp) / 9 > CH_MAX_KS || (int)solve_smem_chain(LChain::make(D, Dp).total, ((D + 5) / 6) * 6) > SOLVE_LDS_LIMIT_CHAIN)
+      return OKVIS_BA_ERR_ARG;
+    // the chain structure: a speed/bias block couples to its two neighbours only.  LChain::at sends every other coupling to the
+    // always-zero words at oZ, which the sweeps read as zeros: the solve would return a wrong x with info = 0
+    for (int i = Dp; i < D; ++i)
+      for (int j = Dp; j < D; ++j) {
+        const int a = (i - Dp) / 9, b = (j - Dp) / 9;
+        if ((a > b + 1 || b > a + 1) && S[(size_t)i * D + j] != 0.0) return OKVIS_BA_ERR_ARG;
+      }
+  }
   if (hipSetDevice(device) != hipSuccess) return OKVIS_BA_ERR_NO_DEVICE;
   if (repeats < 1) repeats = 1;
   auto chk = [](hipError_t err) { return err == hipSuccess ? OKVIS_BA_OK : OKVIS_BA_HIP_ERROR_BASE + (int)err; };

@@ -48,8 +48,11 @@ def is_chain_structured(H, Dp):
     return True
 
 
-def chain_solve(H, g, Dp):
-    """x with H x = g by the steps of ba_chain.hpp::chain_solve"""
+def chain_solve(H, g, Dp, mutation=None, pose_solver=np.linalg.solve):
+    """x with H x = g by the steps of ba_chain.hpp::chain_solve.  mutation (tests/solve_statement.MUTATIONS_CHAIN): the same steps
+    broken the way a kernel could be, for the tests that show the cases notice; pose_solver: what solves the pose system (the
+    kernel: ldl16_solve)"""
+    assert mutation in (None, "drop_col_64", "drop_col_128", "no_share", "transpose_coupling")
     D = H.shape[0]
     Ks = (D - Dp) // 9
     nL, nR, mid = Ks // 2, (Ks - 1) // 2, Ks // 2
@@ -75,6 +78,8 @@ def chain_solve(H, g, Dp):
             k = t if side == 0 else Ks - 1 - t
             n = k + 1 if side == 0 else k - 1
             M = H[sb(k), sb(n)]                         # rows: block k, columns: block n
+            if mutation == "transpose_coupling" and side == 0 and t == 0:
+                M = M.T
             L, d = ldl(A[k])
             P[k], Dinv[k] = np.linalg.inv(L), 1.0 / d
             RC[k] = P[k] @ M
@@ -88,19 +93,24 @@ def chain_solve(H, g, Dp):
             else:
                 A[n] = A[n] - upd_A
                 N[n] = N[n] - upd_N
-    A[mid] = A[mid] + contrib_A
-    N[mid] = N[mid] + contrib_N
+    if mutation != "no_share":
+        A[mid] = A[mid] + contrib_A
+        N[mid] = N[mid] + contrib_N
     L, d = ldl(A[mid])
     P[mid], Dinv[mid] = np.linalg.inv(L), 1.0 / d
     N[mid] = P[mid] @ N[mid]
     # the pose system
     Spp = H[:Dp, :Dp].copy()
     rp = g[:Dp].copy()
+    drop = {"drop_col_64": 64, "drop_col_128": 128}.get(mutation)
     for k in range(Ks):
         Y = N[k]
+        if drop is not None and drop <= Dp:
+            Y = Y.copy()
+            Y[:, drop] = 0.0                            # (the update alone loses the column: the back-substitution keeps it)
         Spp -= Y[:, :Dp].T @ (Dinv[k][:, None] * Y[:, :Dp])
         rp -= Y[:, :Dp].T @ (Dinv[k] * Y[:, Dp])
-    xp = np.linalg.solve(Spp, rp)
+    xp = pose_solver(Spp, rp)
     x = np.zeros(D)
     x[:Dp] = xp
     u = [N[k][:, Dp] - N[k][:, :Dp] @ xp for k in range(Ks)]
