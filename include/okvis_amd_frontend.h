@@ -70,8 +70,16 @@
  *                                absolute threshold, greedy selection of the strongest that keeps them min_dist apart, many images
  *                                per call; exact integer arithmetic.  Stated in this header, not pinned to BRISK
  *
- * What stays with the caller is what needs the estimator's book-keeping or the descriptor extractor: which keypoints carry a
- * landmark, addLandmark / addObservation, BRISK's descriptors (and scale space, octaves > 0).  G =PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
+ *   okvis_fe_describe_keypoints  Frame::describe (okvis_cv/include/okvis/implementation/Frame.hpp:128-156) behind the detector: the keypoint's
+ *                                angle from the extraction direction (gravity in the camera frame) through the projection Jacobian, as
+ *                                the reference computes it, and a 48-byte binary descriptor at that angle and a fixed scale, many
+ *                                images per call; every descriptor byte exact.  The extractor is stated in this header from the
+ *                                published BRISK construction, not pinned to BRISK
+ *   okvis_fe_detect_and_describe the whole of Frontend::detectAndDescribe: the two entries above in one call, the images staged once,
+ *                                the describe kernels reading the selected keypoints where the detect kernels left them
+ *
+ * What stays with the caller is what needs the estimator's book-keeping: which keypoints carry a landmark, addLandmark /
+ * addObservation; and BRISK's own scale space and bit selection (octaves > 0, scale invariance).  G =PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
  * Plain pointers and sizes, int status codes (okvis_amd_ba.h), host buffers in and out; no CPU path.
  */
@@ -651,6 +659,93 @@ typedef struct okvis_fe_detect_job { /* one grey image */
  * image or kp, width or height outside 5..OKVIS_FE_DETECT_MAX_DIM, pitch < width, threshold < 1, min_dist < 0, max_keypoints or
  * cand_capacity outside their limits.  n_jobs = 0 is valid and touches nothing. */
 int okvis_fe_detect_keypoints(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_job* jobs);
+
+#define OKVIS_FE_DESCRIBE_VALID 1u           /* the keypoint lies inside the 11-pixel margin: its descriptor row is written           */
+#define OKVIS_FE_DESCRIBE_ANGLE_UNDEFINED 2u /* backProject failed, the projection's distortion is undefined or eg is not finite:
+                                                rot = 0, angle = 0, and the descriptor is still computed (at rot 0)                  */
+#define OKVIS_FE_DESCRIBE_BYTES 48           /* PopcntofXORed(..., 3) of VioKeyframeWindowMatchingAlgorithm.hpp:253: 3 x 128 bits     */
+#define OKVIS_FE_DESCRIBE_ROTATIONS 1024
+#define OKVIS_FE_DESCRIBE_PAIRS 383
+
+typedef struct okvis_fe_describe_job { /* one grey image and its keypoints */
+  const uint8_t* image;  /* as okvis_fe_detect_job: row y starts at image + y * pitch        */
+  int32_t width, height; /* 5 .. OKVIS_FE_DETECT_MAX_DIM each                                */
+  int32_t pitch;         /* bytes, >= width                                                  */
+  int32_t n;             /* >= 0 keypoints                                                   */
+  const float* kp;       /* [n][3] x, y, size as everywhere; the size is not read            */
+  const okvis_fe_camera* cam; /* the camera of the angle stage; may be NULL with rot_in      */
+  double direction[3];   /* the extraction direction in the camera frame: C_CW * (0, 0, -1)  */
+  const int32_t* rot_in; /* [n] in 0..1023, or NULL.  Given: the angle stage is skipped, rot = rot_in, angle and angle64 are not
+                            written and ANGLE_UNDEFINED is never set                           */
+  /* out */
+  int32_t n_valid;       /* keypoints with VALID                                             */
+  uint8_t* desc;         /* [n][48]: what the matching entries take as descriptors; an invalid keypoint's row is zero             */
+  uint8_t* flags;        /* [n] OKVIS_FE_DESCRIBE_*; the complement of VALID is the matching entries' skip mask                   */
+  int32_t* rot;          /* [n] or NULL: the rotation index the descriptor was taken at                                           */
+  float* angle;          /* [n] or NULL: cv::KeyPoint::angle, degrees                                                             */
+  double* angle64;       /* [n] or NULL: the value before the cast to float.  A referee's output                                  */
+} okvis_fe_describe_job;
+
+/* Frame::describe (okvis_cv/include/okvis/implementation/Frame.hpp:128-156) for many images per call: the angle of every keypoint,
+ * then brisk::BriskDescriptorExtractor(rotationInvariance = true, scaleInvariance = false)::compute at that angle.
+ *
+ * ANGLE (pinned to the reference, Frame.hpp:139-150; fp64, operation for operation, no fused multiply-adds in this stage's own
+ * arithmetic): backProject(kp.x, kp.y) -> ep; project(ep, &reprojection, &Jacobian) (implementation/PinholeCamera.hpp:148-226);
+ * eg = Jacobian * direction; angle64 = atan2(eg[1], eg[0]) / M_PI * 180.0; angle = (float)angle64;
+ * The last expression is the one place where the entry is MORE exact than the reference's three roundings (which leave a double up
+ * to 2 ulp from the expression's value): it is evaluated in double-double from the doubles eg[1], eg[0] and rounded once, so
+ * angle64 is the double nearest to atan2(eg[1], eg[0]) / M_PI * 180 with M_PI the double.  (A zero component of eg takes the three
+ * plain operations, whose result is exact there: 0, +-90, +-180.)
+ * rot = ((int)floor((double)angle * 1024.0 / 360.0 + 0.5)) mod 1024, in 0..1023.  All four OKVIS_BA_DIST_* models.  The reference does
+ * not read backProject's status; here a failed backProject, an undefined distortion in the projection (the reference then reads a
+ * Jacobian it never wrote) or a non-finite eg sets ANGLE_UNDEFINED, rot = 0, angle = angle64 = 0, and the descriptor is still
+ * computed.  A job may pass rot_in instead: the stage is skipped and cam may be NULL.
+ *
+ * EXTRACTION.  BRISK's source is not part of the reference tree (it is fetched at build time): the extractor is stated here from the
+ * published BRISK construction and is NOT pinned to BRISK.  It is integer arithmetic, so every descriptor byte is exact.
+ * Fixed tables (tools/gen_describe_tables.py, from a 60-digit evaluation, rounded to nearest, half away from zero; handed out by
+ * okvis_fe_describe_tables):
+ *   pattern    60 points on 5 rings, N = (1, 10, 14, 15, 20) points per ring at radii r = 0.85 * (0, 2.9, 4.9, 7.4, 10.8) pixels; point a of
+ *              ring m at angle 2 pi a / N_m; the index k runs ring by ring, a ascending; base[60][2] = round(65536 * (x, y)) (Q16, int32).
+ *   boxes      half widths in sixteenths of a pixel (Q4) per ring: h = (10, 16, 19, 27, 30) = round(16 * 1.3 r_m sin(pi / N_m)), 0.65 px
+ *              for the centre; A_k = (2 h_ring(k))^2.
+ *   rotations  cs[1024][2] = round(2^30 * (cos, sin)(2 pi j / 1024)); cs[(j + 256) mod 1024] = (-s_j, c_j) exactly.
+ *   pairs      all (i, k), i < k, whose unrotated distance is below 5.1 pixels, in ascending (i, k) order: 383 of them (the nearest
+ *              distances on either side are 5.0835 and 5.1166, so no rounding decides it).  Descriptor bit b is pair b, stored in
+ *              byte b >> 3 at bit b & 7; bit 383 is always 0.
+ * Per keypoint, with w = width, h = height:
+ *   position   qx = (int64)floor((double)kp.x * 16.0 + 0.5), the same for qy.  VALID iff kp.x, kp.y are finite and
+ *              176 <= qx <= 16 (w - 1) - 176 and 176 <= qy <= 16 (h - 1) - 176: an 11-pixel margin.  Pixel x covers [16 x - 8, 16 x + 8)
+ *              and the tables' largest reach |offset| + h is 177, so no sample box leaves the image.  An invalid keypoint gets an
+ *              all-zero descriptor row and no VALID flag; it keeps its index (the reference would remove it).
+ *   offsets    with (c, s) = cs[rot] and (bx, by) = base[k]: dx = R(c bx - s by), dy = R(s bx + c by) in int64,
+ *              R(z) = sign(z) * ((|z| + 2^41) >> 42): Q46 to Q4, half away from zero (the symmetric rounding makes a quarter turn of
+ *              the image exact).  Centre (cx, cy) = (qx + dx, qy + dy).
+ *   sample     V_k = sum_y sum_x I[y][x] wy(y) wx(x), wx(x) = max(0, min(16 x + 8, cx + h_k) - max(16 x - 8, cx - h_k)), wy likewise: the
+ *              area-weighted box of side 2 h_k around the centre; sum wx = 2 h_k; V <= 255 * 3600 < 2^20.
+ *   bit        for pair (i, k): V_i A_k > V_k A_i, the two means compared by cross-multiplication (products below 3.4e9: int64).
+ * Not here: scale invariance and octaves > 0, BRISK's own bit selection, masks.
+ *
+ * One staging copy in (the images as in okvis_fe_detect_keypoints, keypoints, cameras); describe_angle_kernel, one lane per keypoint;
+ * describe_kernel, one wave per keypoint: its 25 x 25 pixels in LDS, lane k < 60 computes V_k, six ballots are the descriptor; one copy
+ * back.  Rows of desc, flags, rot, angle, angle64 past n are left alone.  The results do not depend on the batch around a job.
+ * OKVIS_BA_ERR_ARG before anything is enqueued and with nothing written: a NULL context or table, a negative job count, a NULL image,
+ * kp, desc or flags, n < 0, width or height outside 5..OKVIS_FE_DETECT_MAX_DIM, pitch < width, cam NULL (or not a camera) with rot_in
+ * NULL, a rot_in entry outside 0..1023.  n_jobs = 0 and n = 0 are valid. */
+int okvis_fe_describe_keypoints(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_describe_job* jobs);
+
+/* Frontend::detectAndDescribe (okvis_frontend/src/Frontend.cpp:92-114) in one call: okvis_fe_detect_keypoints on det[j], then
+ * okvis_fe_describe_keypoints on the keypoints it selected, with det[j]'s image.  The images are staged once, the two detect kernels
+ * run unchanged, the describe kernels read the selected keypoints where detect_select_kernel left them in device memory; one copy
+ * back.  In desc[j], image, width, height, pitch, kp and n are ignored (taken from det[j]); desc, flags, rot, angle, angle64 and rot_in
+ * have det[j].max_keypoints rows, of which the first det[j].n_keypoints are read and written.  A job with OVERFLOW describes nothing
+ * (n_valid = 0).  Every result equals, byte for byte, that of the two calls in sequence.  OKVIS_BA_ERR_ARG as for the two entries. */
+int okvis_fe_detect_and_describe(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_job* det, okvis_fe_describe_job* desc);
+
+/* The library's own tables, for tests: cs [1024][2], base [60][2], ring [60], half [5], pairs [*n_pairs][2].  OKVIS_BA_ERR_ARG on a
+ * NULL argument. */
+int okvis_fe_describe_tables(const int32_t** cs, const int32_t** base, const uint8_t** ring, const int32_t** half, const uint8_t** pairs,
+                             int32_t* n_pairs);
 
 #ifdef __cplusplus
 }

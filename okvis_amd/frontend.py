@@ -3,8 +3,9 @@ with uncertainty, 3D-2D projection and chi-square gating), its descriptor matchi
 best-match search), whole verified matching steps (the matcher under "Hamming distance and verifyMatch"), the outlier rejection
 behind it (bearing vectors, consensus scoring, the two-point and five-point solvers of the 2D-2D problems, the generalised
 three-point solver of the 3D-2D problem, and whole RANSAC runs with the sampler and the adaptive loop on the device), the IMU state
-propagation with covariance and Jacobian, the keyframe decision (exact hulls, areas and inside counts) and keypoint detection
-(Harris scores, 3 x 3 maxima and greedy uniformity selection, exact) on the MI355X.  No CPU path."""
+propagation with covariance and Jacobian, the keyframe decision (exact hulls, areas and inside counts), keypoint detection
+(Harris scores, 3 x 3 maxima and greedy uniformity selection, exact) and keypoint description (the reference's gravity-aligned
+angle, a 48-byte binary descriptor stated in the header, exact) on the MI355X.  No CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -20,7 +21,8 @@ GATE_VERIFIED, GATE_ACCEPTED, GATE_UNCERTAIN = 1, 2, 4
 SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate", "okvis_fe_stereo_triangulate_gn", "okvis_fe_project_landmarks",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
            "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
-           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac", "okvis_fe_detect_keypoints"]
+           "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac", "okvis_fe_detect_keypoints",
+           "okvis_fe_describe_keypoints", "okvis_fe_detect_and_describe", "okvis_fe_describe_tables"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
@@ -35,6 +37,9 @@ DETECT_MAX_DIM, DETECT_MAX_KEYPOINTS, DETECT_MAX_CANDIDATES = 8192, 2048, 8192
 DETECT_TILE_X, DETECT_TILE_Y = 64, 16            # the score kernel's tile (fe_detect.hpp: DET_TILE_X, DET_TILE_Y)
 DETECT_WAVE, DETECT_SELECT_THREADS = 64, 1024    # the selection kernel's widths (DET_SEL_THREADS)
 DETECT_KP_SIZE = 12.0                            # BRISK's basic size at scale 1; okvis takes sigma = 0.8 size / 12
+DESCRIBE_VALID, DESCRIBE_ANGLE_UNDEFINED = 1, 2
+DESCRIBE_BYTES, DESCRIBE_ROTATIONS, DESCRIBE_PAIRS, DESCRIBE_POINTS = 48, 1024, 383, 60
+DESCRIBE_MARGIN = 176                            # sixteenths of a pixel (fe_describe.hpp: DSC_MARGIN)
 
 
 class CameraC(C.Structure):
@@ -122,6 +127,14 @@ class DetectJobC(C.Structure):
                 ("response", C.c_void_p), ("pixel", C.c_void_p), ("score", C.c_void_p)]
 
 
+class DescribeJobC(C.Structure):
+    """okvis_fe_describe_job"""
+    _fields_ = [("image", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("n", C.c_int32),
+                ("kp", C.c_void_p), ("cam", C.POINTER(CameraC)), ("direction", C.c_double * 3), ("rot_in", C.c_void_p),
+                ("n_valid", C.c_int32), ("desc", C.c_void_p), ("flags", C.c_void_p), ("rot", C.c_void_p), ("angle", C.c_void_p),
+                ("angle64", C.c_void_p)]
+
+
 def camera(intr, model, width=752, height=480) -> CameraC:
     c = CameraC()
     k = np.zeros(12)
@@ -185,6 +198,9 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_imu_propagate.argtypes = [vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, C.POINTER(ImuJobC), vp, vp, vp, vp, vp]
         L.okvis_fe_keyframe_decision.argtypes = [vp, i32, vp, vp, i32, C.POINTER(KfImageC), i32, C.POINTER(KfJobC)] + [vp] * 12
         L.okvis_fe_detect_keypoints.argtypes = [vp, i32, C.POINTER(DetectJobC)]
+        L.okvis_fe_describe_keypoints.argtypes = [vp, i32, C.POINTER(DescribeJobC)]
+        L.okvis_fe_detect_and_describe.argtypes = [vp, i32, C.POINTER(DetectJobC), C.POINTER(DescribeJobC)]
+        L.okvis_fe_describe_tables.argtypes = [C.POINTER(vp)] * 5 + [C.POINTER(i32)]
 
 
 class Frontend:
@@ -449,6 +465,51 @@ class Frontend:
         return detect_results(table, out)
 
 
+    def describe_keypoints(self, images, kps, cams=None, directions=None, rot=None, want=("rot", "angle")):
+        """Gravity-aligned 48-byte binary descriptors for the keypoints of many images in one call (okvis_fe_describe_keypoints; the
+        angle is the reference's Frame::describe, the extractor is stated in the header and is not BRISK's).  images: as for
+        detect_keypoints; kps: per image [n][3] (or [n][2]) float32; cams, directions: one CameraC and one 3-vector (the extraction
+        direction in the camera frame, C_CW (0, 0, -1)) for all or per image; rot: per image [n] indices in 0..1023 instead, which
+        skips the angle stage (an entry may be None where the camera is to be used).  want: the optional outputs among rot, angle,
+        angle64.
+        -> per image a dict: desc [n][48] uint8, flags [n] uint8 (DESCRIBE_VALID | DESCRIBE_ANGLE_UNDEFINED), n_valid and what was
+        asked for (angle and angle64 only where the angle stage ran)."""
+        table, keep, out = describe_job_table(images, kps, cams, directions, rot, want)
+        self._call("describe_keypoints", len(out), table)
+        return describe_results(table, out)
+
+    def detect_and_describe(self, images, threshold, cams=None, directions=None, min_dist=40, max_keypoints=400,
+                            cand_capacity=DETECT_MAX_CANDIDATES, kp_size=DETECT_KP_SIZE, want_score=False, rot=None, want=("rot", "angle")):
+        """Frontend::detectAndDescribe in one call (okvis_fe_detect_and_describe): detect_keypoints, then describe_keypoints on what it
+        selected, the images staged once.  rot: per image [max_keypoints] indices instead of cameras (a referee's input).
+        -> the dicts of detect_keypoints extended by desc, flags, n_valid and what `want` names, cut to n_keypoints rows.  `flags`
+        is the describe entry's array (one byte per keypoint); the detector's flags of the image are under `detect_flags`."""
+        det, keep, out = detect_job_table(images, threshold, min_dist, max_keypoints, cand_capacity, kp_size, want_score)
+        rows = [det[j].max_keypoints for j in range(len(out))]
+        table, keep2, out2 = describe_job_table(images, [np.zeros((r, 3), np.float32) for r in rows], cams, directions, rot, want)
+        self._call("detect_and_describe", len(out), det, table)
+        res = detect_results(det, out)
+        for j, r in enumerate(res):
+            table[j].n = det[j].n_keypoints
+        for r, d in zip(res, describe_results(table, out2)):
+            r["detect_flags"] = r.pop("flags")
+            r.update(d)
+        return res
+
+
+def describe_tables():
+    """the library's own tables (okvis_fe_describe_tables) -> dict of int64 arrays: cs [1024][2], base [60][2], ring [60], half [5],
+    pairs [n_pairs][2]"""
+    L = _lib.lib()
+    declare(L)
+    p = [C.c_void_p() for _ in range(5)]
+    n = C.c_int32()
+    _lib.check(L.okvis_fe_describe_tables(*[C.byref(x) for x in p], C.byref(n)), "describe_tables")
+    arr = lambda ptr, ctype, shape: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=shape).astype(np.int64)
+    return {"cs": arr(p[0], C.c_int32, (DESCRIBE_ROTATIONS, 2)), "base": arr(p[1], C.c_int32, (DESCRIBE_POINTS, 2)),
+            "ring": arr(p[2], C.c_uint8, (DESCRIBE_POINTS,)), "half": arr(p[3], C.c_int32, (5,)), "pairs": arr(p[4], C.c_uint8, (n.value, 2))}
+
+
 def landmark_covariance_in_camera(Sigma, T_CW):
     """A landmark's covariance rotated into a camera frame: ``R Sigma R^T``, R the rotation of T_CW (world to camera).  Sigma
     [..., 3, 3]: what ``WindowBatch.landmark_covariance()`` returns for a landmark (divided by w^2 when the stored homogeneous
@@ -579,6 +640,68 @@ def detect_results(table, out):
         if o["score"] is not None:
             r["score"] = o["score"]
         r.update(n_candidates=int(table[j].n_candidates), flags=int(table[j].flags))
+        res.append(r)
+    return res
+
+
+DESCRIBE_OUTPUTS = ("desc", "flags", "rot", "angle", "angle64")
+
+
+def describe_job_table(images, kps, cams=None, directions=None, rot=None, want=("rot", "angle"), leave_out=()):
+    """-> (okvis_fe_describe_job array, what has to outlive the call, the output arrays per job by name (DESCRIBE_OUTPUTS; None
+    where not asked for or named in leave_out)).  An image is passed as it lies in memory."""
+    n = len(images)
+    per = lambda v: list(v) if isinstance(v, (list, tuple)) else [v] * n
+    cams, rots = per(cams), per(rot)
+    dirs = [None] * n if directions is None else (list(np.asarray(directions, np.float64)) if np.ndim(directions) == 2 else [directions] * n)
+    table, keep, out = (DescribeJobC * max(1, n))(), [], []
+    for j, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1) or im.strides[0] < im.shape[1]:
+            raise ValueError("an image is a 2-D uint8 array with contiguous columns and a pitch of at least its width")
+        kp = np.asarray(kps[j], np.float32)
+        kp = kp.reshape(-1, kp.shape[-1] if kp.ndim == 2 else 3)
+        if kp.shape[1] == 2:
+            kp = np.concatenate([kp, np.zeros((len(kp), 1), np.float32)], axis=1)
+        if kp.shape[1] != 3:
+            raise ValueError("keypoints are [n][3] or [n][2]")
+        kp = np.ascontiguousarray(kp, np.float32)
+        rows = len(kp)
+        t = table[j]
+        t.image, t.height, t.width, t.pitch, t.n = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0], rows
+        kp_mem = kp if rows else np.zeros((1, 3), np.float32)          # a pointer even for no keypoints
+        t.kp = kp_mem.ctypes.data
+        r_in = None
+        if rots[j] is not None:
+            r_in = np.ascontiguousarray(rots[j], np.int32).reshape(-1)
+            if len(r_in) != rows:
+                raise ValueError("rot has one entry per keypoint")
+            r_in = r_in if rows else np.zeros(1, np.int32)
+            t.rot_in = r_in.ctypes.data
+        if cams[j] is not None:
+            t.cam = C.pointer(cams[j])
+            t.direction[:] = [float(v) for v in np.asarray(dirs[j], np.float64).reshape(3)]
+        elif r_in is None:
+            raise ValueError("a job needs a camera and a direction, or rot")
+        room = max(1, rows)
+        o = {"desc": np.zeros((room, DESCRIBE_BYTES), np.uint8), "flags": np.zeros(room, np.uint8),
+             "rot": np.zeros(room, np.int32) if "rot" in want else None, "angle": np.zeros(room, np.float32) if "angle" in want else None,
+             "angle64": np.zeros(room, np.float64) if "angle64" in want else None}
+        for k in leave_out:
+            o[k] = None
+        t.desc, t.flags, t.rot, t.angle, t.angle64 = (_ptr(o[k]) for k in DESCRIBE_OUTPUTS)
+        keep += [im, kp_mem, r_in, cams[j]]
+        out.append(o)
+    return table, keep, out
+
+
+def describe_results(table, out):
+    """the filled arrays of describe_job_table as one dict per image, cut to n rows; angle and angle64 only where the stage ran"""
+    res = []
+    for j, o in enumerate(out):
+        n = table[j].n
+        skip = ("angle", "angle64") if table[j].rot_in else ()
+        r = {k: o[k][:n].copy() for k in DESCRIBE_OUTPUTS if o[k] is not None and k not in skip}
+        r["n_valid"] = int(table[j].n_valid)
         res.append(r)
     return res
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry (the sixteen of the header; create and destroy by way of the context) is called through okvis_amd.frontend;
+Every okvis_fe_* entry (the eighteen of the header, the table query aside; create and destroy by way of the context) is called through okvis_amd.frontend;
 every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
 in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
 whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
@@ -38,6 +38,9 @@ itself is in; nothing outside it is read.
   detect              every family of detect_cases.NAMES with and without the score image, every job alone and the family as one
                       call; the end-to-end scenes and the shifted images.  Left out where the tree under --root is from before
                       the entry
+  describe            every family of describe_cases.NAMES, the stereo pair, the shifted and the turned images with given
+                      rotations, every job alone and the family as one call; the angle cases of the four camera models; the
+                      chain on detect families.  Left out where the tree under --root is from before the entries
 """
 import argparse
 import ctypes as C
@@ -357,6 +360,35 @@ if hasattr(fe, "detect_keypoints"):          # a tree from before the entry has 
                 record(f"detect/{tag}_job{j}", **det_arrays(r))
             for j, r in enumerate(detect(jobs, want_score)):
                 record(f"detect_batch/{tag}_job{j}", **det_arrays(r))
+
+# ---------------------------------------------------------------- keypoint description
+if hasattr(fe, "describe_keypoints"):        # a tree from before the entries has every other group
+    import describe_cases as BC  # noqa: E402
+
+    ALL = ("rot", "angle", "angle64")
+
+    def describe(jobs):
+        return fe.describe_keypoints([j["image"] for j in jobs], [j["kp"] for j in jobs], rot=[j["rot"] for j in jobs], want=ALL)
+
+    families = {name: BC.cases(name) for name in BC.NAMES}
+    families["scene"] = BC.scene()
+    families["shifts"] = [BC.shifted(dx, dy) for dx, dy in BC.SHIFTS]
+    families["turn"] = list(BC.quarter_turn())
+    for name, jobs in families.items():
+        for j, job in enumerate(jobs):
+            r, = describe([job])
+            record(f"describe/{name}_job{j}", **det_arrays(r))
+        for j, r in enumerate(describe(jobs)):
+            record(f"describe_batch/{name}_job{j}", **det_arrays(r))
+    angle_image = BC.textured(70, BC.ANGLE_IMAGE_SHAPE[1], BC.ANGLE_IMAGE_SHAPE[0])
+    for c in BC.angle_cases():
+        r, = fe.describe_keypoints([angle_image], [c["kp"]], F.camera(c["cam"]["intr"], c["cam"]["model"]), c["direction"], want=ALL)
+        record(f"describe_angle/{c['name'].replace('/', '_')}", **det_arrays(r))
+    chain = DC.cases("selection") + DC.cases("capacity") + DC.cases("mixed")[:20]
+    cam = F.camera(BC.CAMERAS["equi"]["intr"], 2, 160, 120)
+    fields = [[j[k] for j in chain] for k in ("threshold", "min_dist", "max_keypoints", "cand_capacity", "kp_size")]
+    for j, r in enumerate(fe.detect_and_describe([j["image"] for j in chain], fields[0], cam, [0.2, 0.9, 0.38], *fields[1:], want=ALL)):
+        record(f"describe_chain/job{j}", **det_arrays(r))
 fe.close()
 
 if args.cases:
