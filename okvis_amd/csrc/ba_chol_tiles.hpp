@@ -181,9 +181,17 @@ __device__ void ct_ldl_inv48(double* M, double* X, double* R, double* dinv, int 
         c[i] = M[(16 * b + hi) * CT_LD + 16 * b + lo];
       }
       bool bad = false;
-      // (guarded: a pivot that is not positive becomes 1, the tile reports failure.  Not compensated — ba_ldl16.hpp, ldl16_pivot<.., COMP>:
-      //  a second instantiation in this kernel costs 41 registers, scratch and half the occupancy, configs[2] 327 -> 398 us per solve,
-      //  and two D = 300 windows showed nothing to gain against the long double referee, profiles/r05_referee_large.txt)
+      // (guarded: a pivot that is not positive is left out of the elimination, the tile reports failure.  Not compensated —
+      //  ba_ldl16.hpp, ldl16_pivot<.., COMP>: a second instantiation in this kernel costs 41 registers, scratch and half the
+      //  occupancy, configs[2] 327 -> 398 us per solve.  What that leaves, measured by tests/test_gpu_tiles_referee.py
+      //  (profiles/tiles_referee_notes.md): behind a prior 1e16 n n^T inside ONE 16-block (rows 3 .. 5, where the project's yaw prior
+      //  sits) the scaled residual rho is 6.3e-15 .. 6.1e-13, 600 to 40 000 times the better fp64 peer's and 76 to 7400 times the
+      //  family's reference — exactly what the CPU restatement of this arithmetic gives (tests/tiles_statement.py) — while the error
+      //  of x stays inside the peers' own scatter (0.06 .. 4.1 times the better peer's, at most 0.22 of the family's reference);
+      //  the same prior across a tile edge (rows 46 .. 48) is an ordinary case, rho 0.3 .. 3.1 times the better peer's.  The gap in
+      //  rho is recorded, not closed: on the referee's windows (D = 180 .. 240, one LM or dogleg iteration) the step stays within
+      //  2.5 x the peers' e and 1.5 x their rho, and the referee holds e alone on those three cases.  ADVICE.md has the way to
+      //  close it.)
       ldl16_eliminate<true, true>(c, 16, mine, j, &bad);
       if (bad && lane == 0) *s_fail = 1;
       if (lane < 16) {

@@ -220,13 +220,17 @@ __device__ __forceinline__ void ldl_operand(const double* Xk, const double* dk, 
 // d = r[K] of lane K (already broadcast).  FULL: all 16 pivots exist; otherwise act = (K < npiv) and an inactive step
 // changes nothing.  Lane K keeps 1 / d_K (0 when inactive) in `mine`.  Returns the next pivot, broadcast as soon as its
 // entry is final so that its reciprocal (the dependent chain) overlaps the remaining updates of this step.
-// GUARD: a pivot that is not positive is replaced by 1 (everything stays finite; the caller reports the failure).
+// GUARD: a pivot that is not positive (or not a number) is left out like an inactive one — 1 / d = 0: no update, its row of the
+// inverse factor scaled to zero — and the caller reports the failure.  (Until the tile referee it was replaced by 1 "so that
+// everything stays finite": it does not — the multipliers of a dense block, some 1e2, are squared into what is left at every later
+// pivot that fails in turn, and eight of them overflow.  tests/test_gpu_tiles_referee.py: x was not a number for a pivot of -1 or
+// 0 anywhere in front of the last tile of a dense 97 or 144 system.)
 template <int K, bool FULL, bool GUARD = false, bool COMP = false>
 __device__ __forceinline__ double ldl16_pivot(double (&r)[16], double d, bool act, double& mine, int j, bool* bad = nullptr) {
+  bool neg = false;
   if constexpr (GUARD) {
-    const bool neg = !(d > 0.0);
+    neg = !(d > 0.0);
     *bad = *bad || neg;
-    d = neg ? 1.0 : d;
   }
 #if LDL_PIVOT == 0
 #ifdef LDL_NR1
@@ -235,6 +239,7 @@ __device__ __forceinline__ double ldl16_pivot(double (&r)[16], double d, bool ac
   double rd = rcp_nr(d);
 #endif
   if (!FULL) rd = act ? rd : 0.0;
+  if constexpr (GUARD) rd = neg ? 0.0 : rd;   // (whatever the reciprocal of such a pivot is: the select takes none of it)
   const bool me = (j == K);
   double v = -r[K] * rd;
   double vl = 0.0;
@@ -257,6 +262,10 @@ __device__ __forceinline__ double ldl16_pivot(double (&r)[16], double d, bool ac
   if (!FULL) {
     rd = act ? rd : 0.0;
     v = act ? v : 0.0;
+  }
+  if constexpr (GUARD) {
+    rd = neg ? 0.0 : rd;
+    v = neg ? 0.0 : v;
   }
   const bool me = (j == K);
 #endif
