@@ -77,9 +77,12 @@
  *                                published BRISK construction, not pinned to BRISK
  *   okvis_fe_detect_and_describe the whole of Frontend::detectAndDescribe: the two entries above in one call, the images staged once,
  *                                the describe kernels reading the selected keypoints where the detect kernels left them
+ *   okvis_fe_detect_keypoints_scaled, okvis_fe_detect_scaled_and_describe   the same two with the detection option octaves > 0: the
+ *                                detector on every layer of a half-sampled pyramid, a raw score comparison across layers, the layer
+ *                                and a linear scale interpolation in kp.size; exact.  Stated in this header, not pinned to BRISK
  *
  * What stays with the caller is what needs the estimator's book-keeping: which keypoints carry a landmark, addLandmark /
- * addObservation; and BRISK's own scale space and bit selection (octaves > 0, scale invariance).  G =PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
+ * addObservation; and BRISK's own scale space and bit selection (intra-octaves, scale invariance).  G =PinholeCamera<D> with the distortion models of okvis_amd_ba.h.  The geometry is IEEE
  * double like the reference; keypoints are float like cv::KeyPoint; descriptor distances are integers, exact in float.
  * Plain pointers and sizes, int status codes (okvis_amd_ba.h), host buffers in and out; no CPU path.
  */
@@ -626,8 +629,8 @@ typedef struct okvis_fe_detect_job { /* one grey image */
  * for many images per call: brisk::ScaleSpaceFeatureDetector<brisk::HarrisScoreCalculator>(threshold, octaves, absoluteThreshold,
  * maxNoKeypoints) (:828-831) with octaves = 0 — a Harris score on the full-resolution image, a 3 x 3 maximum search above an absolute
  * threshold, a selection of the strongest maxima that keeps them apart.  BRISK's source is not part of the reference tree (it is
- * fetched at build time): the detector is stated here and is NOT pinned to BRISK.  Scale space (octaves > 0), descriptors and masks
- * are not here.  Images are 8-bit: the statement is integer arithmetic (int64 unless said otherwise) and every output is exact.
+ * fetched at build time): the detector is stated here and is NOT pinned to BRISK.  Descriptors and masks are not here; the scale
+ * space (octaves > 0) is okvis_fe_detect_keypoints_scaled's.  Images are 8-bit: the statement is integer arithmetic (int64 unless said otherwise) and every output is exact.
  * With I the image, w = width, h = height:
  *   derivatives  for 1 <= x <= w-2, 1 <= y <= h-2 (Sobel):
  *                Ix = (I[y-1][x+1] + 2 I[y][x+1] + I[y+1][x+1]) - (I[y-1][x-1] + 2 I[y][x-1] + I[y+1][x-1]),
@@ -724,7 +727,8 @@ typedef struct okvis_fe_describe_job { /* one grey image and its keypoints */
  *   sample     V_k = sum_y sum_x I[y][x] wy(y) wx(x), wx(x) = max(0, min(16 x + 8, cx + h_k) - max(16 x - 8, cx - h_k)), wy likewise: the
  *              area-weighted box of side 2 h_k around the centre; sum wx = 2 h_k; V <= 255 * 3600 < 2^20.
  *   bit        for pair (i, k): V_i A_k > V_k A_i, the two means compared by cross-multiplication (products below 3.4e9: int64).
- * Not here: scale invariance and octaves > 0, BRISK's own bit selection, masks.
+ * Not here: scale invariance (keypoints of coarser layers, okvis_fe_detect_keypoints_scaled, are described at this one scale too),
+ * BRISK's own bit selection, masks.
  *
  * One staging copy in (the images as in okvis_fe_detect_keypoints, keypoints, cameras); describe_angle_kernel, one lane per keypoint;
  * describe_kernel, one wave per keypoint: its 25 x 25 pixels in LDS, lane k < 60 computes V_k, six ballots are the descriptor; one copy
@@ -741,6 +745,82 @@ int okvis_fe_describe_keypoints(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_
  * have det[j].max_keypoints rows, of which the first det[j].n_keypoints are read and written.  A job with OVERFLOW describes nothing
  * (n_valid = 0).  Every result equals, byte for byte, that of the two calls in sequence.  OKVIS_BA_ERR_ARG as for the two entries. */
 int okvis_fe_detect_and_describe(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_job* det, okvis_fe_describe_job* desc);
+
+#define OKVIS_FE_DETECT_MAX_OCTAVES 4 /* the reference's detection option `octaves`: 0 .. 4, at most five layers */
+
+typedef struct okvis_fe_detect_scale_job { /* one grey image, detected on up to octaves + 1 layers */
+  const uint8_t* image;  /* the first nine fields are okvis_fe_detect_job's, with the same limits */
+  int64_t threshold;     /* the same on every layer                                             */
+  int32_t width, height;
+  int32_t pitch;
+  int32_t min_dist;      /* in full-resolution pixels                                           */
+  int32_t max_keypoints;
+  int32_t cand_capacity; /* holds for every layer's candidates and for the pooled survivors     */
+  float kp_size;         /* the size at scale 1: kp.size = (float)((double)kp_size * scale)     */
+  int32_t octaves;       /* 0 .. OKVIS_FE_DETECT_MAX_OCTAVES                                    */
+  /* out */
+  int32_t n_keypoints;
+  int32_t n_candidates;  /* the survivors of all layers, the true count; after a layer overflow see OVERFLOW below */
+  int32_t flags;         /* OKVIS_FE_DETECT_*                                                   */
+  int32_t n_layers;      /* the layers that exist: 1 .. octaves + 1                             */
+  int32_t n_layer_candidates[OKVIS_FE_DETECT_MAX_OCTAVES + 1]; /* per layer the true count of its candidates, 0 for a layer that does not exist */
+  float* kp;             /* [max_keypoints][3] x, y at full resolution, size: the first n_keypoints rows, in selection order */
+  double* response;      /* [max_keypoints] or NULL: (double)S, exact                                                       */
+  int32_t* pixel;        /* [max_keypoints][2] or NULL: x, y of the integer maximum in its layer's coordinates              */
+  int32_t* layer;        /* [max_keypoints] or NULL: the layer the keypoint was found on                                    */
+  double* scale;         /* [max_keypoints] or NULL: t 2^layer.  A referee's output                                         */
+  int64_t* score;        /* [sum_l h_l w_l] or NULL: the score images of all layers one behind the other, 0 outside their
+                            domains.  A referee's output                                                                    */
+  uint8_t* pyramid;      /* [sum_{l >= 1} h_l w_l] or NULL: the layers 1.. one behind the other.  A referee's output        */
+} okvis_fe_detect_scale_job;
+
+/* okvis_fe_detect_keypoints over a scale space: the detection option `octaves` > 0 of the reference's detector
+ * (config_fpga_p2_euroc.yaml:66-68, okvis_frontend/src/Frontend.cpp:828-831).  BRISK's source is not part of the reference tree: like
+ * the detector, the scale space is stated here from its definition and is NOT pinned to BRISK.  It is not BRISK's:
+ * no intra-octaves, a raw Harris comparison across layers, a linear scale interpolation.
+ * Integer arithmetic in int64 unless said otherwise; the double parts have no fused multiply-add; every output is exact.  With I the
+ * image, w_0 = width, h_0 = height:
+ *   pyramid      L_0 = I; w_{l+1} = w_l >> 1, h_{l+1} = h_l >> 1,
+ *                L_{l+1}[y][x] = (L_l[2y][2x] + L_l[2y][2x+1] + L_l[2y+1][2x] + L_l[2y+1][2x+1] + 2) >> 2; an odd last row or column is
+ *                dropped.  Layer l + 1 exists while l < octaves and w_{l+1} >= 5 and h_{l+1} >= 5; n_layers is the number that exist
+ *                (10 x 10: 10 x 10 and 5 x 5; 11 x 23: two layers; 9 x 9 and 20 x 9: one layer).
+ *   layer candidates  per layer exactly okvis_fe_detect_keypoints' definition on L_l with the same threshold: the score S_l, its domain
+ *                2 <= x <= w_l - 3, 2 <= y <= h_l - 3, "beats all eight neighbours" under (larger S, then lower row-major index of that
+ *                layer), the sub-pixel offsets dx, dy.  n_layer_candidates[l] is the true count.
+ *   cross-layer  a layer candidate (l, x, y, S) SURVIVES when it passes the below test and the above test.
+ *                below, if l >= 1: S > S_{l-1}[2y+j][2x+i] for all i, j in {-1, 0, 1, 2}, strictly: on a tie the finer layer wins.  These
+ *                16 pixels always lie in layer l-1's score domain: 2 <= x gives 2x - 1 >= 3 >= 2, and x <= w_l - 3 with 2 w_l <= w_{l-1}
+ *                gives 2x + 2 <= 2 w_l - 4 <= w_{l-1} - 4; the same for y.  s_m is their maximum.
+ *                above, if layer l+1 exists: S >= S_{l+1}[(y>>1)+j][(x>>1)+i] for those i, j in {-1, 0, 1} that lie in layer l+1's score
+ *                domain; s_p is their maximum.  If none of the nine does, that side counts as missing (it happens: with w_l odd, a
+ *                candidate at x = w_l - 3 has all three columns beyond the domain).
+ *                Survival depends on raw scores only, not on the threshold or on the other layers' candidate lists.
+ *   scale        d = the sub-pixel rule's d of (s_m, S, s_p) (num = s_m - s_p, den = 2 (s_m - 2 S + s_p), clamped to [-0.5, 0.5]) when both
+ *                sides are present, else d = 0; t = d >= 0 ? 1.0 + d : 1.0 + 0.5 * d (piecewise linear in the layer index: nothing
+ *                transcendental, so device, host compiler and numpy agree bit for bit); scale = t * 2^l;
+ *                kp.size = (float)((double)kp_size * scale).
+ *   position     with u = (double)x + dx: kp.x = (float)u for l = 0 and (float)((u + 0.5) * 2^l - 0.5) for l >= 1; the same for y.
+ *                pixel is the integer maximum in its layer's coordinates.
+ *   selection    the survivors of all layers are pooled; n_candidates is their number.  p BEATS q when S_p > S_q, else the lower
+ *                layer, else the lower row-major index.  Centres are taken in doubled full-resolution units, which are integers:
+ *                cx = ((2x + 1) << l) - 1, cy likewise; a survivor is ACCEPTABLE when (cx - cx')^2 + (cy - cy')^2 >= 4 min_dist^2 against
+ *                every accepted keypoint.  The rest is okvis_fe_detect_keypoints' rule (greedy, max_keypoints, FULL).  OVERFLOW: any
+ *                n_layer_candidates[l] > cand_capacity, or n_candidates > cand_capacity; no partial result.  After a layer overflow
+ *                the cross-layer test is not run and n_candidates is 0 -- unless there is one layer only, where every candidate
+ *                survives and n_candidates = n_layer_candidates[0], as okvis_fe_detect_keypoints reports it.
+ * octaves = 0 gives, for every output okvis_fe_detect_keypoints has, that entry's bytes.  The descriptors stay at the fixed scale
+ * (scaleInvariance = false): okvis_fe_describe_keypoints does not read the size.
+ * One staging copy in; detect_pyramid_kernel (one workgroup per 64 x 16 tile of layer 0, all its layers in LDS, written behind the images
+ * in the pixel pool); the unchanged detect_score_kernel on every (job, layer); detect_cross_kernel (the neighbouring layers' scores
+ * recomputed from pool pixels: no score image goes to memory unless asked for); detect_select_scaled_kernel; one copy back.  The
+ * results do not depend on the batch around a job or on the run.
+ * OKVIS_BA_ERR_ARG as for okvis_fe_detect_keypoints, and for octaves outside 0..OKVIS_FE_DETECT_MAX_OCTAVES. */
+int okvis_fe_detect_keypoints_scaled(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_scale_job* jobs);
+
+/* okvis_fe_detect_and_describe with okvis_fe_detect_keypoints_scaled as its detector: keypoints of every layer are described at the
+ * fixed scale, at their full-resolution position, in layer 0.  desc[j] as there.  Every result equals, byte for byte, that of the two
+ * calls in sequence; a job with OVERFLOW describes nothing.  OKVIS_BA_ERR_ARG as for the two entries. */
+int okvis_fe_detect_scaled_and_describe(okvis_fe_context* ctx, int32_t n_jobs, okvis_fe_detect_scale_job* det, okvis_fe_describe_job* desc);
 
 /* The library's own tables, for tests: cs [1024][2], base [60][2], ring [60], half [5], pairs [*n_pairs][2].  OKVIS_BA_ERR_ARG on a
  * NULL argument. */

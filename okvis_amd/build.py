@@ -22,10 +22,10 @@ UNITS = {
     "ba_capi.hip": BA_HEADERS,                                     # the bundle-adjustment path (include/okvis_amd_ba.h)
     "store_capi.hip": ["ba_store.hpp", "ba_results.hpp", os.path.join("..", "..", "include", "okvis_amd_ba.h")],   # host-side window container
     "dist_capi.hip": [os.path.join("..", "..", "include", "okvis_amd_ba.h")],   # record all-gather over RCCL (dlopen)
-    "fe_capi.hip": ["fe_kernels.hpp", "fe_match.hpp", "fe_sac.hpp", "fe_sac_solve.hpp", "fe_sac_gp3p.hpp", "fe_vmatch.hpp", "fe_propagate.hpp", "fe_keyframe.hpp", "fe_sac_loop.hpp", "fe_detect.hpp", "fe_describe.hpp", "fe_describe_tables.inc", "ba_math.hpp", os.path.join("..", "..", "include", "okvis_amd_frontend.h"),
+    "fe_capi.hip": ["fe_kernels.hpp", "fe_match.hpp", "fe_sac.hpp", "fe_sac_solve.hpp", "fe_sac_gp3p.hpp", "fe_vmatch.hpp", "fe_propagate.hpp", "fe_keyframe.hpp", "fe_sac_loop.hpp", "fe_detect.hpp", "fe_detect_scale.hpp", "fe_describe.hpp", "fe_describe_tables.inc", "ba_math.hpp", os.path.join("..", "..", "include", "okvis_amd_frontend.h"),
                     os.path.join("..", "..", "include", "okvis_amd_ba.h"),
                     # the parts of fe_capi.hip (one translation unit)
-                    "fe_capi_reprojection.inc", "fe_capi_matching.inc", "fe_capi_ransac.inc", "fe_capi_propagation.inc", "fe_capi_keyframe.inc", "fe_capi_ransac_loop.inc", "fe_capi_detect.inc", "fe_capi_describe.inc"],   # frontend pieces (include/okvis_amd_frontend.h)
+                    "fe_capi_reprojection.inc", "fe_capi_matching.inc", "fe_capi_ransac.inc", "fe_capi_propagation.inc", "fe_capi_keyframe.inc", "fe_capi_ransac_loop.inc", "fe_capi_detect.inc", "fe_capi_describe.inc", "fe_capi_detect_scale.inc"],   # frontend pieces (include/okvis_amd_frontend.h)
 }
 SOURCES = list(UNITS)
 HOST_SOURCES = [os.path.join("host", f) for f in ("estimator.hpp", "estimator.cpp", "replay.hpp", "replay.cpp", "replay_main.cpp", "okvis_config.hpp", "okvis_config.cpp",

@@ -26,6 +26,7 @@
 #include "fe_sac_loop.hpp"
 #include "fe_detect.hpp"
 #include "fe_describe.hpp"
+#include "fe_detect_scale.hpp"
 
 struct okvis_fe_context {
   int device = 0;
@@ -174,3 +175,4 @@ void okvis_fe_destroy(okvis_fe_context* c) {
 #include "fe_capi_ransac_loop.inc"    // whole RANSAC runs: the sampler and the loop around the solvers and the consensus stage
 #include "fe_capi_detect.inc"         // keypoint detection: Harris scores and candidates per tile, selection per image
 #include "fe_capi_describe.inc"       // keypoint description: the angle and the descriptor, alone and chained behind the detection
+#include "fe_capi_detect_scale.inc"   // keypoint detection over a scale space (octaves > 0), alone and with the description behind it

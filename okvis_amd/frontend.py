@@ -22,7 +22,8 @@ SYMBOLS = ["okvis_fe_create", "okvis_fe_destroy", "okvis_fe_stereo_triangulate",
            "okvis_fe_gate_3d2d", "okvis_fe_hamming_candidates", "okvis_fe_match_descriptors", "okvis_fe_bearing_vectors",
            "okvis_fe_sac_consensus", "okvis_fe_match_verified", "okvis_fe_imu_propagate", "okvis_fe_keyframe_decision",
            "okvis_fe_sac_solve", "okvis_fe_sac_solve_absolute", "okvis_fe_ransac", "okvis_fe_detect_keypoints",
-           "okvis_fe_describe_keypoints", "okvis_fe_detect_and_describe", "okvis_fe_describe_tables"]
+           "okvis_fe_describe_keypoints", "okvis_fe_detect_and_describe", "okvis_fe_describe_tables", "okvis_fe_detect_keypoints_scaled",
+           "okvis_fe_detect_scaled_and_describe"]
 MATCH_3D2D, MATCH_2D2D = 1, 2
 SAC_ABSOLUTE, SAC_ROTATION_ONLY, SAC_RELATIVE = 0, 1, 2
 SAC_SAMPLE_ROTATION_ONLY, SAC_SAMPLE_RELATIVE, SAC_MAX_ROOTS = 2, 8, 10
@@ -36,6 +37,7 @@ DETECT_OVERFLOW, DETECT_FULL = 1, 2
 DETECT_MAX_DIM, DETECT_MAX_KEYPOINTS, DETECT_MAX_CANDIDATES = 8192, 2048, 8192
 DETECT_TILE_X, DETECT_TILE_Y = 64, 16            # the score kernel's tile (fe_detect.hpp: DET_TILE_X, DET_TILE_Y)
 DETECT_WAVE, DETECT_SELECT_THREADS = 64, 1024    # the selection kernel's widths (DET_SEL_THREADS)
+DETECT_MAX_OCTAVES, DETECT_MAX_LAYERS = 4, 5       # the scale space (fe_detect_scale.hpp: DET_MAX_OCTAVES, DET_MAX_LAYERS)
 DETECT_KP_SIZE = 12.0                            # BRISK's basic size at scale 1; okvis takes sigma = 0.8 size / 12
 DESCRIBE_VALID, DESCRIBE_ANGLE_UNDEFINED = 1, 2
 DESCRIBE_BYTES, DESCRIBE_ROTATIONS, DESCRIBE_PAIRS, DESCRIBE_POINTS = 48, 1024, 383, 60
@@ -127,6 +129,15 @@ class DetectJobC(C.Structure):
                 ("response", C.c_void_p), ("pixel", C.c_void_p), ("score", C.c_void_p)]
 
 
+class DetectScaleJobC(C.Structure):
+    """okvis_fe_detect_scale_job"""
+    _fields_ = [("image", C.c_void_p), ("threshold", C.c_int64), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32),
+                ("min_dist", C.c_int32), ("max_keypoints", C.c_int32), ("cand_capacity", C.c_int32), ("kp_size", C.c_float),
+                ("octaves", C.c_int32), ("n_keypoints", C.c_int32), ("n_candidates", C.c_int32), ("flags", C.c_int32),
+                ("n_layers", C.c_int32), ("n_layer_candidates", C.c_int32 * 5), ("kp", C.c_void_p), ("response", C.c_void_p),
+                ("pixel", C.c_void_p), ("layer", C.c_void_p), ("scale", C.c_void_p), ("score", C.c_void_p), ("pyramid", C.c_void_p)]
+
+
 class DescribeJobC(C.Structure):
     """okvis_fe_describe_job"""
     _fields_ = [("image", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("n", C.c_int32),
@@ -201,6 +212,8 @@ def declare(L, prefix="okvis_fe_", with_context=True):
         L.okvis_fe_describe_keypoints.argtypes = [vp, i32, C.POINTER(DescribeJobC)]
         L.okvis_fe_detect_and_describe.argtypes = [vp, i32, C.POINTER(DetectJobC), C.POINTER(DescribeJobC)]
         L.okvis_fe_describe_tables.argtypes = [C.POINTER(vp)] * 5 + [C.POINTER(i32)]
+        L.okvis_fe_detect_keypoints_scaled.argtypes = [vp, i32, C.POINTER(DetectScaleJobC)]
+        L.okvis_fe_detect_scaled_and_describe.argtypes = [vp, i32, C.POINTER(DetectScaleJobC), C.POINTER(DescribeJobC)]
 
 
 class Frontend:
@@ -496,6 +509,39 @@ class Frontend:
             r.update(d)
         return res
 
+    def detect_keypoints_scaled(self, images, threshold, octaves, min_dist=40, max_keypoints=400, cand_capacity=DETECT_MAX_CANDIDATES,
+                                kp_size=DETECT_KP_SIZE, want_score=False, want_pyramid=False, want_scale=False):
+        """detect_keypoints over a scale space (okvis_fe_detect_keypoints_scaled; the statement is in the header and is not BRISK's):
+        the detector on up to octaves + 1 half-sampled layers, a raw score comparison across layers, one selection over all layers.
+        octaves: 0..DETECT_MAX_OCTAVES, one value for all or one per image; the rest as for detect_keypoints (min_dist in
+        full-resolution pixels).
+        -> per image the dict of detect_keypoints, where kp holds full-resolution positions and the size kp_size * scale, pixel the
+        integer maximum in its layer, plus layer [n] int32, n_layers, n_layer_candidates [5] and, when asked for, scale [n] float64,
+        score (a list of the layers' score images) and pyramid (a list of the layers 1..)."""
+        table, keep, out = detect_scale_job_table(images, threshold, octaves, min_dist, max_keypoints, cand_capacity, kp_size, want_score,
+                                                  want_pyramid, want_scale)
+        self._call("detect_keypoints_scaled", len(out), table)
+        return detect_scale_results(table, out)
+
+    def detect_scaled_and_describe(self, images, threshold, octaves, cams=None, directions=None, min_dist=40, max_keypoints=400,
+                                   cand_capacity=DETECT_MAX_CANDIDATES, kp_size=DETECT_KP_SIZE, want_score=False, want_pyramid=False,
+                                   want_scale=False, rot=None, want=("rot", "angle")):
+        """detect_and_describe with detect_keypoints_scaled as its detector (okvis_fe_detect_scaled_and_describe): keypoints of every
+        layer are described at the fixed scale at their full-resolution position.  -> the dicts of detect_keypoints_scaled extended as
+        detect_and_describe extends those of detect_keypoints."""
+        det, keep, out = detect_scale_job_table(images, threshold, octaves, min_dist, max_keypoints, cand_capacity, kp_size, want_score,
+                                                want_pyramid, want_scale)
+        rows = [det[j].max_keypoints for j in range(len(out))]
+        table, keep2, out2 = describe_job_table(images, [np.zeros((r, 3), np.float32) for r in rows], cams, directions, rot, want)
+        self._call("detect_scaled_and_describe", len(out), det, table)
+        res = detect_scale_results(det, out)
+        for j in range(len(res)):
+            table[j].n = det[j].n_keypoints
+        for r, d in zip(res, describe_results(table, out2)):
+            r["detect_flags"] = r.pop("flags")
+            r.update(d)
+        return res
+
 
 def describe_tables():
     """the library's own tables (okvis_fe_describe_tables) -> dict of int64 arrays: cs [1024][2], base [60][2], ring [60], half [5],
@@ -640,6 +686,67 @@ def detect_results(table, out):
         if o["score"] is not None:
             r["score"] = o["score"]
         r.update(n_candidates=int(table[j].n_candidates), flags=int(table[j].flags))
+        res.append(r)
+    return res
+
+
+DETECT_SCALE_OUTPUTS = ("kp", "response", "pixel", "layer", "scale", "score", "pyramid")
+
+
+def detect_layers(width, height, octaves):
+    """-> [(w_l, h_l)] of the layers that exist (the header's pyramid rule)"""
+    out = [(int(width), int(height))]
+    while len(out) <= min(int(octaves), DETECT_MAX_OCTAVES) and (out[-1][0] >> 1) >= 5 and (out[-1][1] >> 1) >= 5:
+        out.append((out[-1][0] >> 1, out[-1][1] >> 1))
+    return out
+
+
+def detect_scale_job_table(images, threshold, octaves, min_dist=40, max_keypoints=400, cand_capacity=DETECT_MAX_CANDIDATES,
+                           kp_size=DETECT_KP_SIZE, want_score=False, want_pyramid=False, want_scale=False, leave_out=()):
+    """-> (okvis_fe_detect_scale_job array, what has to outlive the call, the output arrays per job by name (DETECT_SCALE_OUTPUTS; None
+    where not asked for or named in leave_out)).  score and pyramid are flat: the layers one behind the other."""
+    n = len(images)
+    per = lambda v: list(v) if np.ndim(v) else [v] * n
+    thr, octs, md, mk, cc, ks = per(threshold), per(octaves), per(min_dist), per(max_keypoints), per(cand_capacity), per(kp_size)
+    table, keep, out = (DetectScaleJobC * max(1, n))(), [], []
+    for j, im in enumerate(images):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1) or im.strides[0] < im.shape[1]:
+            raise ValueError("an image is a 2-D uint8 array with contiguous columns and a pitch of at least its width")
+        t = table[j]
+        t.image, t.height, t.width, t.pitch = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
+        t.threshold, t.min_dist, t.max_keypoints, t.cand_capacity, t.kp_size = int(thr[j]), int(md[j]), int(mk[j]), int(cc[j]), float(ks[j])
+        t.octaves = int(octs[j])
+        rows = max(0, int(mk[j]))
+        layers = detect_layers(im.shape[1], im.shape[0], max(0, int(octs[j])))
+        o = {"kp": np.zeros((rows, 3), np.float32), "response": np.zeros(rows), "pixel": np.zeros((rows, 2), np.int32),
+             "layer": np.zeros(rows, np.int32), "scale": np.zeros(rows) if want_scale else None,
+             "score": np.zeros(sum(w * h for w, h in layers), np.int64) if want_score else None,
+             "pyramid": np.zeros(max(1, sum(w * h for w, h in layers[1:])), np.uint8) if want_pyramid else None}
+        for k in leave_out:
+            o[k] = None
+        t.kp, t.response, t.pixel, t.layer, t.scale, t.score, t.pyramid = (_ptr(o[k]) for k in DETECT_SCALE_OUTPUTS)
+        keep.append(im), out.append(o)
+    return table, keep, out
+
+
+def detect_scale_results(table, out):
+    """the filled arrays of detect_scale_job_table as one dict per image, cut to n_keypoints rows; score and pyramid as lists of
+    2-D arrays, one per layer (pyramid: the layers 1..)"""
+    res = []
+    for j, o in enumerate(out):
+        t = table[j]
+        n = t.n_keypoints
+        r = {k: o[k][:n].copy() for k in ("kp", "response", "pixel", "layer", "scale") if o[k] is not None}
+        layers = detect_layers(t.width, t.height, t.octaves)
+        assert len(layers) == t.n_layers
+        for name, which in (("score", layers), ("pyramid", layers[1:])):
+            if o[name] is not None:
+                at, r[name] = 0, []
+                for w, h in which:
+                    r[name].append(o[name][at:at + w * h].reshape(h, w))
+                    at += w * h
+        r.update(n_candidates=int(t.n_candidates), flags=int(t.flags), n_layers=int(t.n_layers),
+                 n_layer_candidates=np.array(list(t.n_layer_candidates), np.int32))
         res.append(r)
     return res
 
