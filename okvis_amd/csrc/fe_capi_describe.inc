@@ -1,12 +1,16 @@
 // Part of fe_capi.hip (one translation unit).  Keypoint description: the angle per keypoint and the 48-byte descriptor, on their own
-// (okvis_fe_describe_keypoints) and behind the detect kernels on the keypoints they left in device memory
-// (okvis_fe_detect_and_describe).  DescribeStage is one call's describe work in steps, like DetectStage.
+// (okvis_fe_describe_keypoints) and behind the kernels of a detect stage on the keypoints they left in device memory
+// (run_detect_describe: okvis_fe_detect_and_describe here, okvis_fe_detect_scaled_and_describe in fe_capi_detect_scale.inc).
+// DescribeStage is one call's describe work in steps, like DetectStage.  Of a detect stage in front of it, it knows one
+// DescribeSource per job and the device arrays of the selection.
 namespace {
 
 struct DescribeStage {
   int32_t n_jobs = 0;
   okvis_fe_describe_job* jobs = nullptr;
-  const okvis_fe_detect_job* det = nullptr;   // the chain: images, keypoints and counts are the detect jobs'
+  const DescribeSource* src = nullptr;   // per job: its image and its rows
+  std::vector<DescribeSource> own;       // ... made here from the jobs, unless a detect stage in front handed its own out
+  bool chained = false;                  // images, keypoints and counts are the detect stage's
   size_t n_pix = 0, n_rows = 0, n_cams = 0;
   bool want_angle = false, want_angle64 = false;
   Staged<uint8_t> s_pix;
@@ -21,19 +25,18 @@ struct DescribeStage {
   Staged<uint8_t> s_flags;
   Staged<uint8_t> s_desc;
 
-  int rows_of(int j) const { return det ? det[j].max_keypoints : jobs[j].n; }
-
-  // every check before anything is enqueued or written; the detect jobs of a chain have passed DetectStage::check
-  int check(int32_t n, okvis_fe_describe_job* table, const okvis_fe_detect_job* chain) {
-    n_jobs = n, jobs = table, det = chain;
+  // every check before anything is enqueued or written; chain: the sources of a detect stage whose check has passed, or null
+  int check(int32_t n, okvis_fe_describe_job* table, const DescribeSource* chain) {
+    n_jobs = n, jobs = table, src = chain, chained = chain != nullptr;
     for (int j = 0; j < n_jobs; ++j) {
       const okvis_fe_describe_job& J = jobs[j];
       if (!J.desc || !J.flags) return OKVIS_BA_ERR_ARG;
-      if (!det) {
+      if (!chained) {
         if (!J.kp || J.n < 0 || !image_ok(J.image, J.width, J.height, J.pitch)) return OKVIS_BA_ERR_ARG;
+        own.push_back(DescribeSource{(int64_t)n_pix, J.width, J.height, 0, J.n});
         n_pix += pool_bytes(J.width, J.height);
       }
-      const int rows = rows_of(j);
+      const int rows = chained ? src[j].rows : J.n;
       if (J.rot_in) {
         for (int i = 0; i < rows; ++i)
           if (J.rot_in[i] < 0 || J.rot_in[i] >= fe::DSC_ROTS) return OKVIS_BA_ERR_ARG;
@@ -45,14 +48,15 @@ struct DescribeStage {
       want_angle = want_angle || (J.angle && !J.rot_in), want_angle64 = want_angle64 || (J.angle64 && !J.rot_in);
     }
     if (n_rows > (size_t)INT32_MAX / fe::DSC_BYTES) return OKVIS_BA_ERR_ARG;
+    if (!chained) src = own.data();
     return OKVIS_BA_OK;
   }
   void plan_in(Stage& st) {
-    if (!det) s_pix = st.in<uint8_t>(n_pix);
+    if (!chained) s_pix = st.in<uint8_t>(n_pix);
     s_images = st.in<fe::DscImage>((size_t)n_jobs);
     s_row_job = st.in<int32_t>(n_rows);
     s_cams = st.in<fe::DscCamera>(n_cams, n_cams > 0);
-    s_kp = st.in<float>(3 * n_rows, !det);
+    s_kp = st.in<float>(3 * n_rows, !chained);
     s_rot_in = st.in<int32_t>(n_rows, n_cams < (size_t)n_jobs);
   }
   void plan_out(Stage& st) {
@@ -62,22 +66,19 @@ struct DescribeStage {
     s_flags = st.out<uint8_t>(n_rows);
     s_desc = st.out<uint8_t>((size_t)fe::DSC_BYTES * n_rows);
   }
-  // det_images: the detect stage's image records (the chain), whose pixel offsets and selection ranges are taken over
-  void fill(const Stage& st, const fe::DetImage* det_images) const {
+  void fill(const Stage& st) const {
     fe::DscImage* images = st.host(s_images);
     int32_t* row_job = st.host(s_row_job);
-    size_t at_pix = 0, at_row = 0, at_cam = 0;
+    size_t at_row = 0, at_cam = 0;
     for (int j = 0; j < n_jobs; ++j) {
       const okvis_fe_describe_job& J = jobs[j];
+      const DescribeSource& S = src[j];
       fe::DscImage& I = images[j];
-      const int rows = rows_of(j);
-      I.kp0 = (int32_t)at_row, I.reserved = 0;
-      if (det) {
-        I.pix = det_images[j].pix, I.w = det_images[j].w, I.h = det_images[j].h, I.n = -1, I.det = j, I.sel0 = det_images[j].sel0;
-      } else {
-        I.pix = (int64_t)at_pix, I.w = J.width, I.h = J.height, I.n = J.n, I.det = -1, I.sel0 = 0;
-        pool_image(st.host(s_pix) + at_pix, J.image, J.width, J.height, J.pitch);
-        at_pix += pool_bytes(J.width, J.height);
+      const int rows = S.rows;
+      I.pix = S.pix, I.w = S.w, I.h = S.h, I.kp0 = (int32_t)at_row, I.sel0 = S.sel0, I.reserved = 0;
+      I.n = chained ? -1 : J.n, I.det = chained ? j : -1;   // chained: the count is the detect result's
+      if (!chained) {
+        pool_image(st.host(s_pix) + S.pix, J.image, J.width, J.height, J.pitch);
         if (rows) std::memcpy(st.host(s_kp) + 3 * at_row, J.kp, sizeof(float) * 3 * (size_t)rows);
       }
       if (J.rot_in) {
@@ -108,12 +109,12 @@ struct DescribeStage {
     FE_TRY(hipGetLastError());
     return OKVIS_BA_OK;
   }
-  // counts: the keypoints each job really has (the chain: what the detect kernels selected)
+  // det_res: the detect stage's results, whose counts are the keypoints each job really has (null without a chain)
   void unpack(const Stage& st, const fe::DetResult* det_res) const {
     const fe::DscImage* images = st.host(s_images);
     for (int j = 0; j < n_jobs; ++j) {
       okvis_fe_describe_job& J = jobs[j];
-      const size_t n = (size_t)(det ? det_res[j].n_keypoints : J.n), at = (size_t)images[j].kp0;
+      const size_t n = (size_t)(det_res ? det_res[j].n_keypoints : J.n), at = (size_t)images[j].kp0;
       int32_t n_valid = 0;
       const uint8_t* flags = st.host(s_flags) + at;
       for (size_t i = 0; i < n; ++i) n_valid += flags[i] & fe::DSC_VALID;
@@ -127,6 +128,31 @@ struct DescribeStage {
     }
   }
 };
+
+// one call of a detect stage D with the describe stage behind it: the images staged once, the describe kernels read the selected
+// keypoints where D's selection kernel leaves them
+template <class D>
+int run_detect_describe(okvis_fe_context* c, int32_t n_jobs, typename D::Job* det, okvis_fe_describe_job* desc) {
+  if (!c || n_jobs < 0 || (n_jobs > 0 && (!det || !desc))) return OKVIS_BA_ERR_ARG;
+  D d;
+  DescribeStage B;
+  if (int rc = d.check(n_jobs, det)) return rc;
+  if (n_jobs == 0) return OKVIS_BA_OK;
+  if (int rc = B.check(n_jobs, desc, d.src.data())) return rc;
+  FE_TRY(hipSetDevice(c->device));
+  Stage st{c};
+  d.plan_in(st), B.plan_in(st), d.plan_scratch(st), d.plan_out(st), B.plan_out(st);
+  if (int rc = st.reserve()) return rc;
+  d.fill(st);
+  B.fill(st);
+  if (int rc = st.upload()) return rc;
+  if (int rc = d.launch(st)) return rc;
+  if (int rc = B.launch(st, st.dev(d.s_pix), st.dev(d.s_sel), st.dev(d.s_res))) return rc;
+  if (int rc = st.download()) return rc;
+  d.unpack(st);
+  B.unpack(st, st.host(d.s_res));
+  return OKVIS_BA_OK;
+}
 
 }  // namespace
 
@@ -144,7 +170,7 @@ int okvis_fe_describe_keypoints(okvis_fe_context* c, int32_t n_jobs, okvis_fe_de
   Stage st{c};
   B.plan_in(st), B.plan_out(st);
   if (int rc = st.reserve()) return rc;
-  B.fill(st, nullptr);
+  B.fill(st);
   if (int rc = st.upload()) return rc;
   if (int rc = B.launch(st, st.dev(B.s_pix), nullptr, nullptr)) return rc;
   if (int rc = st.download()) return rc;
@@ -153,26 +179,7 @@ int okvis_fe_describe_keypoints(okvis_fe_context* c, int32_t n_jobs, okvis_fe_de
 }
 
 int okvis_fe_detect_and_describe(okvis_fe_context* c, int32_t n_jobs, okvis_fe_detect_job* det, okvis_fe_describe_job* desc) {
-  if (!c || n_jobs < 0 || (n_jobs > 0 && (!det || !desc))) return OKVIS_BA_ERR_ARG;
-  DetectStage D;
-  DescribeStage B;
-  if (int rc = D.check(n_jobs, det)) return rc;
-  if (int rc = B.check(n_jobs, desc, det)) return rc;
-  if (n_jobs == 0) return OKVIS_BA_OK;
-  FE_TRY(hipSetDevice(c->device));
-  Stage st{c};
-  // the images once; the describe kernels read the selected keypoints where detect_select_kernel leaves them
-  D.plan_in(st), B.plan_in(st), D.plan_scratch(st), D.plan_out(st), B.plan_out(st);
-  if (int rc = st.reserve()) return rc;
-  D.fill(st);
-  B.fill(st, st.host(D.s_images));
-  if (int rc = st.upload()) return rc;
-  if (int rc = D.launch(st)) return rc;
-  if (int rc = B.launch(st, st.dev(D.s_pix), st.dev(D.s_sel), st.dev(D.s_res))) return rc;
-  if (int rc = st.download()) return rc;
-  D.unpack(st);
-  B.unpack(st, st.host(D.s_res));
-  return OKVIS_BA_OK;
+  return run_detect_describe<DetectStage>(c, n_jobs, det, desc);
 }
 
 int okvis_fe_describe_tables(const int32_t** cs, const int32_t** base, const uint8_t** ring, const int32_t** half, const uint8_t** pairs,

@@ -13,9 +13,12 @@
 //   det_beats        the total order "larger S, then lower row-major index" on (S, key) with key = y << 16 | x
 //   det_offset       the parabola's vertex through three scores, clamped to [-0.5, 0.5]
 //   det_close        integer squared distance of two keys below min_dist^2
-//   detect_image_serial  the whole per-image statement as plain loops (host referee of the probe, CPU side of the benchmark): it
-//                    ORDERS the candidates by det_beats and walks them, where the kernel takes the strongest remaining one by
-//                    reduction; both give the statement's result because the order is total
+//   DetOrder         what a selection asks of its candidates: the key type, load, beats, close, accept.  The scale space has its
+//                    own (DetScaledOrder of fe_detect_scale.hpp); the selection itself is written once per side:
+//   det_select_serial    (host) ORDERS the candidates by the order's beats and walks them, where det_select_rounds (device) takes
+//                    the strongest remaining one by reduction; both give the statement's result because the order is total
+//   det_layer_candidates_serial, detect_image_serial   the candidates of one image, and the whole per-image statement, as plain
+//                    loops (host referee of the probe, CPU side of the benchmark)
 //
 // detect_score_kernel: one workgroup of 256 lanes per DET_TILE_X x DET_TILE_Y tile of one image (a tile table built on the host).
 // The tile's bytes go to LDS with a halo of 3 (one pixel for Sobel, one for the window, one for the neighbour test; coordinates
@@ -24,10 +27,12 @@
 // tile: one 24-byte record each, appended to the image's list through one atomic counter per image.  The list's order in memory
 // is whatever the hardware made it; nothing downstream reads it as an order.  The score image goes to memory only for a referee.
 //
-// detect_select_kernel: one workgroup of 1024 lanes per image.  Lane t holds candidates t, t + 1024, ... (at most 8: the limit of
-// 8192) as (S, key) in registers; one out of play has S = 0.  Per accepted keypoint: every lane's best in play, a 6-step butterfly
-// per wave, the sixteen waves' results through LDS (two buffers in turn: one barrier per keypoint) and a 4-step butterfly, then
-// every lane strikes out what lies inside the winner's disc.  At most max_keypoints + 1 rounds; no scratch, no atomics.
+// detect_select_kernel: one workgroup of 1024 lanes per image: the overflow rule, then det_select_rounds under DetOrder.
+// det_select_rounds: lane t holds candidates t, t + 1024, ... (at most 8: the limit of 8192) as (S, key) in registers; one out of
+// play has S = 0.  Per accepted keypoint: every lane's best in play, a 6-step butterfly per wave, the sixteen waves' results
+// through LDS (two buffers in turn: one barrier per keypoint) and a 4-step butterfly, then every lane strikes out what lies inside
+// the winner's disc.  At most max_keypoints + 1 rounds; no scratch, no atomics.  The key type is the order's (32 bits here, 64
+// over a scale space): the one-layer kernel keeps its registers and shuffles.
 //
 // The per-pixel and per-candidate functions are BA_HD like ba_math.hpp's: a plain host compiler sees them too.
 #pragma once
@@ -118,12 +123,49 @@ BA_HD bool det_close(uint32_t ka, uint32_t kb, int64_t min_dist2) {
   return dx * dx + dy * dy < min_dist2;
 }
 
-// The per-image statement as plain loops.  sel has room for max_keypoints records; score (h * w, or nullptr) receives the score
-// image, 0 outside its domain.
-inline DetResult detect_image_serial(const uint8_t* image, int w, int h, int pitch, int64_t threshold, int min_dist, int max_keypoints,
-                                     int cand_capacity, DetCand* sel, int64_t* score) {
+// The selection's order over one-layer candidates, for det_select_rounds (the device) and det_select_serial (the host) alike.
+// An order names its Key and supplies load (candidate i as (S, key)), beats (the total order), close (two keys nearer than the
+// job's minimum distance) and accept (candidate pos becomes keypoint number slot).
+struct DetOrder {
+  using Key = uint32_t;
+  const DetCand* cand;  // the job's candidates
+  DetCand* sel;         // the job's keypoints
+  int64_t min_dist2;
+  BA_HD void load(int i, int64_t& s, Key& k) const { s = cand[i].s, k = det_key(cand[i].x, cand[i].y); }
+  BA_HD static bool beats(int64_t sp, Key kp, int64_t sq, Key kq) { return det_beats(sp, kp, sq, kq); }
+  BA_HD bool close(Key a, Key b) const { return det_close(a, b, min_dist2); }
+  BA_HD void accept(int slot, int pos) const { sel[slot] = cand[pos]; }
+};
+
+// The selection as plain loops: the n candidates ORDERED by the order and walked, each accepted unless it lies close to one
+// accepted before it; FULL when one more than max_kp would have been accepted.  -> the number accepted
+template <class Order>
+inline int det_select_serial(const Order& o, int n, int max_kp, int32_t& flags) {
+  using Key = typename Order::Key;
+  std::vector<int64_t> s((size_t)n);
+  std::vector<Key> k((size_t)n), taken;
+  std::vector<int32_t> order((size_t)n);
+  for (int i = 0; i < n; ++i) o.load(i, s[i], k[i]), order[i] = i;
+  std::sort(order.begin(), order.end(), [&](int32_t p, int32_t q) { return Order::beats(s[p], k[p], s[q], k[q]); });
+  for (int32_t i : order) {
+    bool ok = true;
+    for (size_t a = 0; a < taken.size() && ok; ++a) ok = !o.close(k[i], taken[a]);
+    if (!ok) continue;
+    if ((int)taken.size() == max_kp) {  // one more would have been accepted: the list is cut short
+      flags |= DET_FULL;
+      break;
+    }
+    o.accept((int)taken.size(), i);
+    taken.push_back(k[i]);
+  }
+  return (int)taken.size();
+}
+
+// the candidates of one w x h layer: S gets the scores, DET_OUTSIDE beyond the domain
+inline void det_layer_candidates_serial(const uint8_t* image, int w, int h, int64_t pitch, int64_t threshold, std::vector<int64_t>& S,
+                                        std::vector<DetCand>& cand) {
   std::vector<uint32_t> g((size_t)w * h, 0u);
-  std::vector<int64_t> S((size_t)w * h, DET_OUTSIDE);
+  S.assign((size_t)w * h, DET_OUTSIDE);
   for (int y = 1; y <= h - 2; ++y)
     for (int x = 1; x <= w - 2; ++x) {
       const uint8_t* r = image + (size_t)(y - 1) * pitch + (x - 1);
@@ -131,9 +173,6 @@ inline DetResult detect_image_serial(const uint8_t* image, int w, int h, int pit
     }
   for (int y = 2; y <= h - 3; ++y)
     for (int x = 2; x <= w - 3; ++x) S[(size_t)y * w + x] = det_score(&g[(size_t)(y - 1) * w + (x - 1)], w);
-  if (score)
-    for (size_t i = 0; i < (size_t)w * h; ++i) score[i] = S[i] == DET_OUTSIDE ? 0 : S[i];
-  std::vector<DetCand> cand;
   for (int y = 2; y <= h - 3; ++y)
     for (int x = 2; x <= w - 3; ++x) {
       const int64_t s = S[(size_t)y * w + x];
@@ -146,23 +185,22 @@ inline DetResult detect_image_serial(const uint8_t* image, int w, int h, int pit
         cand.push_back(det_candidate(x, y, s, S[(size_t)y * w + x - 1], S[(size_t)y * w + x + 1], S[(size_t)(y - 1) * w + x],
                                      S[(size_t)(y + 1) * w + x]));
     }
+}
+
+// The per-image statement as plain loops.  sel has room for max_keypoints records; score (h * w, or nullptr) receives the score
+// image, 0 outside its domain.
+inline DetResult detect_image_serial(const uint8_t* image, int w, int h, int pitch, int64_t threshold, int min_dist, int max_keypoints,
+                                     int cand_capacity, DetCand* sel, int64_t* score) {
+  std::vector<int64_t> S;
+  std::vector<DetCand> cand;
+  det_layer_candidates_serial(image, w, h, pitch, threshold, S, cand);
+  if (score)
+    for (size_t i = 0; i < S.size(); ++i) score[i] = S[i] == DET_OUTSIDE ? 0 : S[i];
   DetResult R = {0, (int32_t)cand.size(), 0, 0};
-  if ((int64_t)cand.size() > cand_capacity) {
+  if ((int64_t)cand.size() > cand_capacity)
     R.flags = DET_OVERFLOW;
-    return R;
-  }
-  std::sort(cand.begin(), cand.end(), [](const DetCand& p, const DetCand& q) { return det_beats(p.s, det_key(p.x, p.y), q.s, det_key(q.x, q.y)); });
-  const int64_t md2 = (int64_t)min_dist * min_dist;
-  for (const DetCand& c : cand) {
-    bool ok = true;
-    for (int i = 0; i < R.n_keypoints && ok; ++i) ok = !det_close(det_key(c.x, c.y), det_key(sel[i].x, sel[i].y), md2);
-    if (!ok) continue;
-    if (R.n_keypoints == max_keypoints) {  // one more would have been accepted: the list is cut short
-      R.flags |= DET_FULL;
-      break;
-    }
-    sel[R.n_keypoints++] = c;
-  }
+  else
+    R.n_keypoints = det_select_serial(DetOrder{cand.data(), sel, (int64_t)min_dist * min_dist}, (int)cand.size(), max_keypoints, R.flags);
   return R;
 }
 
@@ -248,52 +286,48 @@ __global__ void __launch_bounds__(DET_THREADS) detect_score_kernel(const DetPara
   }
 }
 
-__global__ void __launch_bounds__(DET_SEL_THREADS) detect_select_kernel(const DetParams P) {
+// The selection of one workgroup of DET_SEL_THREADS lanes over the n <= DET_MAX_CANDIDATES candidates of an order (DetOrder's
+// comment), the body of both selection kernels: the register-resident slots, the rounds, the LDS hand-off and the FULL rule.
+// -> the number accepted, the same in every lane
+template <class Order>
+__device__ __forceinline__ int det_select_rounds(const Order& o, int n, int max_kp, int32_t& flags) {
+  using Key = typename Order::Key;
   constexpr int WAVES = DET_SEL_THREADS / 64;
   static_assert(WAVES <= 64 && (WAVES & (WAVES - 1)) == 0, "the waves' results are reduced by one butterfly");
   __shared__ int64_t red_s[2][WAVES];
-  __shared__ uint32_t red_k[2][WAVES];
+  __shared__ Key red_k[2][WAVES];
   __shared__ int32_t red_p[2][WAVES];
-  const int tid = threadIdx.x, job = blockIdx.x;
-  const DetImage im = P.images[job];
-  const int n = P.count[job];
-  DetResult R = {0, n, 0, 0};
-  if (n > im.cap) {  // the same for every lane
-    R.flags = DET_OVERFLOW;
-    if (tid == 0) P.res[job] = R;
-    return;
-  }
+  const int tid = threadIdx.x;
   // a candidate out of play, and a slot without one, has S = 0 and key 0: it beats nothing, and every candidate (S >= 1) beats it
   int64_t s[DET_SEL_PER_LANE];
-  uint32_t k[DET_SEL_PER_LANE];
-  const DetCand* cand = P.cand + im.cand0;
+  Key k[DET_SEL_PER_LANE];
 #pragma unroll
   for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
     const int pos = tid + j * DET_SEL_THREADS;
     const bool in = pos < n;
-    const DetCand c = cand[in ? pos : 0];  // record 0 exists (cap >= 1); what it holds when n = 0 is not used
-    s[j] = in ? c.s : 0, k[j] = in ? det_key(c.x, c.y) : 0u;
+    int64_t cs;
+    Key ck;
+    o.load(in ? pos : 0, cs, ck);  // record 0 exists (cap >= 1); what it holds when n = 0 is not used
+    s[j] = in ? cs : 0, k[j] = in ? ck : (Key)0;
   }
-  const int64_t md2 = (int64_t)im.min_dist * im.min_dist;
   int accepted = 0;
 #pragma nounroll
-  for (int it = 0; it <= im.max_kp; ++it) {
+  for (int it = 0; it <= max_kp; ++it) {
     // the strongest of the lane's candidates in play, then of the wave's
     int64_t bs = 0;
-    uint32_t bk = 0u;
+    Key bk = 0;
     int32_t bp = -1;
 #pragma unroll
-    for (int j = 0; j < DET_SEL_PER_LANE; ++j)
-    {
-      const bool b = det_beats(s[j], k[j], bs, bk);
+    for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
+      const bool b = Order::beats(s[j], k[j], bs, bk);
       bs = b ? s[j] : bs, bk = b ? k[j] : bk, bp = b ? tid + j * DET_SEL_THREADS : bp;
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
       const int64_t os = __shfl_xor(bs, m, 64);
-      const uint32_t ok = __shfl_xor(bk, m, 64);
+      const Key ok = __shfl_xor(bk, m, 64);
       const int32_t op = __shfl_xor(bp, m, 64);
-      if (det_beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
+      if (Order::beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
     }
     const int buf = it & 1;
     if ((tid & 63) == 0) red_s[buf][tid >> 6] = bs, red_k[buf][tid >> 6] = bk, red_p[buf][tid >> 6] = bp;
@@ -303,26 +337,36 @@ __global__ void __launch_bounds__(DET_SEL_THREADS) detect_select_kernel(const De
 #pragma unroll
     for (int m = 1; m < WAVES; m <<= 1) {
       const int64_t os = __shfl_xor(bs, m, 64);
-      const uint32_t ok = __shfl_xor(bk, m, 64);
+      const Key ok = __shfl_xor(bk, m, 64);
       const int32_t op = __shfl_xor(bp, m, 64);
-      if (det_beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
+      if (Order::beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
     }
     if (bp < 0) break;  // nothing left in play
-    if (accepted == im.max_kp) {
-      R.flags |= DET_FULL;
+    if (accepted == max_kp) {
+      flags |= DET_FULL;
       break;
     }
-    if (tid == 0) P.sel[im.sel0 + accepted] = cand[bp];
+    if (tid == 0) o.accept(accepted, bp);
     ++accepted;
 #pragma unroll
-    for (int j = 0; j < DET_SEL_PER_LANE; ++j)
-    {
-      const bool out = tid + j * DET_SEL_THREADS == bp || det_close(k[j], bk, md2);
-      s[j] = out ? 0 : s[j], k[j] = out ? 0u : k[j];
+    for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
+      const bool out = tid + j * DET_SEL_THREADS == bp || o.close(k[j], bk);
+      s[j] = out ? 0 : s[j], k[j] = out ? (Key)0 : k[j];
     }
   }
-  R.n_keypoints = accepted;
-  if (tid == 0) P.res[job] = R;
+  return accepted;
+}
+
+__global__ void __launch_bounds__(DET_SEL_THREADS) detect_select_kernel(const DetParams P) {
+  const int job = blockIdx.x;
+  const DetImage im = P.images[job];
+  const int n = P.count[job];
+  DetResult R = {0, n, 0, 0};
+  if (n > im.cap)  // the same for every lane
+    R.flags = DET_OVERFLOW;
+  else
+    R.n_keypoints = det_select_rounds(DetOrder{P.cand + im.cand0, P.sel + im.sel0, (int64_t)im.min_dist * im.min_dist}, n, im.max_kp, R.flags);
+  if (threadIdx.x == 0) P.res[job] = R;
 }
 #endif  // __HIPCC__
 

@@ -15,6 +15,7 @@
 //   det_scale, det_scaled_size, det_scaled_position   t 2^l, the size and the full-resolution position
 //   det_scaled_beats     the order "larger S, then lower layer, then lower row-major index" on (S, layer << 32 | y << 16 | x)
 //   det_scaled_close     squared distance of two centres in doubled full-resolution units below 4 min_dist^2
+//   DetScaledOrder       these three as an order of the selection (fe_detect.hpp: det_select_rounds, det_select_serial)
 //   detect_scaled_image_serial   the whole per-image statement as plain loops (host referee of the probe, CPU side of the benchmark)
 //
 // detect_pyramid_kernel: one workgroup of 256 lanes per 64 x 16 tile of layer 0 (of the jobs with more than one layer).  Every
@@ -25,8 +26,8 @@
 // The 16 + 9 scores of the neighbouring layers (and the four axis neighbours of a candidate above layer 0, whose sub-pixel offset
 // is needed in double) are recomputed from pool pixels; a survivor is appended to the job's pooled list through one counter per
 // job.  The list's order in memory reaches no output.
-// detect_select_scaled_kernel: detect_select_kernel with the three-level order and the doubled-centre distance; it also hands
-// out the layers' counts.
+// detect_select_scaled_kernel: the layers' counts, the overflow rule over all layers, then det_select_rounds under DetScaledOrder
+// (the three-level order and the doubled-centre distance) on the job's pooled survivors.
 #pragma once
 #include "fe_detect.hpp"
 
@@ -193,31 +194,19 @@ BA_HD DetSurvivor det_cross(const DetCand& c, int l, bool has_coarse, const DetL
   return r;
 }
 
-// the candidates of one w x h layer (detect_image_serial's first half): S gets the scores, DET_OUTSIDE beyond the domain
-inline void det_layer_candidates_serial(const uint8_t* image, int w, int h, int64_t pitch, int64_t threshold, std::vector<int64_t>& S,
-                                        std::vector<DetCand>& cand) {
-  std::vector<uint32_t> g((size_t)w * h, 0u);
-  S.assign((size_t)w * h, DET_OUTSIDE);
-  for (int y = 1; y <= h - 2; ++y)
-    for (int x = 1; x <= w - 2; ++x) {
-      const uint8_t* r = image + (size_t)(y - 1) * pitch + (x - 1);
-      g[(size_t)y * w + x] = det_sobel(r, r + pitch, r + 2 * (size_t)pitch);
-    }
-  for (int y = 2; y <= h - 3; ++y)
-    for (int x = 2; x <= w - 3; ++x) S[(size_t)y * w + x] = det_score(&g[(size_t)(y - 1) * w + (x - 1)], w);
-  for (int y = 2; y <= h - 3; ++y)
-    for (int x = 2; x <= w - 3; ++x) {
-      const int64_t s = S[(size_t)y * w + x];
-      if (s < threshold) continue;
-      bool best = true;
-      for (int dy = -1; dy <= 1 && best; ++dy)
-        for (int dx = -1; dx <= 1 && best; ++dx)
-          if (dx || dy) best = det_beats(s, det_key(x, y), S[(size_t)(y + dy) * w + (x + dx)], det_key(x + dx, y + dy));
-      if (best)
-        cand.push_back(det_candidate(x, y, s, S[(size_t)y * w + x - 1], S[(size_t)y * w + x + 1], S[(size_t)(y - 1) * w + x],
-                                     S[(size_t)(y + 1) * w + x]));
-    }
-}
+// the selection's order over the pooled survivors of all layers (DetOrder's comment)
+struct DetScaledOrder {
+  using Key = uint64_t;
+  const DetCand* pool;   // the job's survivors
+  const DetScaleExtra* poolx;
+  DetCand* sel;          // the job's keypoints
+  DetScaleExtra* selx;
+  int64_t reach;
+  BA_HD void load(int i, int64_t& s, Key& k) const { s = pool[i].s, k = det_scaled_key(poolx[i].layer, pool[i].x, pool[i].y); }
+  BA_HD static bool beats(int64_t sp, Key kp, int64_t sq, Key kq) { return det_scaled_beats(sp, kp, sq, kq); }
+  BA_HD bool close(Key a, Key b) const { return det_scaled_close(a, b, reach); }
+  BA_HD void accept(int slot, int pos) const { sel[slot] = pool[pos], selx[slot] = poolx[pos]; }
+};
 
 // The per-image statement as plain loops.  sel, selx have room for max_keypoints records; layer_counts for DET_MAX_LAYERS counts;
 // score (sum_l h_l w_l, or nullptr) receives the layers' score images one behind the other, 0 outside their domains; pyramid
@@ -269,22 +258,8 @@ inline DetResult detect_scaled_image_serial(const uint8_t* image, int w, int h, 
     R.flags = DET_OVERFLOW;
     return R;
   }
-  std::vector<int32_t> order(pool.size());
-  for (size_t i = 0; i < order.size(); ++i) order[i] = (int32_t)i;
-  const auto key = [&](int32_t i) { return det_scaled_key(poolx[i].layer, pool[i].x, pool[i].y); };
-  std::sort(order.begin(), order.end(), [&](int32_t p, int32_t q) { return det_scaled_beats(pool[p].s, key(p), pool[q].s, key(q)); });
-  const int64_t reach = det_scaled_reach(min_dist);
-  for (int32_t i : order) {
-    bool ok = true;
-    for (int k = 0; k < R.n_keypoints && ok; ++k) ok = !det_scaled_close(key(i), det_scaled_key(selx[k].layer, sel[k].x, sel[k].y), reach);
-    if (!ok) continue;
-    if (R.n_keypoints == max_keypoints) {
-      R.flags |= DET_FULL;
-      break;
-    }
-    sel[R.n_keypoints] = pool[i], selx[R.n_keypoints] = poolx[i];
-    ++R.n_keypoints;
-  }
+  const DetScaledOrder order{pool.data(), poolx.data(), sel, selx, det_scaled_reach(min_dist)};
+  R.n_keypoints = det_select_serial(order, (int)pool.size(), max_keypoints, R.flags);
   return R;
 }
 
@@ -382,10 +357,6 @@ __global__ void __launch_bounds__(DET_CROSS_THREADS) detect_cross_kernel(const D
 }
 
 __global__ void __launch_bounds__(DET_SEL_THREADS) detect_select_scaled_kernel(const DetScaleParams P) {
-  constexpr int WAVES = DET_SEL_THREADS / 64;
-  __shared__ int64_t red_s[2][WAVES];
-  __shared__ uint64_t red_k[2][WAVES];
-  __shared__ int32_t red_p[2][WAVES];
   const int tid = threadIdx.x, job = blockIdx.x;
   const DetScaleJob J = P.jobs[job];
   bool overflow = false;
@@ -398,66 +369,10 @@ __global__ void __launch_bounds__(DET_SEL_THREADS) detect_select_scaled_kernel(c
   DetResult R = {0, n, 0, 0};
   if (overflow || n > J.cap) {   // the same for every lane
     R.flags = DET_OVERFLOW;
-    if (tid == 0) P.res[job] = R;
-    return;
+  } else {
+    const DetScaledOrder order{P.pool + J.pool0, P.poolx + J.pool0, P.sel + J.sel0, P.selx + J.sel0, det_scaled_reach(J.min_dist)};
+    R.n_keypoints = det_select_rounds(order, n, J.max_kp, R.flags);
   }
-  // a survivor out of play, and a slot without one, has S = 0 and key 0: it beats nothing, and every survivor (S >= 1) beats it
-  int64_t s[DET_SEL_PER_LANE];
-  uint64_t k[DET_SEL_PER_LANE];
-  const DetCand* pool = P.pool + J.pool0;
-  const DetScaleExtra* poolx = P.poolx + J.pool0;
-#pragma unroll
-  for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
-    const int pos = tid + j * DET_SEL_THREADS;
-    const bool in = pos < n;
-    const DetCand c = pool[in ? pos : 0];   // record 0 exists (cap >= 1); what it holds when n = 0 is not used
-    const int32_t layer = poolx[in ? pos : 0].layer;
-    s[j] = in ? c.s : 0, k[j] = in ? det_scaled_key(layer, c.x, c.y) : 0u;
-  }
-  const int64_t reach = det_scaled_reach(J.min_dist);
-  int accepted = 0;
-#pragma nounroll
-  for (int it = 0; it <= J.max_kp; ++it) {
-    int64_t bs = 0;
-    uint64_t bk = 0u;
-    int32_t bp = -1;
-#pragma unroll
-    for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
-      const bool b = det_scaled_beats(s[j], k[j], bs, bk);
-      bs = b ? s[j] : bs, bk = b ? k[j] : bk, bp = b ? tid + j * DET_SEL_THREADS : bp;
-    }
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) {
-      const int64_t os = __shfl_xor(bs, m, 64);
-      const uint64_t ok = __shfl_xor(bk, m, 64);
-      const int32_t op = __shfl_xor(bp, m, 64);
-      if (det_scaled_beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
-    }
-    const int buf = it & 1;
-    if ((tid & 63) == 0) red_s[buf][tid >> 6] = bs, red_k[buf][tid >> 6] = bk, red_p[buf][tid >> 6] = bp;
-    __syncthreads();   // one per round, as in detect_select_kernel
-    bs = red_s[buf][tid & (WAVES - 1)], bk = red_k[buf][tid & (WAVES - 1)], bp = red_p[buf][tid & (WAVES - 1)];
-#pragma unroll
-    for (int m = 1; m < WAVES; m <<= 1) {
-      const int64_t os = __shfl_xor(bs, m, 64);
-      const uint64_t ok = __shfl_xor(bk, m, 64);
-      const int32_t op = __shfl_xor(bp, m, 64);
-      if (det_scaled_beats(os, ok, bs, bk)) bs = os, bk = ok, bp = op;
-    }
-    if (bp < 0) break;   // nothing left in play
-    if (accepted == J.max_kp) {
-      R.flags |= DET_FULL;
-      break;
-    }
-    if (tid == 0) P.sel[J.sel0 + accepted] = pool[bp], P.selx[J.sel0 + accepted] = poolx[bp];
-    ++accepted;
-#pragma unroll
-    for (int j = 0; j < DET_SEL_PER_LANE; ++j) {
-      const bool out = tid + j * DET_SEL_THREADS == bp || det_scaled_close(k[j], bk, reach);
-      s[j] = out ? 0 : s[j], k[j] = out ? 0u : k[j];
-    }
-  }
-  R.n_keypoints = accepted;
   if (tid == 0) P.res[job] = R;
 }
 #endif  // __HIPCC__

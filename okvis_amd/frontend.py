@@ -498,16 +498,7 @@ class Frontend:
         -> the dicts of detect_keypoints extended by desc, flags, n_valid and what `want` names, cut to n_keypoints rows.  `flags`
         is the describe entry's array (one byte per keypoint); the detector's flags of the image are under `detect_flags`."""
         det, keep, out = detect_job_table(images, threshold, min_dist, max_keypoints, cand_capacity, kp_size, want_score)
-        rows = [det[j].max_keypoints for j in range(len(out))]
-        table, keep2, out2 = describe_job_table(images, [np.zeros((r, 3), np.float32) for r in rows], cams, directions, rot, want)
-        self._call("detect_and_describe", len(out), det, table)
-        res = detect_results(det, out)
-        for j, r in enumerate(res):
-            table[j].n = det[j].n_keypoints
-        for r, d in zip(res, describe_results(table, out2)):
-            r["detect_flags"] = r.pop("flags")
-            r.update(d)
-        return res
+        return self._describe_behind("detect_and_describe", det, out, detect_results, images, cams, directions, rot, want)
 
     def detect_keypoints_scaled(self, images, threshold, octaves, min_dist=40, max_keypoints=400, cand_capacity=DETECT_MAX_CANDIDATES,
                                 kp_size=DETECT_KP_SIZE, want_score=False, want_pyramid=False, want_scale=False):
@@ -531,10 +522,15 @@ class Frontend:
         detect_and_describe extends those of detect_keypoints."""
         det, keep, out = detect_scale_job_table(images, threshold, octaves, min_dist, max_keypoints, cand_capacity, kp_size, want_score,
                                                 want_pyramid, want_scale)
+        return self._describe_behind("detect_scaled_and_describe", det, out, detect_scale_results, images, cams, directions, rot, want)
+
+    def _describe_behind(self, entry, det, out, results, images, cams, directions, rot, want):
+        """the chain of both detectors: the describe table on max_keypoints rows per image, one call of `entry`, the detector's
+        dicts (results(det, out)) extended by the describe entry's, cut to n_keypoints rows"""
         rows = [det[j].max_keypoints for j in range(len(out))]
-        table, keep2, out2 = describe_job_table(images, [np.zeros((r, 3), np.float32) for r in rows], cams, directions, rot, want)
-        self._call("detect_scaled_and_describe", len(out), det, table)
-        res = detect_scale_results(det, out)
+        table, keep, out2 = describe_job_table(images, [np.zeros((r, 3), np.float32) for r in rows], cams, directions, rot, want)
+        self._call(entry, len(out), det, table)
+        res = results(det, out)
         for j in range(len(res)):
             table[j].n = det[j].n_keypoints
         for r, d in zip(res, describe_results(table, out2)):
@@ -657,10 +653,22 @@ def detect_job_table(images, threshold, min_dist=40, max_keypoints=400, cand_cap
                      want_score=False, leave_out=()):
     """-> (okvis_fe_detect_job array, what has to outlive the call, the output arrays per job by name (DETECT_OUTPUTS; None where
     not asked for or named in leave_out)).  An image is passed as it lies in memory: no copy is made of a view with a pitch."""
+    table, keep, out = _detect_jobs(DetectJobC, images, threshold, min_dist, max_keypoints, cand_capacity, kp_size)
+    for t, im, o in zip(table, images, out):
+        o["score"] = np.zeros(im.shape, np.int64) if want_score else None
+        for k in leave_out:
+            o[k] = None
+        t.kp, t.response, t.pixel, t.score = (_ptr(o[k]) for k in DETECT_OUTPUTS)
+    return table, keep, out
+
+
+def _detect_jobs(ctype, images, threshold, min_dist, max_keypoints, cand_capacity, kp_size):
+    """what both detect job tables begin with: the images checked, the fields the two structs share (one value for all, or one per
+    image) and the per-keypoint arrays kp, response, pixel on max_keypoints rows -> (table, keep, out)"""
     n = len(images)
     per = lambda v: list(v) if np.ndim(v) else [v] * n
     thr, md, mk, cc, ks = per(threshold), per(min_dist), per(max_keypoints), per(cand_capacity), per(kp_size)
-    table, keep, out = (DetectJobC * max(1, n))(), [], []
+    table, out = (ctype * max(1, n))(), []
     for j, im in enumerate(images):
         if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1) or im.strides[0] < im.shape[1]:
             raise ValueError("an image is a 2-D uint8 array with contiguous columns and a pitch of at least its width")
@@ -668,13 +676,8 @@ def detect_job_table(images, threshold, min_dist=40, max_keypoints=400, cand_cap
         t.image, t.height, t.width, t.pitch = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
         t.threshold, t.min_dist, t.max_keypoints, t.cand_capacity, t.kp_size = int(thr[j]), int(md[j]), int(mk[j]), int(cc[j]), float(ks[j])
         rows = max(0, int(mk[j]))
-        o = {"kp": np.zeros((rows, 3), np.float32), "response": np.zeros(rows), "pixel": np.zeros((rows, 2), np.int32),
-             "score": np.zeros(im.shape, np.int64) if want_score else None}
-        for k in leave_out:
-            o[k] = None
-        t.kp, t.response, t.pixel, t.score = (_ptr(o[k]) for k in DETECT_OUTPUTS)
-        keep.append(im), out.append(o)
-    return table, keep, out
+        out.append({"kp": np.zeros((rows, 3), np.float32), "response": np.zeros(rows), "pixel": np.zeros((rows, 2), np.int32)})
+    return table, list(images), out
 
 
 def detect_results(table, out):
@@ -705,27 +708,18 @@ def detect_scale_job_table(images, threshold, octaves, min_dist=40, max_keypoint
                            kp_size=DETECT_KP_SIZE, want_score=False, want_pyramid=False, want_scale=False, leave_out=()):
     """-> (okvis_fe_detect_scale_job array, what has to outlive the call, the output arrays per job by name (DETECT_SCALE_OUTPUTS; None
     where not asked for or named in leave_out)).  score and pyramid are flat: the layers one behind the other."""
-    n = len(images)
-    per = lambda v: list(v) if np.ndim(v) else [v] * n
-    thr, octs, md, mk, cc, ks = per(threshold), per(octaves), per(min_dist), per(max_keypoints), per(cand_capacity), per(kp_size)
-    table, keep, out = (DetectScaleJobC * max(1, n))(), [], []
-    for j, im in enumerate(images):
-        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2 or (im.shape[1] > 1 and im.strides[1] != 1) or im.strides[0] < im.shape[1]:
-            raise ValueError("an image is a 2-D uint8 array with contiguous columns and a pitch of at least its width")
-        t = table[j]
-        t.image, t.height, t.width, t.pitch = im.ctypes.data, im.shape[0], im.shape[1], im.strides[0]
-        t.threshold, t.min_dist, t.max_keypoints, t.cand_capacity, t.kp_size = int(thr[j]), int(md[j]), int(mk[j]), int(cc[j]), float(ks[j])
+    table, keep, out = _detect_jobs(DetectScaleJobC, images, threshold, min_dist, max_keypoints, cand_capacity, kp_size)
+    octs = list(octaves) if np.ndim(octaves) else [octaves] * len(images)
+    for j, (t, im, o) in enumerate(zip(table, images, out)):
         t.octaves = int(octs[j])
-        rows = max(0, int(mk[j]))
-        layers = detect_layers(im.shape[1], im.shape[0], max(0, int(octs[j])))
-        o = {"kp": np.zeros((rows, 3), np.float32), "response": np.zeros(rows), "pixel": np.zeros((rows, 2), np.int32),
-             "layer": np.zeros(rows, np.int32), "scale": np.zeros(rows) if want_scale else None,
-             "score": np.zeros(sum(w * h for w, h in layers), np.int64) if want_score else None,
-             "pyramid": np.zeros(max(1, sum(w * h for w, h in layers[1:])), np.uint8) if want_pyramid else None}
+        rows = len(o["kp"])
+        layers = detect_layers(im.shape[1], im.shape[0], max(0, t.octaves))
+        o.update(layer=np.zeros(rows, np.int32), scale=np.zeros(rows) if want_scale else None,
+                 score=np.zeros(sum(w * h for w, h in layers), np.int64) if want_score else None,
+                 pyramid=np.zeros(max(1, sum(w * h for w, h in layers[1:])), np.uint8) if want_pyramid else None)
         for k in leave_out:
             o[k] = None
         t.kp, t.response, t.pixel, t.layer, t.scale, t.score, t.pyramid = (_ptr(o[k]) for k in DETECT_SCALE_OUTPUTS)
-        keep.append(im), out.append(o)
     return table, keep, out
 
 

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Digest of the frontend entries (include/okvis_amd_frontend.h) over the scenes of the existing tests: needs a GPU.
 
-Every okvis_fe_* entry (the eighteen of the header, the table query aside; create and destroy by way of the context) is called through okvis_amd.frontend;
+Every okvis_fe_* entry (the nineteen of the header, the table query aside; create and destroy by way of the context) is called through okvis_amd.frontend;
 every output array of every case is hashed (SHA-256).  OUT.json holds one record per group of cases (the part of a case's name
 in front of the slash): how many cases and arrays, and the SHA-256 over their (case, array, hash) lines in sorted order.  Two trees
 whose files are equal computed the same bytes for every case; two runs on one tree show that the digest is repeatable.  Where a
@@ -10,7 +10,7 @@ group differs, --cases FILE writes the hash of every array of every case (some 1
     python tools/fe_digest.py OUT.json [--root TREE] [--cases FILE]   (TREE: the checkout whose okvis_amd is used, default this one)
 
 The scenes (tests/vmatch_scene.py, the generator of tests/test_gpu_descriptor_matcher.py, tests/sac_cases.py,
-tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/ransac_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/detect_cases.py, tests/golden/) are those of the checkout the tool
+tests/sac_solve_cases.py, tests/sac_abs_cases.py, tests/ransac_cases.py, tests/imu_propagate_cases.py, tests/keyframe_cases.py, tests/detect_cases.py, tests/describe_cases.py, tests/detect_scale_cases.py, tests/golden/) are those of the checkout the tool
 itself is in; nothing outside it is read.
   verified matching   the eight shapes of tests/test_gpu_vmatch.py x both kinds x both camera models x the five (num_best, use_ratio)
                       settings x with and without skip masks, every case alone, and all of them as one mixed batch per setting
@@ -41,6 +41,10 @@ itself is in; nothing outside it is read.
   describe            every family of describe_cases.NAMES, the stereo pair, the shifted and the turned images with given
                       rotations, every job alone and the family as one call; the angle cases of the four camera models; the
                       chain on detect families.  Left out where the tree under --root is from before the entries
+  detect_scaled       every family of detect_scale_cases.NAMES with and without the referee outputs (scale, the layers' score
+                      images and pixels), every job alone (detect_scaled) and the family as one call (detect_scaled_batch);
+                      detect_scaled_and_describe on the capacity and edges families and twenty mixed jobs with every output
+                      (detect_scaled_chain).  Left out where the tree under --root is from before the entries
 """
 import argparse
 import ctypes as C
@@ -389,6 +393,36 @@ if hasattr(fe, "describe_keypoints"):        # a tree from before the entries ha
     fields = [[j[k] for j in chain] for k in ("threshold", "min_dist", "max_keypoints", "cand_capacity", "kp_size")]
     for j, r in enumerate(fe.detect_and_describe([j["image"] for j in chain], fields[0], cam, [0.2, 0.9, 0.38], *fields[1:], want=ALL)):
         record(f"describe_chain/job{j}", **det_arrays(r))
+
+# ---------------------------------------------------------------- keypoint detection over a scale space
+if hasattr(fe, "detect_keypoints_scaled"):   # a tree from before the entries has every other group
+    import detect_scale_cases as DSC  # noqa: E402
+
+    def scaled_args(jobs):
+        return [[j["image"] for j in jobs]] + [[j[k] for j in jobs] for k in DSC.FIELDS]
+
+    def detect_scaled(jobs, referee):
+        return fe.detect_keypoints_scaled(*scaled_args(jobs), want_score=referee, want_pyramid=referee, want_scale=referee)
+
+    def scaled_arrays(r):    # score and pyramid are lists of layers of different shapes: their bytes one behind the other
+        return {k: np.frombuffer(b"".join(np.ascontiguousarray(a).tobytes() for a in v), np.uint8) if isinstance(v, list) else np.asarray(v)
+                for k, v in r.items()}
+
+    for name in DSC.NAMES:
+        jobs = DSC.cases(name)
+        for referee in (False, True):
+            tag = f"{name}_referee{int(referee)}"
+            for j, job in enumerate(jobs):
+                r, = detect_scaled([job], referee)
+                record(f"detect_scaled/{tag}_job{j}", **scaled_arrays(r))
+            for j, r in enumerate(detect_scaled(jobs, referee)):
+                record(f"detect_scaled_batch/{tag}_job{j}", **scaled_arrays(r))
+    chain = DSC.cases("capacity") + DSC.cases("edges") + DSC.cases("mixed")[:20]
+    cam = F.camera(BC.CAMERAS["equi"]["intr"], 2, 160, 120)
+    images, threshold, octaves, *rest = scaled_args(chain)
+    for j, r in enumerate(fe.detect_scaled_and_describe(images, threshold, octaves, cam, [0.2, 0.9, 0.38], *rest, want_score=True, want_pyramid=True,
+                                                        want_scale=True, want=ALL)):
+        record(f"detect_scaled_chain/job{j}", **scaled_arrays(r))
 fe.close()
 
 if args.cases:
